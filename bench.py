@@ -398,7 +398,37 @@ def parse_args():
     ap.add_argument("--worker-timeout", type=float, default=float(os.environ.get("M3T_BENCH_WORKER_TIMEOUT", "900")),
                     help="N > 1: seconds a worker may go WITHOUT a heartbeat (one per step and phase) before its supervisor declares it stuck "
                          "and starts the fallback")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: see dump_outputs()")
     return ap.parse_args()
+
+
+DUMP_GRAD_SAMPLE = 1 << 22         # gradient values kept by --dump-outputs (16 MB of fp32; the whole flat gradient is ~106 MB)
+
+
+def dump_outputs(out_dir, model, ddp, res):
+    """--dump-outputs: what a caller of the timed step receives, from its last timed call, as float32 / float64 .npy files
+    (about 17 MB in all).  y [B, T, 9] (the model's output), loss [1], stats [8] (ops.va_loss), grad_norm [1] (the norm the clip
+    saw), grad_param_norms [one per parameter tensor] (fp64 L2 norm of every parameter's clipped gradient, named_parameters() order) and
+    grad_sample: DUMP_GRAD_SAMPLE entries of the clipped gradients concatenated in that order, at sorted indices drawn by
+    np.random.RandomState(0) -- the same indices in every run with the same arguments."""
+    loss, stats, y = res
+    os.makedirs(out_dir, exist_ok=True)
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).cpu().numpy() for p in model.parameters()]
+    flat = np.concatenate(grads).astype(np.float32, copy=False)
+    k = min(flat.size, DUMP_GRAD_SAMPLE)
+    idx = np.sort(np.random.RandomState(0).choice(flat.size, k, replace=False))
+    arrays = {
+        "y": y.detach().float().cpu().numpy(),
+        "loss": loss.detach().double().reshape(1).cpu().numpy(),
+        "stats": stats.detach().double().reshape(-1).cpu().numpy(),
+        "grad_norm": torch.as_tensor(ddp.last_norm).detach().double().reshape(-1).cpu().numpy(),
+        "grad_param_norms": np.array([np.linalg.norm(g.astype(np.float64)) for g in grads]),
+        "grad_sample": flat[idx],
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def _free_port():
@@ -564,9 +594,13 @@ def worker(args):
     # the step (m3t/workloads.py): zero_grad -> forward -> ccc_mtl loss -> backward -> all-reduce (N > 1) + 1/N + clip 1.0.
     # tests/test_gpu_bench_path.py runs this same function at B=32 x T=300 against a reference-generated golden.
     ddp, step_fn = make_c3_step(model, batch, max_norm=1.0)
+    last = [None]                                   # --dump-outputs: (loss, stats, y) of the latest step
 
     def step():
-        return step_fn()[0].detach()
+        res = step_fn()
+        if args.dump_outputs:
+            last[0] = res
+        return res[0].detach()
 
     def fence():
         torch.cuda.synchronize()
@@ -633,6 +667,9 @@ def worker(args):
               file=sys.stderr, flush=True)
         print("# host per-step ms: " + " ".join("%.2f" % ((b - a) * 1e3) for a, b in zip([t0] + host_marks[:-1], host_marks)),
               file=sys.stderr, flush=True)
+    dumped = None
+    if args.dump_outputs and rank == 0:             # outside the timed region, before the enqueue probe below runs more steps
+        dumped = dump_outputs(args.dump_outputs, model, ddp, last[0])
     beat()
     # host enqueue cost with an IDLE queue: the GPU is parked behind a spin kernel while the host enqueues whole steps, so
     # the figure has no queue back-pressure in it -- `host_enqueue_ms_per_step` above mixes the two (a host that runs ahead of the GPU
@@ -790,6 +827,8 @@ def worker(args):
             "allreduce": allreduce,
             "memory_roofline_frac": round((clips / dt) * 66.15e6 / (HBM_PEAK_GBS * 1e9 * world), 5),
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if fallback:
             out["fallback"] = ("launch-per-step scans + gradient buckets overlapped with backward, in fresh worker processes, after: %s"
                                % fallback)

@@ -207,7 +207,11 @@ def test_init_digests_match_reference_rng_stream():
         torch.manual_seed(12345)
         m = ctor()
         for n, p in m.named_parameters():
-            np.testing.assert_allclose(grad_digest(p.detach().numpy()), g["%s.%s" % (tag, n)], rtol=1e-6, atol=1e-7,
+            # the GRU's per-gate orthogonal weight_hh comes out of a LAPACK QR, whose float32 rounding depends on the host's BLAS code
+            # path (AVX-512 vs AVX2 kernels: ~1 ulp per entry, ~1e-6 on the sum of a 768-entry tensor); another RNG order moves these
+            # digests by more than 1.  Every other parameter is a plain draw and must match to the last bits.
+            atol = 4e-6 if "weight_hh" in n else 1e-7
+            np.testing.assert_allclose(grad_digest(p.detach().numpy()), g["%s.%s" % (tag, n)], rtol=1e-6, atol=atol,
                                        err_msg="%s.%s" % (tag, n))
 
 
