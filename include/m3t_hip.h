@@ -716,6 +716,81 @@ int m3t_power_to_db(const float* s, long long n, float amin, float top_db, float
 int m3t_stack_context(const float* mel, long long n_rows, int n_mels, long long start, int w_len, int step, int width,
                       float* out, void* stream);
 
+
+/* ---------------------------------------------------------------------------------
+ * Attention decoder of --fusion_type att_dec (csrc/attdec.hip).  Replaces the decoder loop of AttEncDec.forward with
+ * Decoder.forward and Attention.forward inside it (reference models/rnn.py:93-136, 145-165) and its autograd.
+ * H = hidden width (H % 64 == 0, H <= 512), E = 2 (input and output width), B >= 1 clips, T >= 1 encoder frames (<= 8192),
+ * L >= 1 output frames (T, or the target's length with teacher forcing), S = L - 1 decoder steps.
+ * Step t = 1 .. L-1, with h_0 = h0, y_in = y0 (or 0) at t = 1:
+ *   a = W_ah h_{t-1}, s_tau = v . relu(P[tau] + a), alpha = softmax_tau(s), c = sum_tau alpha_tau enc[tau],
+ *   h_t = GRUCell([y_in, c], h_{t-1}), y_t = W_o [h_t, c] + b_o -> out[:, t];  y_in of step t+1 = tf[t] ? trg[:, t] : y_t.
+ * P = enc W_ae^T + b_a is the caller's (m3t_sgemm), W_a = [W_ah | W_ae] is the attn weight [H][2H]. */
+typedef struct {
+    const float* enc;     /* [B][T][H] encoder outputs                                              */
+    const float* P;       /* [B][T][H] enc W_ae^T + b_a                                             */
+    const float* h0;      /* [B][H]                                                                 */
+    const float* w_a;     /* [H][2H] attention weight (W_ah = columns [0, H))                       */
+    const float* v;       /* [H]                                                                    */
+    const float* w_ih;    /* [3H][2 + H], gates r | z | n as nn.GRU                                 */
+    const float* w_hh;    /* [3H][H]                                                                */
+    const float* b_ih;    /* [3H]                                                                   */
+    const float* b_hh;    /* [3H]                                                                   */
+    const float* w_o;     /* [2][2H]                                                                */
+    const float* b_o;     /* [2]                                                                    */
+    const float* y0;      /* [B][2] input of step 1, NULL = zeros                                   */
+    const float* trg;     /* [B][L][2] teacher target, or NULL                                      */
+    const int* tf;        /* [L] device flags: tf[t] != 0 feeds trg[:, t] to step t+1; needs trg     */
+    float* out;           /* [B][L][2] (out[:, 0] = 0)                                              */
+    float* h_last;        /* [B][H] h_{L-1}                                                         */
+    float* G;             /* [B][4H] scratch: [W_hh h + b_hh | W_ah h]                               */
+    /* per-step records: save != 0 -> S records each (backward), save == 0 -> scratch (alpha, gates: one record; x, hs: two) */
+    float* alpha;         /* [S][B][T]                                                              */
+    float* a_save;        /* [S][B][H] a of each step (save only)                                    */
+    float* x;             /* [S][B][2 + H] the step's input [y_in, c]                                */
+    float* gates;         /* [S][B][4H] r, z, n, W_hn h + b_hn                                       */
+    float* hs;            /* [L][B][H] h_0 .. h_{L-1}                                                */
+    /* backward (m3t_attdec_bwd / m3t_attdec_post) */
+    const float* dout;    /* [B][L][2]                                                              */
+    const float* dh_last; /* [B][H] gradient of h_last, or NULL                                     */
+    float* dgi;           /* [S][B][3H] gradient of W_ih x + b_ih                                   */
+    float* dgh;           /* [S][B][3H] gradient of W_hh h + b_hh                                   */
+    float* dc;            /* [S][B][H] gradient of the context                                      */
+    float* da;            /* [S][B][H] gradient of a                                                */
+    float* dy;            /* [S][B][2] total gradient of y_t (output + feedback)                    */
+    float* dP;            /* [B][T][H] gradient of P (zeroed by the call, then accumulated per step) */
+    float* dv_acc;        /* [B][H] per-clip gradient of v (zeroed by the call)                      */
+    float* dh;            /* [B][H] -> gradient of h0                                                */
+    float* dy0;           /* [B][2] gradient of y0, or NULL                                          */
+    float* w_iht;         /* [2 + H][3H] scratch (W_ih^T)                                            */
+    float* wt;            /* [H][4H] scratch ([W_hh^T | W_ah^T])                                     */
+    float* dyin;          /* [B][2] scratch                                                         */
+    float* dhz;           /* [B][H] scratch                                                         */
+    int B, T, L, H, save;
+} m3t_attdec_args;
+/* forward loop: a prologue (h_0 -> x, G) and three launches per step (attention, GRU cell, [W_hh; W_ah] h_t with the output layer);
+ * no host synchronisation.  save = 0 (inference) keeps only scratch records. */
+int m3t_attdec_fwd(const m3t_attdec_args* args, void* stream);
+/* backward loop over the records of a save != 0 forward (L >= 2): four launches per step (cell backward with the output and feedback
+ * gradient, context gradient W_ih[:, 2:]^T dgi + W_o[:, H:]^T dy, attention backward with dP += .. in place, dh_{t-1}).  The
+ * feedback W_ih[:, :2]^T dgi_{t+1} reaches y_t only where step t+1 was fed y_t (not teacher-forced).  The caller finishes with
+ * m3t_sgemm / m3t_colsum over the records (dW_ih = dgi^T x, dW_hh = dgh^T h_{t-1}, dW_ah = da^T h_{t-1}, dW_ae = dP^T enc,
+ * d enc = dP W_ae + m3t_attdec_post) */
+int m3t_attdec_bwd(const m3t_attdec_args* args, void* stream);
+/* after m3t_attdec_bwd: dw_o [2][2H], db_o [2], dv [H] (all three or none), and d_enc [B][T][H] += sum_t alpha_t^T dc_t per clip
+ * (d_enc NULL: skipped).  Fixed-order sums. */
+int m3t_attdec_post(const m3t_attdec_args* args, float* dw_o, float* db_o, float* dv, float* d_enc, void* stream);
+/* Attention.forward alone (reference models/rnn.py:93-111): alpha [B][T] from P, a ([B] rows of lda) and v; c [B][H] (optional) the
+ * context.  Backward from d alpha: dP += .., da = .., dv_acc += .. (per clip; the caller zeroes dP and dv_acc). */
+int m3t_attdec_attn_fwd(const float* enc, const float* P, const float* a, int lda, const float* v, float* alpha, float* c,
+                        int B, int T, int H, void* stream);
+int m3t_attdec_attn_bwd(const float* enc, const float* P, const float* a, const float* v, const float* alpha,
+                        const float* dalpha, float* dP, float* da, float* dv_acc, int B, int T, int H, void* stream);
+/* the sum of a bidirectional GRU's two halves, y [rows][H] = x[:, :H] + x[:, H:] (reference models/rnn.py:153), and its gradient
+ * dx [rows][2H] = [dy, dy] */
+int m3t_attdec_sum_halves(const float* x, float* y, size_t rows, int H, void* stream);
+int m3t_attdec_dup_halves(const float* dy, float* dx, size_t rows, int H, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,14 @@ class WindowProblem(C.Structure):
     _fields_ = [("A", _f), ("B", _f), ("C", _f), ("bias", _f), ("amax_a", _f), ("amax_b", _f), ("accumulate", _i)]
 
 
+class AttDecArgs(C.Structure):
+    """m3t_attdec_args of include/m3t_hip.h (field order and types as declared there)."""
+    _fields_ = [(n, _f) for n in ("enc", "P", "h0", "w_a", "v", "w_ih", "w_hh", "b_ih", "b_hh", "w_o", "b_o", "y0", "trg", "tf",
+                                  "out", "h_last", "G", "alpha", "a_save", "x", "gates", "hs", "dout", "dh_last", "dgi", "dgh",
+                                  "dc", "da", "dy", "dP", "dv_acc", "dh", "dy0", "w_iht", "wt", "dyin", "dhz")] + \
+        [(n, _i) for n in ("B", "T", "L", "H", "save")]
+
+
 M3T_WINDOW_BATCH = 8
 
 # name -> argtypes; the test-suite checks that every symbol of include/m3t_hip.h is here and exported.
@@ -145,6 +153,13 @@ SIGNATURES = {
     "m3t_grad_dead_check": [_f, _s],
     "m3t_adam_step": [_f, _f, _f, _f, _z, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, _f, _s],
     "m3t_sgd_step": [_f, _f, _f, _z, C.c_float, C.c_float, C.c_float, _i, _f, _s],
+    "m3t_attdec_fwd": [C.POINTER(AttDecArgs), _s],
+    "m3t_attdec_bwd": [C.POINTER(AttDecArgs), _s],
+    "m3t_attdec_post": [C.POINTER(AttDecArgs), _f, _f, _f, _f, _s],
+    "m3t_attdec_attn_fwd": [_f, _f, _f, _i, _f, _f, _f, _i, _i, _i, _s],
+    "m3t_attdec_attn_bwd": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _s],
+    "m3t_attdec_sum_halves": [_f, _f, _z, _i, _s],
+    "m3t_attdec_dup_halves": [_f, _f, _z, _i, _s],
 }
 
 RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t}

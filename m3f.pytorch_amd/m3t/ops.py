@@ -3358,3 +3358,192 @@ def conv2d(x, w, b, stride, padding):
         return _Conv3dGemmWgrad.apply(x, w, b, tuple(stride), tuple(padding), True)
     finally:
         _X_SLOT[0] = None
+
+
+# ----------------------------------------------------------------------------- attention decoder (--fusion_type att_dec)
+# Reference models/rnn.py:84-165 (Attention, Decoder, AttEncDec).  The T-1 step recurrence runs in csrc/attdec.hip: one library call per
+# pass enqueues the whole loop (3 launches a step forward, 4 backward); P = enc W_ae^T + b_a and every weight gradient are GEMMs over the
+# per-step records.  The decoder is fp32 whatever ops.precision() says: its GEMMs take the six-product fp32-accurate form (flags 0), its
+# loop kernels are plain fp32 -- "bf16" / "high" / "x6" leave it unchanged.
+def _ad_gemm(transA, transB, M, N, K, A, a_off, lda, Bm, b_off, ldb, Cm, c_off, ldc, bias=None, accumulate=False):
+    sgemm(transA, transB, M, N, K, A, a_off, lda, Bm, b_off, ldb, Cm, c_off, ldc, bias=bias, accumulate=accumulate, prec=0)
+
+
+def _ad_proj(enc, w_a, b_a):
+    """P = enc W_ae^T + b_a, W_ae = w_a[:, H:]"""
+    B, T, H = enc.shape
+    P = torch.empty_like(enc)
+    _ad_gemm(0, 1, B * T, H, H, enc, 0, H, w_a, H, 2 * H, P, 0, H, bias=b_a)
+    return P
+
+
+def teacher_forcing_mask(L, ratio, rng=None):
+    """The reference's teacher-forcing draws (models/rnn.py:160): one `random.random()` per step t = 1 .. L-1, in order, from Python's
+    module-level generator (or `rng`); tf[t] = 1 when step t+1 is fed the target.  Returns a list of L ints (tf[0] = 0)."""
+    import random
+    draw = (rng or random).random
+    return [0] + [1 if draw() < ratio else 0 for _ in range(1, L)]
+
+
+def _ad_args(**kw):
+    a = _lib.AttDecArgs()
+    for k, v in kw.items():
+        setattr(a, k, v if isinstance(v, int) and k in ("B", "T", "L", "H", "save") else (_p(v) if isinstance(v, torch.Tensor) else v))
+    return a
+
+
+class _AttDecode(torch.autograd.Function):
+    """outputs [B, L, 2] of AttEncDec's decoder loop (out[:, 0] = 0), h_{L-1} and the last step's attention weights [B, T]."""
+
+    @staticmethod
+    def forward(ctx, enc, h0, y0, w_a, b_a, v, w_ih, w_hh, b_ih, b_hh, w_o, b_o, trg, tf, L, save):
+        enc = _req(enc.contiguous(), "enc")
+        h0 = _req(h0.contiguous(), "h0")
+        B, T, H = enc.shape
+        S = L - 1
+        dev = enc.device
+        ws = [_req(t, n) for t, n in ((w_a, "attn.weight"), (v, "v"), (w_ih, "weight_ih"), (w_hh, "weight_hh"), (b_ih, "bias_ih"),
+                                      (b_hh, "bias_hh"), (w_o, "out.weight"), (b_o, "out.bias"))]
+        P = _ad_proj(enc, w_a, b_a)
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)       # noqa: E731
+        out, h_last, G = f(B, L, 2), f(B, H), f(B, 4 * H)
+        if save:
+            alpha, a_save, x, gates, hs = f(S, B, T), f(S, B, H), f(S, B, H + 2), f(S, B, 4 * H), f(L, B, H)
+        else:
+            alpha, a_save, x, gates, hs = f(1, B, T), None, f(2, B, H + 2), f(1, B, 4 * H), f(2, B, H)
+        args = _ad_args(enc=enc, P=P, h0=h0, w_a=w_a, v=v, w_ih=w_ih, w_hh=w_hh, b_ih=b_ih, b_hh=b_hh, w_o=w_o, b_o=b_o,
+                        y0=y0, trg=trg, tf=tf, out=out, h_last=h_last, G=G, alpha=alpha, a_save=a_save, x=x, gates=gates, hs=hs,
+                        B=B, T=T, L=L, H=H, save=int(save))
+        _lib.check(lib().m3t_attdec_fwd(C.byref(args), _stream()), "m3t_attdec_fwd")
+        alpha_last = alpha[-1].clone()
+        ctx.mark_non_differentiable(alpha_last)
+        ctx.dims = (B, T, L, H)
+        ctx.has_y0 = y0 is not None
+        if save:
+            ctx.save_for_backward(enc, P, h0, w_a, v, w_ih, w_hh, w_o, alpha, a_save, x, gates, hs, trg, tf)
+        del ws
+        return out, h_last, alpha_last
+
+    @staticmethod
+    def backward(ctx, dout, dh_last, _dalpha):
+        enc, P, h0, w_a, v, w_ih, w_hh, w_o, alpha, a_save, x, gates, hs, trg, tf = ctx.saved_tensors
+        B, T, L, H = ctx.dims
+        S, N, dev = L - 1, (L - 1) * B, enc.device
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)       # noqa: E731
+        dout = _req(dout.contiguous(), "dout") if dout is not None else torch.zeros(B, L, 2, device=dev)
+        dh_last = _req(dh_last.contiguous(), "dh_last") if dh_last is not None else None
+        dgi, dgh, dc, da, dy = f(S, B, 3 * H), f(S, B, 3 * H), f(S, B, H), f(S, B, H), f(S, B, 2)
+        dP, dv_acc, dh, dy0 = f(B, T, H), f(B, H), f(B, H), (f(B, 2) if ctx.has_y0 else None)
+        args = _ad_args(enc=enc, P=P, h0=h0, w_a=w_a, v=v, w_ih=w_ih, w_hh=w_hh, w_o=w_o, trg=trg, tf=tf, alpha=alpha, a_save=a_save,
+                        x=x, gates=gates, hs=hs, dout=dout, dh_last=dh_last, dgi=dgi, dgh=dgh, dc=dc, da=da, dy=dy, dP=dP, dv_acc=dv_acc,
+                        dh=dh, dy0=dy0, w_iht=f(H + 2, 3 * H), wt=f(H, 4 * H), dyin=f(B, 2), dhz=f(B, H), B=B, T=T, L=L, H=H, save=1)
+        _lib.check(lib().m3t_attdec_bwd(C.byref(args), _stream()), "m3t_attdec_bwd")
+        dw_a, db_a, dw_ih, db_ih, dw_hh, db_hh = f(H, 2 * H), f(H), f(3 * H, H + 2), f(3 * H), f(3 * H, H), f(3 * H)
+        dw_o, db_o, dv, denc = f(2, 2 * H), f(2), f(H), f(B, T, H)
+        _ad_gemm(1, 0, H, H, N, da, 0, H, hs, 0, H, dw_a, 0, 2 * H)                 # dW_ah = sum_t da_t^T h_{t-1}
+        _ad_gemm(1, 0, H, H, B * T, dP, 0, H, enc, 0, H, dw_a, H, 2 * H)            # dW_ae = dP^T enc
+        colsum(dP, 0, B * T, H, H, db_a)
+        _ad_gemm(1, 0, 3 * H, H + 2, N, dgi, 0, 3 * H, x, 0, H + 2, dw_ih, 0, H + 2)   # dW_ih = sum_t dgi_t^T [y_in, c]_t
+        colsum(dgi, 0, N, 3 * H, 3 * H, db_ih)
+        _ad_gemm(1, 0, 3 * H, H, N, dgh, 0, 3 * H, hs, 0, H, dw_hh, 0, H)           # dW_hh = sum_t dgh_t^T h_{t-1}
+        colsum(dgh, 0, N, 3 * H, 3 * H, db_hh)
+        _ad_gemm(0, 0, B * T, H, H, dP, 0, H, w_a, H, 2 * H, denc, 0, H)            # d enc = dP W_ae ...
+        _lib.check(lib().m3t_attdec_post(C.byref(args), _p(dw_o), _p(db_o), _p(dv), _p(denc), _stream()), "m3t_attdec_post")  # ... + sum_t alpha_t^T dc_t
+        return denc, dh, dy0, dw_a, db_a, dv, dw_ih, dw_hh, db_ih, db_hh, dw_o, db_o, None, None, None, None
+
+
+def att_decode(enc, h0, w_a, b_a, v, w_ih, w_hh, b_ih, b_hh, w_o, b_o, trg=None, tf_mask=None, y0=None, L=None):
+    """AttEncDec's decoder loop (reference models/rnn.py:145-165) on the HIP kernels.
+    enc [B,T,H] encoder outputs (directions summed), h0 [B,H]; w_a/b_a: attention.attn, v: attention.v; w_ih, w_hh, b_ih, b_hh: the
+    decoder GRU's layer 0 ([3H, 2+H] / [3H, H]); w_o/b_o: out.  trg [B,L,2] with tf_mask (teacher_forcing_mask(L, ratio), drawn on the
+    host and uploaded once): teacher forcing; y0 [B,2]: input of step 1 (default zeros).  Returns (outputs [B,L,2], h_{L-1} [B,H],
+    attention weights of the last step [B,T]).  L defaults to trg's length, else T.  With L == 1 there is no step: zeros, h0,
+    and no graph, as in the reference.  The decoder runs in fp32 under every ops.precision() mode (bf16 / high / x6 included)."""
+    B, T, H = enc.shape
+    if L is None:
+        L = trg.size(1) if trg is not None else T
+    if H % 64 or H > 512:
+        raise M3THipError("att_decode: H must be a multiple of 64 up to 512, got %d" % H)
+    if w_ih.shape != (3 * H, 2 + H) or w_hh.shape != (3 * H, H) or w_a.shape != (H, 2 * H) or w_o.shape != (2, 2 * H):
+        raise M3THipError("att_decode: weight shapes do not match H = %d with 2 inputs and 2 outputs" % H)
+    if L <= 1:
+        alpha = torch.empty(B, T, dtype=torch.float32, device=enc.device)
+        return enc.new_zeros(B, max(L, 0), 2), h0, alpha
+    tf = None
+    if trg is not None:
+        trg = _req(trg.detach().to(enc.device, torch.float32).contiguous(), "trg")
+        if trg.shape != (B, L, 2):
+            raise M3THipError("att_decode: trg must be [B, L, 2]")
+        mask = list(tf_mask) if tf_mask is not None else [0] * L
+        if len(mask) != L:
+            raise M3THipError("att_decode: tf_mask must have L entries")
+        tf = torch.tensor(mask, dtype=torch.int32).to(enc.device, non_blocking=True)
+    if y0 is not None:
+        y0 = _req(y0.contiguous(), "y0")
+    params = (enc, h0, y0, w_a, b_a, v, w_ih, w_hh, b_ih, b_hh, w_o, b_o)
+    save = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params)
+    return _AttDecode.apply(enc, h0, y0, w_a, b_a, v, w_ih, w_hh, b_ih, b_hh, w_o, b_o, trg, tf, int(L), bool(save))
+
+
+class _AttnWeights(torch.autograd.Function):
+    """Attention.forward (reference models/rnn.py:93-111): softmax_tau(v . relu(W_a [h, enc_tau] + b_a)) -> [B, T]"""
+
+    @staticmethod
+    def forward(ctx, hidden, enc, w_a, b_a, v):
+        enc, hidden = _req(enc.contiguous(), "enc"), _req(hidden.contiguous(), "hidden")
+        B, T, H = enc.shape
+        P = _ad_proj(enc, w_a, b_a)
+        a = torch.empty(B, H, dtype=torch.float32, device=enc.device)
+        _ad_gemm(0, 1, B, H, H, hidden, 0, H, w_a, 0, 2 * H, a, 0, H)
+        alpha = torch.empty(B, T, dtype=torch.float32, device=enc.device)
+        _lib.check(lib().m3t_attdec_attn_fwd(_p(enc), _p(P), _p(a), H, _p(v), _p(alpha), None, B, T, H, _stream()), "m3t_attdec_attn_fwd")
+        ctx.save_for_backward(hidden, enc, P, a, w_a, v, alpha)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, dalpha):
+        hidden, enc, P, a, w_a, v, alpha = ctx.saved_tensors
+        B, T, H = enc.shape
+        dalpha = _req(dalpha.contiguous(), "dalpha")
+        dP = torch.zeros_like(enc)
+        dv_acc = torch.zeros(B, H, dtype=torch.float32, device=enc.device)
+        da = torch.empty_like(dv_acc)
+        _lib.check(lib().m3t_attdec_attn_bwd(_p(enc), _p(P), _p(a), _p(v), _p(alpha), _p(dalpha), _p(dP), _p(da), _p(dv_acc), B, T, H,
+                                             _stream()), "m3t_attdec_attn_bwd")
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=enc.device)       # noqa: E731
+        dw_a, db_a, dv, dh, denc = f(H, 2 * H), f(H), f(H), f(B, H), f(B, T, H)
+        _ad_gemm(1, 0, H, H, B, da, 0, H, hidden, 0, H, dw_a, 0, 2 * H)
+        _ad_gemm(1, 0, H, H, B * T, dP, 0, H, enc, 0, H, dw_a, H, 2 * H)
+        colsum(dP, 0, B * T, H, H, db_a)
+        colsum(dv_acc, 0, B, H, H, dv)
+        _ad_gemm(0, 0, B, H, H, da, 0, H, w_a, 0, 2 * H, dh, 0, H)
+        _ad_gemm(0, 0, B * T, H, H, dP, 0, H, w_a, H, 2 * H, denc, 0, H)
+        return dh, denc, dw_a, db_a, dv
+
+
+def attention_weights(hidden, enc, w_a, b_a, v):
+    return _AttnWeights.apply(hidden, enc, w_a, b_a, v)
+
+
+class _SumHalves(torch.autograd.Function):
+    """x [.., 2H] -> x[..., :H] + x[..., H:] (reference models/rnn.py:153: the encoder's two directions summed)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _req(x.contiguous(), "x")
+        H = x.shape[-1] // 2
+        y = torch.empty(x.shape[:-1] + (H,), dtype=x.dtype, device=x.device)
+        _lib.check(lib().m3t_attdec_sum_halves(_p(x), _p(y), x.numel() // (2 * H), H, _stream()), "m3t_attdec_sum_halves")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _req(dy.contiguous(), "dy")
+        H = dy.shape[-1]
+        dx = torch.empty(dy.shape[:-1] + (2 * H,), dtype=dy.dtype, device=dy.device)
+        _lib.check(lib().m3t_attdec_dup_halves(_p(dy), _p(dx), dy.numel() // H, H, _stream()), "m3t_attdec_dup_halves")
+        return dx
+
+
+def sum_halves(x):
+    return _SumHalves.apply(x)

@@ -13,8 +13,9 @@ pooling kernels too (models/backbone.py; rounds 4-6).  If pytorch_lightning is
 installed the class derives from pl.LightningModule exactly as the reference does; without it
 (this image) it is a plain nn.Module with the same hooks.
 
-Validation/test window stitching is host glue in m3t/stitch.py.  Out of scope: dataloaders
-(need the Aff-Wild2 dataset and cv2), the LR range finder, `--fusion_type att_dec`.
+`--fusion_type att_dec` (model.py:96-97,119-126) runs the attention encoder-decoder of models/rnn.py (AttEncDec) on the
+decoder kernels of csrc/attdec.hip.  Validation/test window stitching is host glue in m3t/stitch.py.
+Out of scope: dataloaders (need the Aff-Wild2 dataset and cv2), the LR range finder.
 """
 import os
 from argparse import ArgumentParser
@@ -25,7 +26,7 @@ from torch.nn import functional as F
 
 from m3t import ops
 from .backbone import VA_3DResNet, VA_3DVGGM, VA_3DVGGM_Split
-from .rnn import GRU, run_grus, run_grus_cat
+from .rnn import GRU, AttEncDec, run_grus, run_grus_cat
 from .att_fusion import AttFusion
 from .utils import concordance_cc2, mse  # noqa: F401  (re-exported like the reference)
 
@@ -76,6 +77,8 @@ class AffWild2VA(_Base):
                 self.fusion = GRU(512, hp.num_hidden, 2, fc_outputs, hp.num_fc_layers)
             elif hp.fusion_type == 'concat':
                 self.fusion = GRU(512 * 2, hp.num_hidden, 2, fc_outputs, hp.num_fc_layers)
+            elif hp.fusion_type == 'att_dec':
+                self.fusion = AttEncDec()           # 2 outputs (valence, arousal) whatever the loss (model.py:96-97)
             else:
                 raise NotImplementedError("fusion_type '%s' is outside the MI355X hot path" % hp.fusion_type)
         self.history = {'lr': [], 'loss': []}
@@ -103,6 +106,11 @@ class AffWild2VA(_Base):
             video_feats = ops.linear(video_feats, self.proj_v.weight, self.proj_v.bias, 0)
             if hp.fusion_type == 'attention':
                 return self.fusion(self.att_fuse(audio_feats, video_feats))
+            if hp.fusion_type == 'att_dec':
+                features = torch.cat((audio_feats, video_feats), dim=-1)
+                if 'arousal' in batch.keys():       # the reference's condition (model.py:121): teacher forcing on 'valence' / 'arousal'
+                    return self.fusion(features, torch.stack((batch['valence'], batch['arousal']), dim=-1))
+                return self.fusion(features)
             return self.fusion(torch.cat((audio_feats, video_feats), dim=-1))
         return self.visual(x, batch['se_features'], batch['se_features'])
 
@@ -136,6 +144,10 @@ class AffWild2VA(_Base):
         if 'mse' not in hp.loss:
             assert 'ccc' in hp.loss, 'invalid loss specification'
         C_ = y_hat.size(-1)
+        if mtl and C_ < 9:
+            # fusion_type att_dec emits (valence, arousal) only; the reference would index y_hat[..., 7] out of range (model.py:152)
+            raise ValueError("loss '%s' needs 9 outputs (7 expression logits, valence, arousal), the model gives %d "
+                             "(fusion_type att_dec has 2: use a loss without 'mtl')" % (hp.loss, C_))
         return ops.va_loss(y_hat, batch['label_valence'], batch['label_arousal'],
                            batch['class_expr'] if mtl else None, batch['expr_valid'] if mtl else None,
                            iv=7 if mtl else C_ - 2, ia=C_ - 1, n_expr=7 if mtl else 0,

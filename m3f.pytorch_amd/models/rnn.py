@@ -6,8 +6,9 @@ names/shapes (`gru.weight_ih_l{k}[_reverse]`, `gru.weight_hh_...`, `gru.bias_..`
 `fc.*`), same initialisation recipe (rnn.py:57-69) drawn in the same RNG order.
 The arithmetic runs in libm3t_hip.so: input projections and FC layers on the fp32-MFMA
 GEMM, the recurrence in the grouped per-step scan kernels (m3t.ops.multi_bigru).
-`Attention/Decoder/AttEncDec` (rnn.py:84-165, --fusion_type att_dec) are out of scope
-(non-deterministic teacher forcing).
+`Attention`, `Decoder`, `AttEncDec` (rnn.py:84-165, --fusion_type att_dec): same constructors, attribute names
+and init order; the decoder loop runs in csrc/attdec.hip (m3t.ops.att_decode), greedy or teacher-forced with the
+reference's `random.random()` draws (m3t.ops.teacher_forcing_mask).  One decoder layer, input and output width 2.
 """
 import math
 
@@ -20,15 +21,16 @@ from m3t import ops
 
 class BiGRUParameters(nn.Module):
     """Parameter holder with nn.GRU's names, shapes, registration order and default init
-    (bidirectional, batch_first).  No forward: the scan lives in m3t.ops."""
+    (bidirectional unless told otherwise, batch_first).  No forward: the scan lives in m3t.ops."""
 
-    def __init__(self, input_size, hidden_size, num_layers):
+    def __init__(self, input_size, hidden_size, num_layers, bidirectional=True):
         super().__init__()
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
+        self.bidirectional = bidirectional
         H = hidden_size
         for layer in range(num_layers):
-            in_l = input_size if layer == 0 else 2 * H
-            for suffix in ("", "_reverse"):
+            in_l = input_size if layer == 0 else (2 if bidirectional else 1) * H
+            for suffix in ("", "_reverse") if bidirectional else ("",):
                 tag = "l%d%s" % (layer, suffix)
                 self.register_parameter("weight_ih_" + tag, nn.Parameter(torch.empty(3 * H, in_l)))
                 self.register_parameter("weight_hh_" + tag, nn.Parameter(torch.empty(3 * H, H)))
@@ -146,3 +148,69 @@ def run_grus_cat(modules, inputs, lo, hi):
         return outs[:lo + 1] + outs[hi:]
     outs = run_grus(modules, inputs)
     return outs[:lo] + [torch.cat(outs[lo:hi], dim=-1)] + outs[hi:]
+
+
+class Attention(nn.Module):
+    """Reference models/rnn.py:84-111: additive attention over the encoder frames."""
+
+    def __init__(self, hidden_size):
+        super().__init__()
+        self.hidden_size = hidden_size
+        self.attn = nn.Linear(self.hidden_size * 2, hidden_size)
+        self.v = nn.Parameter(torch.rand(hidden_size))
+        stdv = 1. / math.sqrt(self.v.size(0))
+        self.v.data.uniform_(-stdv, stdv)
+
+    def forward(self, hidden, encoder_outputs):
+        """hidden [B,H], encoder_outputs [B,T,H] -> softmax weights [B,1,T]"""
+        return ops.attention_weights(hidden, encoder_outputs, self.attn.weight, self.attn.bias, self.v).unsqueeze(1)
+
+
+class Decoder(nn.Module):
+    """Reference models/rnn.py:114-142: one attention + GRU-cell + output step.  The kernels fix the input and output width at 2
+    (AttEncDec's) and the depth at one layer."""
+
+    def __init__(self, embed_size=128, hidden_size=512, output_size=2, n_layers=1):
+        super().__init__()
+        if n_layers != 1:
+            raise NotImplementedError("Decoder: only n_layers = 1 (the reference's AttEncDec) runs on the HIP decoder")
+        if embed_size != 2 or output_size != 2:
+            raise NotImplementedError("Decoder: the HIP decoder feeds its 2 outputs back as its 2 inputs (embed_size = output_size = 2)")
+        self.embed_size = embed_size
+        self.hidden_size = hidden_size
+        self.output_size = output_size
+        self.n_layers = n_layers
+        self.attention = Attention(hidden_size)
+        self.gru = BiGRUParameters(hidden_size + embed_size, hidden_size, n_layers, bidirectional=False)
+        self.out = nn.Linear(hidden_size * 2, output_size)
+
+    def weights(self):
+        g = self.gru
+        return (self.attention.attn.weight, self.attention.attn.bias, self.attention.v, g.weight_ih_l0, g.weight_hh_l0,
+                g.bias_ih_l0, g.bias_hh_l0, self.out.weight, self.out.bias)
+
+    def forward(self, inputs, last_hidden, encoder_outputs):
+        """inputs [B,2], last_hidden [1,B,H], encoder_outputs [B,T,H] -> (output [B,2], hidden [1,B,H], attn_weights [B,1,T])"""
+        out, h, _ = ops.att_decode(encoder_outputs, last_hidden[-1], *self.weights(), y0=inputs, L=2)
+        # the weights the step used, as a differentiable output of their own (att_decode's copy carries no gradient)
+        attn_weights = self.attention(last_hidden[-1], encoder_outputs)
+        return out[:, 1], h.unsqueeze(0), attn_weights
+
+
+class AttEncDec(nn.Module):
+    """Reference models/rnn.py:145-165: BiGRU encoder, directions summed, attention decoder over T-1 steps (greedy, or teacher-forced
+    with probability teacher_forcing_ratio per step when a target is given)."""
+
+    def __init__(self):
+        super().__init__()
+        self.encoder = GRU(1024, 512, 2, -1, return_h=True)
+        self.decoder = Decoder(2, 512, 2, 1)
+
+    def forward(self, src, trg=None, teacher_forcing_ratio=0.5):
+        max_len = trg.size(1) if trg is not None else src.size(1)
+        encoder_output, hidden = self.encoder(src)
+        encoder_output = ops.sum_halves(encoder_output)
+        hidden = hidden[: self.decoder.n_layers]
+        tf = ops.teacher_forcing_mask(max_len, teacher_forcing_ratio) if trg is not None else None
+        outputs, _, _ = ops.att_decode(encoder_output, hidden[-1], *self.decoder.weights(), trg=trg, tf_mask=tf, L=max_len)
+        return outputs
