@@ -42,7 +42,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const float* __restrict__ 
         const float* pr = Pb + (size_t)tau * H;
         float s = 0.f;
 #pragma unroll
-        for (int k = 0; k < KH; ++k) s += vr[k] * fmaxf(pr[lane + 64 * k] + ar[k], 0.f);
+        for (int k = 0; k < KH; ++k) s += vr[k] * m3t_relu(pr[lane + 64 * k] + ar[k]);
         s = wave_sum(s);
         if (lane == 0) s_lds[tau] = s;
     }

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % (size_t)C);
         float v = (x[i] - mean[c]) * invstd[c] * (gamma ? gamma[c] : 1.f) + (beta ? beta[c] : 0.f);
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = m3t_relu(v);
         y[i] = v;
     }
 }
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void bnp_apply_kernel(const float* __restrict_
     const float* p = x + plane * (size_t)S;
     float* q = y + plane * (size_t)S;
     float mx = 0.f;                                  // amax (m3t_amax_out): the slot is raised to max |y| -- the next convolution's operand scale
-    auto f = [&](float v) { float r = (v - mu) * a + b; r = relu ? fmaxf(r, 0.f) : r; mx = fmaxf(mx, m3t_fin_abs(r)); return r; };
+    auto f = [&](float v) { float r = (v - mu) * a + b; r = relu ? m3t_relu(r) : r; mx = fmaxf(mx, m3t_fin_abs(r)); return r; };
     if (VEC) {
         for (int i = s0 + 4 * threadIdx.x; i < s1; i += 1024) {
             const float4 v = *reinterpret_cast<const float4*>(p + i);
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void bnp_small_map_kernel(const float* __restr
         for (int e = 0; e < E; ++e) {
             if (MODE == 0) {
                 const float r = (v[e] - mu) * w + b;
-                o[e] = relu ? fmaxf(r, 0.f) : r;
+                o[e] = relu ? m3t_relu(r) : r;
             } else {
                 float g = v[e];
                 if (relu && !(yv[e] > 0.f)) g = 0.f;

@@ -15,7 +15,7 @@ __device__ __forceinline__ void wave_argmax(float& v, int& idx) {
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(v, o, 64);
         const int oi = __shfl_xor(idx, o, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+        if (m3t_argmax_wins(ov, oi, v, idx)) { v = ov; idx = oi; }
     }
 }
 
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void channel_fwd_kernel(const float* __restric
                 sum += __shfl_xor(sum, o, 64);
                 const float ov = __shfl_xor(mx, o, 64);
                 const int oi = __shfl_xor(am, o, 64);
-                if (ov > mx || (ov == mx && oi < am)) { mx = ov; am = oi; }
+                if (m3t_argmax_wins(ov, oi, mx, am)) { mx = ov; am = oi; }
             }
             if (sub == 0 && c < C) {
                 const float avg = sum / (float)HW;
@@ -80,16 +80,16 @@ __global__ __launch_bounds__(256) void channel_fwd_kernel(const float* __restric
             for (int i = lane; i < (HW >> 2); i += 64) {
                 const float4 v = p4[i];
                 sum += (v.x + v.y) + (v.z + v.w);
-                if (v.x > mx) { mx = v.x; am = 4 * i; }
-                if (v.y > mx) { mx = v.y; am = 4 * i + 1; }
-                if (v.z > mx) { mx = v.z; am = 4 * i + 2; }
-                if (v.w > mx) { mx = v.w; am = 4 * i + 3; }
+                if (m3t_nan_gt(v.x, mx)) { mx = v.x; am = 4 * i; }
+                if (m3t_nan_gt(v.y, mx)) { mx = v.y; am = 4 * i + 1; }
+                if (m3t_nan_gt(v.z, mx)) { mx = v.z; am = 4 * i + 2; }
+                if (m3t_nan_gt(v.w, mx)) { mx = v.w; am = 4 * i + 3; }
             }
         } else
         for (int i = lane; i < HW; i += 64) {
             const float v = pl[i];
             sum += v;
-            if (v > mx) { mx = v; am = i; }
+            if (m3t_nan_gt(v, mx)) { mx = v; am = i; }
         }
         sum = wave_sum(sum);
         wave_argmax(mx, am);
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void channel_fwd_kernel(const float* __restric
         h = wave_sum(h) + b1[r];
         if (lane == 0) {
             hidden[((size_t)n * 2 + which) * Cr + r] = h;
-            s_h[j] = fmaxf(h, 0.f);
+            s_h[j] = m3t_relu(h);
         }
     }
     __syncthreads();
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void channel_bwd_kernel(const float* __restric
         g_dh[((size_t)n * 2 + which) * Cr + r] = dh;
         if (which == 0) {
             const float hm = hidden[((size_t)n * 2 + 1) * Cr + r];
-            g_r[(size_t)n * Cr + r] = fmaxf(h, 0.f) + fmaxf(hm, 0.f);
+            g_r[(size_t)n * Cr + r] = m3t_relu(h) + m3t_relu(hm);
         }
     }
     __syncthreads();
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void spatial_compress_kernel(const float* __re
     for (int c = 0; c < C; ++c) {
         const float v = xb[(size_t)c * HW];
         sum += v;
-        if (v > mx) { mx = v; am = c; }
+        if (m3t_nan_gt(v, mx)) { mx = v; am = c; }
     }
     comp[((size_t)n * 2 + 0) * HW + p] = mx;
     comp[((size_t)n * 2 + 1) * HW + p] = sum / (float)C;
@@ -475,10 +475,10 @@ __global__ __launch_bounds__(256) void spatial_compress4_kernel(const float4* __
     for (int c = 0; c < C; ++c) {
         const float4 v = xb[(size_t)c * HW4];
         sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
-        if (v.x > mx.x) { mx.x = v.x; am.x = c; }
-        if (v.y > mx.y) { mx.y = v.y; am.y = c; }
-        if (v.z > mx.z) { mx.z = v.z; am.z = c; }
-        if (v.w > mx.w) { mx.w = v.w; am.w = c; }
+        if (m3t_nan_gt(v.x, mx.x)) { mx.x = v.x; am.x = c; }
+        if (m3t_nan_gt(v.y, mx.y)) { mx.y = v.y; am.y = c; }
+        if (m3t_nan_gt(v.z, mx.z)) { mx.z = v.z; am.z = c; }
+        if (m3t_nan_gt(v.w, mx.w)) { mx.w = v.w; am.w = c; }
     }
     const float ic = 1.f / (float)C;
     comp[((size_t)n * 2 + 0) * HW4 + q] = mx;

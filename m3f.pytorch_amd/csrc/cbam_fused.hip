@@ -74,7 +74,7 @@ __device__ __forceinline__ float group_sum(float v, int G) {
 
 // (max, first index of the max) with torch's tie rule (the lower index wins): symmetric, so both partners end with the same pair
 __device__ __forceinline__ void amax_take(float& mx, int& am, float ov, int oi) {
-    if (ov > mx || (ov == mx && oi < am)) { mx = ov; am = oi; }
+    if (m3t_argmax_wins(ov, oi, mx, am)) { mx = ov; am = oi; }
 }
 __device__ __forceinline__ void group_sum_argmax(float& sum, float& mx, int& am, int G) {
 #define M3T_CB_STEP(CTRL)                                              \
@@ -197,8 +197,8 @@ __device__ __forceinline__ void gate_mlp_fwd(const float* s_avg, const float* s_
             ha += bias1; hm += bias1;
             hidden[((size_t)n * 2 + 0) * Cr + r] = ha;
             hidden[((size_t)n * 2 + 1) * Cr + r] = hm;
-            s_h[r] = fmaxf(ha, 0.f);
-            s_h[Cr + r] = fmaxf(hm, 0.f);
+            s_h[r] = m3t_relu(ha);
+            s_h[Cr + r] = m3t_relu(hm);
         }
     }
     __syncthreads();
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(FT) void cbam_f1_kernel(const float* __restrict__ x
 #pragma unroll
                         for (int e = 0; e < E; ++e) {
                             sum += v[k][e];
-                            if (v[k][e] > mx) { mx = v[k][e]; am = sub * E + e; }
+                            if (m3t_nan_gt(v[k][e], mx)) { mx = v[k][e]; am = sub * E + e; }
                         }
                     }
                     group_sum_argmax(sum, mx, am, G);
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(FT) void cbam_f1_kernel(const float* __restrict__ x
 #pragma unroll
                         for (int e = 0; e < E; ++e) {
                             sum += v[k][e];
-                            if (v[k][e] > mx) { mx = v[k][e]; am = (u0 + k * G) * E + e; }
+                            if (m3t_nan_gt(v[k][e], mx)) { mx = v[k][e]; am = (u0 + k * G) * E + e; }
                         }
                     }
             }
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(FT) void cbam_f1_kernel(const float* __restrict__ x
                         for (int e = 0; e < E; ++e) {
                             const float t = v[j][e] * sc;
                             sum[e] += t;
-                            if (t > mx[e]) { mx[e] = t; am[e] = c; }
+                            if (m3t_nan_gt(t, mx[e])) { mx[e] = t; am[e] = c; }
                         }
                     }
             }
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(FT) void cbam_f1_kernel(const float* __restrict__ x
                     sum[e] += __shfl_xor(sum[e], o, 64);
                     const float ov = __shfl_xor(mx[e], o, 64);
                     const int oi = __shfl_xor(am[e], o, 64);
-                    if (ov > mx[e] || (ov == mx[e] && oi < am[e])) { mx[e] = ov; am[e] = oi; }
+                    if (m3t_argmax_wins(ov, oi, mx[e], am[e])) { mx[e] = ov; am[e] = oi; }
                 }
             }
             if (lane < Qp) {
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(FT) void cbam_f1_kernel(const float* __restrict__ x
                     fs[e] += p_sum[idx];
                     const float ov = p_mx[idx];
                     const int oi = p_am[idx];
-                    if (ov > fm[e] || (ov == fm[e] && oi < fa[e])) { fm[e] = ov; fa[e] = oi; }
+                    if (m3t_argmax_wins(ov, oi, fm[e], fa[e])) { fm[e] = ov; fa[e] = oi; }
                 }
             }
             float mean[E];
@@ -841,7 +841,7 @@ __device__ __forceinline__ void gate_mlp_bwd(const float* s_datt, float* s_part,
         g_dh[((size_t)n * 2 + which) * Cr + r] = dh;
         if (which == 0) {
             const float hm = hidden[((size_t)n * 2 + 1) * Cr + r];
-            g_r[(size_t)n * Cr + r] = fmaxf(h, 0.f) + fmaxf(hm, 0.f);
+            g_r[(size_t)n * Cr + r] = m3t_relu(h) + m3t_relu(hm);
         }
     }
     __syncthreads();
@@ -1280,7 +1280,7 @@ __global__ __launch_bounds__(FT, NV <= 4 ? 6 : 4) void cbam_f1l_kernel(const flo
         for (int p = 0; p < HW; ++p) {
             const float t = pl[p];
             sum += t;
-            if (t > mx) { mx = t; am = p; }
+            if (m3t_nan_gt(t, mx)) { mx = t; am = p; }
         }
         s_avg[c] = sum / (float)HW; s_max[c] = mx; s_amp[c] = am;
     }
@@ -1307,7 +1307,7 @@ __global__ __launch_bounds__(FT, NV <= 4 ? 6 : 4) void cbam_f1l_kernel(const flo
             for (int c = kq; c < C; c += KS) {
                 const float t = s_f[c * S + q] * s_sc[c];
                 sum += t;
-                if (t > mx) { mx = t; am = c; }
+                if (m3t_nan_gt(t, mx)) { mx = t; am = c; }
             }
         }
         for (int o = Qp; o < 64; o <<= 1) {       // the slices of a pixel inside the wave sit Qp lanes apart

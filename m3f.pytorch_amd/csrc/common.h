@@ -83,6 +83,17 @@ static __device__ __forceinline__ void m3t_drop_mask4(const M3TDrop& d, uint32_t
 // all-zero operand gives zeros either way.
 // inf / NaN do not count towards the maximum (m3t_fin_abs): the finite values keep their scale and the non-finite ones become fp16
 // inf / NaN, which poison exactly the outputs they would poison in an fp32 GEMM.
+// ReLU as torch.relu: NaN stays NaN (fmaxf(NaN, 0.f) is 0, which would hide a diverged input from the loss and the
+// non-finite-gradient guard); for every other input, the sign of zero included, the same bits as fmaxf(v, 0.f).  Every fused
+// ReLU uses it (tests/test_relu_source_rule.py keeps fmaxf(x, 0.f) out of the kernels).
+static __device__ __forceinline__ float m3t_relu(float v) { return (v != v) ? v : fmaxf(v, 0.f); }
+// Max-with-argmax steps in which NaN wins, as in torch.max / max_pool2d: m3t_nan_gt for a scan in index order (a NaN beats
+// every number and the first NaN stays), m3t_argmax_wins for merging two candidates (v, i) into (mx, am) -- the larger, NaN
+// above all, and the lower index on a tie (two NaN included).
+static __device__ __forceinline__ bool m3t_nan_gt(float v, float mx) { return v > mx || (v != v && mx == mx); }
+static __device__ __forceinline__ bool m3t_argmax_wins(float v, int i, float mx, int am) {
+    return (v != v) ? (mx == mx || i < am) : (mx == mx && (v > mx || (v == mx && i < am)));
+}
 static __device__ __forceinline__ float m3t_fin_abs(float x) {          // |x|, or 0 for inf / NaN
     const unsigned b = __float_as_uint(x) & 0x7fffffffu;
     return b < 0x7f800000u ? __uint_as_float(b) : 0.f;

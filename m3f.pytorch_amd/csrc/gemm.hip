@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void sgemm_kernel(GemmParams p) {
                 float* q = dst + (size_t)row * ldd + col;
                 if (direct) {
                     v += bv;
-                    if (p.act == 1) v = fmaxf(v, 0.f);
+                    if (p.act == 1) v = m3t_relu(v);
                     if (p.accumulate) v += *q;
                 }
                 *q = v;
@@ -260,7 +260,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, float* __rest
         float s = 0.f;
         for (int k = 0; k < splits; ++k) s += ws[(size_t)k * total + i];
         if (bias) s += bias[n];
-        if (act == 1) s = fmaxf(s, 0.f);
+        if (act == 1) s = m3t_relu(s);
         float* q = C + (size_t)m * ldc + n;
         if (accumulate) s += *q;
         *q = s;
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __rest
         }
         const int m = (int)(i / n4), n = (int)(i % n4) * 4;
         if (bias) { s.x += bias[n]; s.y += bias[n + 1]; s.z += bias[n + 2]; s.w += bias[n + 3]; }
-        if (act == 1) { s.x = fmaxf(s.x, 0.f); s.y = fmaxf(s.y, 0.f); s.z = fmaxf(s.z, 0.f); s.w = fmaxf(s.w, 0.f); }
+        if (act == 1) { s.x = m3t_relu(s.x); s.y = m3t_relu(s.y); s.z = m3t_relu(s.z); s.w = m3t_relu(s.w); }
         float4* q = reinterpret_cast<float4*>(C + (size_t)m * ldc + n);
         if (accumulate) { const float4 c = *q; s.x += c.x; s.y += c.y; s.z += c.z; s.w += c.w; }
         *q = s;
@@ -487,12 +487,12 @@ __global__ __launch_bounds__(256) void add_relu_kernel(const float* __restrict__
     float mx = 0.f;                                  // (m3t_amax_out: the slot is raised to max |out| -- the next convolutions' operand scale)
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const float4 x = a4[i], y = b4[i];
-        const float4 o = make_float4(fmaxf(x.x + y.x, 0.f), fmaxf(x.y + y.y, 0.f), fmaxf(x.z + y.z, 0.f), fmaxf(x.w + y.w, 0.f));
+        const float4 o = make_float4(m3t_relu(x.x + y.x), m3t_relu(x.y + y.y), m3t_relu(x.z + y.z), m3t_relu(x.w + y.w));
         o4[i] = o;
         mx = fmaxf(fmaxf(mx, m3t_fin_abs(o.x)), fmaxf(m3t_fin_abs(o.y), fmaxf(m3t_fin_abs(o.z), m3t_fin_abs(o.w))));
     }
     for (size_t i = n4 * 4 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float o = fmaxf(a[i] + b[i], 0.f);
+        const float o = m3t_relu(a[i] + b[i]);
         out[i] = o;
         mx = fmaxf(mx, m3t_fin_abs(o));
     }

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ring_kernel(RingParams p) {
                 float* q = dst + (size_t)row * ldd + col;
                 if (direct) {
                     v += bv;
-                    if (p.act == 1) v = fmaxf(v, 0.f);
+                    if (p.act == 1) v = m3t_relu(v);
                     if (p.accumulate) v += *q;
                 }
                 *q = v;
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ringt_kernel(RingParams p) {
                 float* q = dst + (size_t)row * ldd + col;
                 if (direct) {
                     v += bv;
-                    if (p.act == 1) v = fmaxf(v, 0.f);
+                    if (p.act == 1) v = m3t_relu(v);
                     if (p.accumulate) v += *q;
                 }
                 *q = v;

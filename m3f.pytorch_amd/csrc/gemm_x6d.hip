@@ -315,12 +315,12 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
                     v += bv;
                     if (p.cv_pre) p.cv_pre[o] = v;
                     const float mk = p.cv_drop.on ? dm[r & 3] : (p.cv_mask ? p.cv_mask[o] : 1.f);
-                    if (p.act == 1) v = fmaxf(v, 0.f) * mk;
-                    else if (p.act == 2) v = fmaxf(fmaxf(v, 0.f) * mk + p.cv_res[o], 0.f);
+                    if (p.act == 1) v = m3t_relu(v) * mk;
+                    else if (p.act == 2) v = m3t_relu(m3t_relu(v) * mk + p.cv_res[o]);
                     else if (p.cv_res) v += p.cv_res[o];
                 } else if (direct) {
                     v += bv;
-                    if (p.act == 1) v = fmaxf(v, 0.f);
+                    if (p.act == 1) v = m3t_relu(v);
                     if (p.accumulate) v += *q;
                 }
                 *q = v;

@@ -331,7 +331,7 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
                 float* q = dst + (size_t)row * ldd + col;
                 if (direct) {
                     v += bv;
-                    if (p.act == 1) v = fmaxf(v, 0.f);
+                    if (p.act == 1) v = m3t_relu(v);
                     if (p.accumulate) v += *q;
                 }
                 *q = v;

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(CL_TH) void bncl_map_kernel(const float* __restrict
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float r = (ve[e] - mu[e]) * w[e] + b[e];
-                o[e] = relu ? fmaxf(r, 0.f) : r;
+                o[e] = relu ? m3t_relu(r) : r;
             }
         } else {
             const float4 xv = reinterpret_cast<const float4*>(x)[i];
@@ -350,9 +350,8 @@ __global__ __launch_bounds__(CL_TH) void bnpool_fwd_kernel(const float* __restri
             const float ve[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float y = fmaxf((ve[e] - mu[e]) * w[e] + b[e], 0.f);
-                const float yy = (ve[e] != ve[e]) ? ve[e] : y;          // (fmaxf would drop a NaN; torch.relu keeps it and the pooling lets it win)
-                if (t == 0 || yy > best[e] || (yy != yy && best[e] == best[e])) { best[e] = yy; bi[e] = t; }
+                const float y = m3t_relu((ve[e] - mu[e]) * w[e] + b[e]);          // (NaN stays NaN, as torch.relu; the pooling lets it win)
+                if (t == 0 || m3t_nan_gt(y, best[e])) { best[e] = y; bi[e] = t; }
             }
         }
         reinterpret_cast<float4*>(yp)[i] = make_float4(best[0], best[1], best[2], best[3]);

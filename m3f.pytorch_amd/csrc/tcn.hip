@@ -180,8 +180,8 @@ __global__ __launch_bounds__(256) void causal_conv_kernel(ConvParams p) {
                 float v = acc[i][j][r] + bv;
                 if (p.pre) p.pre[o] = v;
                 const float mk = p.drop.on ? dm[r & 3] : (p.mask ? p.mask[o] : 1.f);
-                if (p.act == 1) v = fmaxf(v, 0.f) * mk;
-                else if (p.act == 2) v = fmaxf(fmaxf(v, 0.f) * mk + p.res[o], 0.f);
+                if (p.act == 1) v = m3t_relu(v) * mk;
+                else if (p.act == 2) v = m3t_relu(m3t_relu(v) * mk + p.res[o]);
                 else if (p.res) v += p.res[o];
                 p.y[o] = v;
             }

@@ -113,6 +113,8 @@ class FlatGradDDP:
                         view = self.flat_params[o:o + p.numel()].view_as(p)
                         view.copy_(p.data)
                         p.data = view
+            from . import ops
+            ops.weights_changed()      # (p.data = view keeps ._version; writes through flat_params never bump it)
         self._left = [0] * len(self.buckets)
         self._handles = []
         if self.world > 1:
@@ -172,6 +174,8 @@ class FlatGradDDP:
         with torch.no_grad():
             for t in list(self.module.parameters()) + list(self.module.buffers()):
                 dist.broadcast(t.data, src=dist.get_global_rank(self.pg, src) if self.pg is not None else src, group=self.pg)
+        from . import ops
+        ops.weights_changed()              # broadcast into .data: ._version does not see it
 
     def _make_hook(self, bi):
         def hook(_p):

@@ -407,8 +407,18 @@ def amax_slots(n, device):
 # final (the optimizer has run) -- now measures EVERY weight matrix of the model in one go; forward calls find the slot here.  Entries
 # die at FlatGradDDP.finish() (the optimizer is about to change the weights): a forward outside a step (validation) measures for itself
 # as before.  M3T_WEIGHT_AMAX=0 turns the table off.
-_W_AMAX = {}              # id(parameter) -> (weakref(parameter), slot address, owner id, slots tensor, parameter._version, data_ptr)
+_W_AMAX = {}              # id(parameter) -> (weakref(parameter), slot address, owner id, slots tensor, parameter._version, data_ptr, generation)
 _W_AMAX_ON = os.environ.get("M3T_WEIGHT_AMAX", "1") != "0"
+_W_GEN = [0]              # weight generation: bumped by every write to the weights that ._version does not see (weight_amax docstring)
+
+
+def weights_changed():
+    """the weights may have changed behind autograd's back (.data writes, flat-buffer writes, raw-pointer optimizer steps): every cached
+    magnitude -- this step's table and the no_grad slots -- is measured again at its next use"""
+    _W_GEN[0] += 1
+
+
+invalidate_weight_amax = weights_changed     # the public name for callers that write parameters through .data
 
 
 def measure_weight_amax(params, owner=None):
@@ -423,7 +433,7 @@ def measure_weight_amax(params, owner=None):
     slots = amax_slots(len(ws), ws[0].device)
     if measure_amax([(p.detach().view(p.shape[0], -1), slots.data_ptr() + 8 * i) for i, p in enumerate(ws)]):
         for i, p in enumerate(ws):
-            _W_AMAX[id(p)] = (weakref.ref(p), slots.data_ptr() + 8 * i, id(owner), slots, p._version, p.data_ptr())
+            _W_AMAX[id(p)] = (weakref.ref(p), slots.data_ptr() + 8 * i, id(owner), slots, p._version, p.data_ptr(), _W_GEN[0])
 
 
 def drop_weight_amax(owner=None):
@@ -434,12 +444,16 @@ def drop_weight_amax(owner=None):
 def weight_amax(w, keep=None):
     """address of this step's magnitude slot of the parameter object `w`, or None (not measured this step: the caller measures); keep: a
     list that receives the tensor holding the slot (an autograd context keeps it alive for its backward).  An entry is only trusted while the
-    parameter is the tensor that was measured: an in-place change since (optimizer.step() after zero_grad(), load_state_dict, an EMA copy, a
-    clamp -- anything that bumps ._version) or a re-pointed .data drops it and the caller measures again."""
+    parameter is the tensor that was measured at the same weight generation: a change of w._version (an autograd-visible in-place op such as
+    w.mul_() or load_state_dict), a re-pointed .data, or a weights_changed() call drops it and the caller measures again.
+    Cache contract: a write that autograd does not see leaves ._version alone -- p.data.copy_() / p.data.mul_() (an EMA swap, a
+    re-initialisation), an in-place op on FlatGradDDP.flat_params, a raw-pointer write.  The project's own writers (FlatAdam.step,
+    FlatSGD.step, FlatGradDDP flattening and broadcast_state, Trainer.load_checkpoint) call weights_changed() themselves; any other caller
+    that writes through .data or a raw pointer must call invalidate_weight_amax() before the next forward, or it runs on stale scales."""
     e = _W_AMAX.get(id(w))
     if e is None or e[0]() is not w:
         return _frozen_weight_amax(w, keep)
-    if e[4] != w._version or e[5] != w.data_ptr():
+    if e[4] != w._version or e[5] != w.data_ptr() or e[6] != _W_GEN[0]:
         del _W_AMAX[id(w)]
         return None
     if keep is not None and not any(k is e[3] for k in keep):
@@ -447,18 +461,18 @@ def weight_amax(w, keep=None):
     return e[1]
 
 
-_W_AMAX_FROZEN = {}      # id(parameter) -> (weakref, slot tensor, version, data_ptr): weights measured under no_grad
+_W_AMAX_FROZEN = {}      # id(parameter) -> (weakref, slot tensor, version, data_ptr, generation): weights measured under no_grad
 
 
 def _frozen_weight_amax(w, keep):
     """Inference (torch.no_grad(): validation_step / test_step, reference models/model.py:226-246,320-337): nothing changes the weights between
-    calls, so a weight matrix is measured ONCE and the slot is kept for as long as the parameter is that tensor at that version (an optimizer
-    step, load_state_dict or any in-place write bumps it: measured again).  Training steps never come here with a hit -- FlatGradDDP measures
-    per step (measure_weight_amax), plain autograd training measures per call as before (grad mode on)."""
+    calls, so a weight matrix is measured ONCE and the slot is kept for as long as the parameter is that tensor at that version and weight
+    generation (the cache contract of weight_amax: a write ._version does not see must call weights_changed()).  Training steps never come
+    here with a hit -- FlatGradDDP measures per step (measure_weight_amax), plain autograd training measures per call as before (grad mode on)."""
     if torch.is_grad_enabled() or not _W_AMAX_ON or not torch.is_tensor(w) or not w.is_cuda or w.dtype != torch.float32 or w.dim() < 2:
         return None
     e = _W_AMAX_FROZEN.get(id(w))
-    if e is not None and e[0]() is w and e[2] == w._version and e[3] == w.data_ptr():
+    if e is not None and e[0]() is w and e[2] == w._version and e[3] == w.data_ptr() and e[4] == _W_GEN[0]:
         slot = e[1]
     else:
         if not w.is_contiguous() or (w.numel() // w.shape[0]) % 4 != 0 or w.data_ptr() % 16 != 0:
@@ -468,7 +482,7 @@ def _frozen_weight_amax(w, keep):
         slot = torch.zeros(1, dtype=torch.int64, device=w.device)      # (its own allocation: the slot pool's chunks are recycled per step)
         if not measure_amax([(w.detach().view(w.shape[0], -1), slot.data_ptr())]):
             return None
-        _W_AMAX_FROZEN[id(w)] = (weakref.ref(w), slot, w._version, w.data_ptr())
+        _W_AMAX_FROZEN[id(w)] = (weakref.ref(w), slot, w._version, w.data_ptr(), _W_GEN[0])
     if keep is not None and not any(k is slot for k in keep):
         keep.append(slot)
     return slot.data_ptr()

@@ -6,7 +6,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 
 def _p(t):
@@ -41,6 +41,7 @@ class FlatAdam(_Guarded):
         rc = _lib.load().m3t_adam_step(_p(d.flat_params), _p(d.flat), _p(self.m), _p(self.v), d.flat.numel(), self.lr,
                                        self.betas[0], self.betas[1], self.eps, self.weight_decay, self.t, self._guard(), _s())
         _lib.check(rc, "m3t_adam_step")
+        ops.weights_changed()              # a raw-pointer write: the parameters' ._version does not move
 
 
 class FlatSGD(_Guarded):
@@ -57,3 +58,4 @@ class FlatSGD(_Guarded):
         rc = _lib.load().m3t_sgd_step(_p(d.flat_params), _p(d.flat), _p(self.buf), d.flat.numel(), self.lr, self.momentum,
                                       self.weight_decay, self.t, self._guard(), _s())
         _lib.check(rc, "m3t_sgd_step")
+        ops.weights_changed()

@@ -237,4 +237,5 @@ class Trainer:
         if ck.get("scheduler") and self.scheduler is not None:
             self.scheduler.load_state_dict(ck["scheduler"])
         self.ddp.broadcast_state()
+        ops.weights_changed()                        # (world size 1: broadcast_state returns before it writes anything)
         return ck
