@@ -9,9 +9,15 @@ One process per GPU (torchrun), clips sharded across ranks (weak scaling), one f
 all-reduce of the gradients per step.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full   # + CPU baseline, secondary configs, idle-queue enqueue probe
     python bench.py --gpus 8                      # starts its own 8 ranks (torch.distributed.run) before touching a GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--scaling strong]
+
+A plain run does what `value` and `ms_per_step` need: set-up, warm-up, the timed steps, --dump-outputs, the JSON line (with the
+roofline and kernel figures read from HIP events of the timed steps themselves).  Everything that takes runs of its own -- the
+CPU baseline, the secondary configurations (`aux`), the idle-queue enqueue probe (`host_enqueue_ms_idle`) and, for N > 1, the
+back-to-back all-reduce -- runs only under --full; in a plain run their keys read null (`aux`, `aux_ms`, `speedup_vs_cpu`: absent).
 
 Process structure for N > 1.  The process torchrun starts for a rank is a SUPERVISOR: it never touches the GPU, starts the
 real worker (`--worker`) as a child and watches it.  If a worker reports a persistent scan that gave up (M3T_ESPIN: e.g. an
@@ -389,9 +395,13 @@ def parse_args():
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch clips on EVERY GPU; strong: --batch clips in all, split over the GPUs (SURVEY 8(d) C4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline: CPU baseline, secondary configs (--aux), idle-queue enqueue probe, "
+                         "back-to-back all-reduce (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-clips", type=int, default=32, help="clips per CPU-baseline iteration (default: the GPU's batch)")
-    ap.add_argument("--aux", default="c3fp32,c1,c2,c2bf16,c3x6,c3_eval,c5,c5_eval,cbam", help="secondary configs timed after the main leg at N=1 ('' = none)")
+    ap.add_argument("--aux", default="c3fp32,c1,c2,c2bf16,c3x6,c3_eval,c5,c5_eval,cbam",
+                    help="secondary configs timed after the main leg at N=1 under --full ('' = none)")
     ap.add_argument("--aux-budget", type=float, default=240.0)
     ap.add_argument("--aux-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--worker", type=int, default=None, help=argparse.SUPPRESS)      # attempt number (0, or 1 = fallback)
@@ -671,11 +681,12 @@ def worker(args):
     if args.dump_outputs and rank == 0:             # outside the timed region, before the enqueue probe below runs more steps
         dumped = dump_outputs(args.dump_outputs, model, ddp, last[0])
     beat()
-    # host enqueue cost with an IDLE queue: the GPU is parked behind a spin kernel while the host enqueues whole steps, so
-    # the figure has no queue back-pressure in it -- `host_enqueue_ms_per_step` above mixes the two (a host that runs ahead of the GPU
-    # blocks in the driver's full queue and reads as "slow host").  Outside the timed region; 3 steps behind ~60 ms of spin.
+    persist_per_step = (_lib.load().m3t_gru_persist_count() - n_persist0) / max(1, args.steps)     # (the timed steps' launches only)
+    # --full: host enqueue cost with an IDLE queue: the GPU is parked behind a spin kernel while the host enqueues whole
+    # steps, so the figure has no queue back-pressure in it -- `host_enqueue_ms_per_step` above mixes the two (a host that runs ahead of the
+    # GPU blocks in the driver's full queue and reads as "slow host").  Outside the timed region; 3 steps behind ~60 ms of spin.
     host_idle_ms = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             torch.cuda.synchronize()
             torch.cuda._sleep(int(0.06 * 2.4e9))
@@ -687,29 +698,31 @@ def worker(args):
         except Exception:  # noqa: BLE001
             host_idle_ms = None
     ddp.agree_on_scan_error()                      # a scan that gave up (on any rank) would make the number meaningless: every rank raises
-    persist_per_step = (_lib.load().m3t_gru_persist_count() - n_persist0) / max(1, args.steps)
-    # N > 1: the gradient all-reduce alone (same buffer, same communicator), outside the timed region
     allreduce = None
     if world > 1:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(2):
-            dist.all_reduce(ddp._buf, op=dist.ReduceOp.SUM)
-        fence()
-        reps = 10
-        ev0.record()
-        for _ in range(reps):
-            dist.all_reduce(ddp._buf, op=dist.ReduceOp.SUM)
-        ev1.record()
-        torch.cuda.synchronize()
-        ar_ms = ev0.elapsed_time(ev1) / reps
         nbytes = ddp._buf.numel() * 4
-        algbw = nbytes / (ar_ms * 1e-3) / 1e9
+        ar_ms = algbw = None
+        if args.full:
+            # the gradient all-reduce alone (same buffer, same communicator), outside the timed region
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(2):
+                dist.all_reduce(ddp._buf, op=dist.ReduceOp.SUM)
+            fence()
+            reps = 10
+            ev0.record()
+            for _ in range(reps):
+                dist.all_reduce(ddp._buf, op=dist.ReduceOp.SUM)
+            ev1.record()
+            torch.cuda.synchronize()
+            ar_ms = ev0.elapsed_time(ev1) / reps
+            algbw = nbytes / (ar_ms * 1e-3) / 1e9
         in_step = [a.elapsed_time(b) for a, b in ar_events]
-        allreduce = {"bytes": nbytes, "ms": round(ar_ms, 4),
+        allreduce = {"bytes": nbytes, "ms": round(ar_ms, 4) if args.full else None,
                      "ms_in_step": round(sum(in_step) / len(in_step), 4) if in_step else None,
                      "ms_in_step_note": "HIP events on the step's stream around poison kernel + collective(s) + dead-rank check, profiled steps only; "
-                                        "`ms` is the same collective back to back after the timed region", "algbw_GBps": round(algbw, 2),
-                     "busbw_GBps": round(algbw * 2 * (world - 1) / world, 2), "world_size": dist.get_world_size(),
+                                        "`ms` (--full) is the same collective back to back after the timed region",
+                     "algbw_GBps": round(algbw, 2) if args.full else None,
+                     "busbw_GBps": round(algbw * 2 * (world - 1) / world, 2) if args.full else None, "world_size": dist.get_world_size(),
                      "schedule": ("bucket 0 (fusion GRU) early on a communication stream beside backward, the rest + dead slot after backward (M3T_DDP_EARLY_BUCKET=1)"
                                   if getattr(ddp, "_early", False) else
                                   "one all-reduce of the flat buffer after backward" if not ddp.overlap else "3 buckets overlapped with backward"),
@@ -822,8 +835,8 @@ def worker(args):
             "host_enqueue_ms_per_step": round(host_ms, 3),
             "host_enqueue_ms_idle": round(host_idle_ms, 3) if host_idle_ms is not None else None,
             "host_enqueue_note": "host_enqueue_ms_per_step = wall time of the timed loop's enqueue calls / steps: it contains the time the host spends "
-                                 "blocked behind a full queue (a host that is ahead reads as slow); host_enqueue_ms_idle = the same step enqueued 3 times "
-                                 "while the GPU is parked behind a 60 ms spin kernel (no back-pressure): the enqueue path itself",
+                                 "blocked behind a full queue (a host that is ahead reads as slow); host_enqueue_ms_idle (--full) = the same step enqueued "
+                                 "3 times while the GPU is parked behind a 60 ms spin kernel (no back-pressure): the enqueue path itself",
             "allreduce": allreduce,
             "memory_roofline_frac": round((clips / dt) * 66.15e6 / (HBM_PEAK_GBS * 1e9 * world), 5),
         }
@@ -833,7 +846,7 @@ def worker(args):
             out["fallback"] = ("launch-per-step scans + gradient buckets overlapped with backward, in fresh worker processes, after: %s"
                                % fallback)
         out["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             print("# gpu leg done: %.2f clips/s, %.3f ms/step; timing the CPU baseline ..." % (out["value"], step_ms),
                   file=sys.stderr, flush=True)
             try:
@@ -841,7 +854,7 @@ def worker(args):
                 out["speedup_vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
             except Exception as e:  # noqa: BLE001
                 out["cpu_baseline_error"] = repr(e)
-        if world == 1 and args.aux:
+        if args.full and world == 1 and args.aux:
             print("# timing the secondary configs (%s) ..." % args.aux, file=sys.stderr, flush=True)
             try:
                 out["aux"] = run_aux(args.aux, args.aux_budget)

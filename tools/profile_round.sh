@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 T=${1:-r01}
 cd $R && timeout 1200 python -m pytest tests -x -q -m gpu > $O/pytest_$T.log 2>&1; tail -2 $O/pytest_$T.log
-python bench.py --steps 20 --warmup 3 > $O/bench_$T.json 2> $O/bench_$T.err; tail -c 300 $O/bench_$T.json
+python bench.py --steps 20 --warmup 3 --full > $O/bench_$T.json 2> $O/bench_$T.err; tail -c 300 $O/bench_$T.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof_$T; rocprofv3 --kernel-trace --stats -d $O/prof_$T -o $T --output-format csv -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/prof_${T}_bench.log 2>&1
 find $O/prof_$T -name "*kernel_trace.csv" -delete

@@ -5,7 +5,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; T=${1:-r02}
 cd $R
 if [ "$2" != "notest" ]; then timeout 1500 python -m pytest tests -q -m gpu -x > $O/pytest_$T.log 2>&1; tail -3 $O/pytest_$T.log; fi
-python bench.py --steps 20 --warmup 5 > $O/bench_$T.json 2> $O/bench_$T.err; tail -c 600 $O/bench_$T.json; echo
+python bench.py --steps 20 --warmup 5 --full > $O/bench_$T.json 2> $O/bench_$T.err; tail -c 600 $O/bench_$T.json; echo
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof_$T; rocprofv3 --kernel-trace --stats -d $O/prof_$T -o $T --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --aux "" > $O/prof_${T}_bench.log 2>&1
 find $O/prof_$T -name "*kernel_trace.csv" -delete

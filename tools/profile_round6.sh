@@ -5,7 +5,7 @@
 # usage: bash tools/profile_round6.sh <tag>
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; T=${1:-r06}
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_$T.json 2> $O/bench_$T.err; tail -c 400 $O/bench_$T.json; echo
+python bench.py --steps 20 --warmup 5 --full > $O/bench_$T.json 2> $O/bench_$T.err; tail -c 400 $O/bench_$T.json; echo
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof_$T; rocprofv3 --kernel-trace --stats -d $O/prof_$T -o $T --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --aux "" > $O/prof_${T}_bench.log 2>&1
 find $O/prof_$T -name "*kernel_trace.csv" -delete
