@@ -791,6 +791,52 @@ int m3t_attdec_attn_bwd(const float* enc, const float* P, const float* a, const 
 int m3t_attdec_sum_halves(const float* x, float* y, size_t rows, int H, void* stream);
 int m3t_attdec_dup_halves(const float* dy, float* dx, size_t rows, int H, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * The 3-D DenseNet of --backbone densenet (csrc/dense.hip; reference models/densenet.py:5-93, models/backbone.py:375-423), on channels-last
+ * rows [N T H W][C] with a leading dimension: a dense block is one buffer its layers write their new columns into.  fp32 arithmetic, fixed
+ * reduction orders, no atomics: bit-identical run to run.
+ *
+ * Batch statistics of columns [0, C) of x (ld): mean and the biased variance, fp64 per-chunk partials.  Replaces the statistics pass of
+ * nn.BatchNorm3d in train mode (densenet.py:8,11,34,62); a column's statistics serve every BatchNorm that reads it.  ws: 8-B aligned,
+ * m3t_dense_stats_ws_bytes(rows, C) bytes. */
+size_t m3t_dense_stats_ws_bytes(size_t rows, int C);
+int m3t_dense_col_stats(const float* x, size_t rows, int ld, int C, float* mean, float* var, void* ws, size_t ws_bytes, void* stream);
+/* y (ldy) = relu(gamma (x - mean) / sqrt(var + eps) + beta) over [rows][C] of x (ldx): nn.BatchNorm3d + nn.ReLU (densenet.py:8-9,11-12).
+ * C % 4 == 0, ldx % 4 == 0, ldy % 4 == 0, x and y 16-B aligned.  ReLU keeps NaN. */
+int m3t_dense_bn_relu_fwd(const float* x, int ldx, size_t rows, int C, const float* mean, const float* var, const float* gamma,
+                          const float* beta, float eps, float* y, int ldy, void* stream);
+/* running_mean / running_var <- (1 - momentum) running + momentum (mean, var rows / (rows - 1)): the buffer update of a train-mode
+ * nn.BatchNorm3d from given batch statistics (rows >= 2). */
+int m3t_dense_bn_running(const float* mean, const float* var, size_t rows, int C, float* run_mean, float* run_var, float momentum, void* stream);
+/* Backward of m3t_dense_bn_relu_fwd: g = dy where the ReLU's input is not <= 0; dbeta = sum g, dgamma = sum g xhat (either may be NULL);
+ * dx (lddx; NULL: skipped) = (or += with accumulate) gamma / sqrt(var + eps) (g - mean g - xhat mean(g xhat)) with training, the same
+ * without the two means for running statistics.  ws: 8-B aligned, m3t_dense_stats_ws_bytes(rows, C) + 8 C bytes. */
+int m3t_dense_bn_relu_bwd(const float* dy, int ldy, const float* x, int ldx, size_t rows, int C, const float* mean, const float* var,
+                          const float* gamma, const float* beta, float eps, int training, float* dx, int lddx, int accumulate,
+                          float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+/* Transition (densenet.py:32-39): y [P (H/2) (W/2)][C] = AvgPool3d((1, 2, 2)) of relu(bn(x)) over frames x [P H W][C] (ldx), floor mode.
+ * The transition's 1x1x1 convolution, which commutes with the pooling, then runs on a quarter of the rows.  The spread is the pooling's
+ * backward: dfull [P H W][C] = dy / 4 inside the pooled area, 0 on a dropped last row / column. */
+int m3t_dense_pool_fwd(const float* x, int ldx, size_t P, int H, int W, int C, const float* mean, const float* var, const float* gamma,
+                       const float* beta, float eps, float* y, void* stream);
+int m3t_dense_pool_spread(const float* dy, size_t P, int H, int W, int C, float* dfull, void* stream);
+/* norm5 + relu5 + aggregation (densenet.py:61-63,79-91) over frames x [P HW][C] (ldx): mode 0 (agg 'ap', AdaptiveAvgPool2d(1)):
+ * y [P][C] = the mean over the frame; mode 1 (agg 'fc'): y [P][C HW] = relu(bn(x)) in (c, h, w) order, the input of DenseNet52_3D.fc.
+ * The spread is the backward of the aggregation: dfull [P HW][C]. */
+int m3t_dense_mean_fwd(const float* x, int ldx, size_t P, int HW, int C, const float* mean, const float* var, const float* gamma,
+                       const float* beta, float eps, int mode, float* y, void* stream);
+int m3t_dense_mean_spread(const float* dy, size_t P, int HW, int C, int mode, float* dfull, void* stream);
+/* Conv3d(Ci, Co, 3, stride 1, padding 1, bias=False) on channels-last rows (densenet.py:13-14): y [N T H W][Co] (ldy; or += with accumulate)
+ * from x (ldx) and w [27][Ci][Co] (tap = (kt, kh, kw) row-major).  With the flipped, transposed weights w'[26 - tap][co][ci] the same call is
+ * the layer's data gradient.  Tiles of 128 rows x 32 output channels: Ci % 32 == 0, Co % 32 == 0, ld % 4 == 0, 16-B aligned operands. */
+int m3t_dense_conv333(const float* x, int ldx, int N, int T, int H, int W, int Ci, const float* w, float* y, int ldy, int Co,
+                      int accumulate, void* stream);
+/* Its weight gradient dw [27][Ci][Co] = sum over rows of x[row + tap offset] (ldx) dy[row] (ldy): fixed row chunks, summed in order.
+ * Ci % 128 == 0, Co % 32 == 0, ld % 4 == 0, 16-B aligned operands; ws: m3t_dense_wgrad_ws_bytes(N T H W, Ci, Co) bytes. */
+size_t m3t_dense_wgrad_ws_bytes(size_t rows, int Ci, int Co);
+int m3t_dense_conv333_wgrad(const float* x, int ldx, const float* dy, int ldy, int N, int T, int H, int W, int Ci, int Co, float* dw,
+                            void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

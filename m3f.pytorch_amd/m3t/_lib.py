@@ -160,9 +160,22 @@ SIGNATURES = {
     "m3t_attdec_attn_bwd": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _s],
     "m3t_attdec_sum_halves": [_f, _f, _z, _i, _s],
     "m3t_attdec_dup_halves": [_f, _f, _z, _i, _s],
+    "m3t_dense_stats_ws_bytes": [_z, _i],
+    "m3t_dense_col_stats": [_f, _z, _i, _i, _f, _f, _f, _z, _s],
+    "m3t_dense_bn_relu_fwd": [_f, _i, _z, _i, _f, _f, _f, _f, C.c_float, _f, _i, _s],
+    "m3t_dense_bn_running": [_f, _f, _z, _i, _f, _f, C.c_float, _s],
+    "m3t_dense_bn_relu_bwd": [_f, _i, _f, _i, _z, _i, _f, _f, _f, _f, C.c_float, _i, _f, _i, _i, _f, _f, _f, _z, _s],
+    "m3t_dense_pool_fwd": [_f, _i, _z, _i, _i, _i, _f, _f, _f, _f, C.c_float, _f, _s],
+    "m3t_dense_pool_spread": [_f, _z, _i, _i, _i, _f, _s],
+    "m3t_dense_mean_fwd": [_f, _i, _z, _i, _i, _f, _f, _f, _f, C.c_float, _i, _f, _s],
+    "m3t_dense_mean_spread": [_f, _z, _i, _i, _i, _f, _s],
+    "m3t_dense_conv333": [_f, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _s],
+    "m3t_dense_wgrad_ws_bytes": [_z, _i, _i],
+    "m3t_dense_conv333_wgrad": [_f, _i, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f, _z, _s],
 }
 
-RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t}
+RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t,
+            "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t}
 
 _lib = None
 

@@ -3561,3 +3561,267 @@ class _SumHalves(torch.autograd.Function):
 
 def sum_halves(x):
     return _SumHalves.apply(x)
+
+
+# ----------------------------------------------------------------------------- DenseNet52_3D (reference models/densenet.py, --backbone densenet)
+# The whole feature stack -- four dense blocks, three transitions, norm5 + ReLU and the aggregation -- is ONE autograd operator on the kernels
+# of csrc/dense.hip and the GEMMs (DESIGN.md section 10b):
+#   * a dense block is one buffer [rows = N T H W][C_final]; the block's input (the stem's rows, or a transition's GEMM output) fills columns
+#     [0, C_0) and layer i's 3x3x3 convolution writes its 32 channels straight into [C_i, C_i + 32): no concatenation
+#   * batch statistics are computed once per column, when the column is written; each BatchNorm applies its own gamma / beta to them and
+#     updates its own running buffers (train mode); eval uses each module's running buffers
+#   * backward keeps one gradient buffer per block and walks the layers in reverse: layer i reads the finished gradient of its own 32 columns
+#     and adds its input gradient into [0, C_i) (stream order, no atomics); relu(bn(.)) operands are recomputed, not stored
+#   * a transition pools before its 1x1x1 convolution (both are linear per pixel and the convolution has no bias): the GEMM runs on a
+#     quarter of the rows and writes into the next block's buffer
+def _densenet_spec(net):
+    """[(layers, transition or None)] per block, each layer (norm1, conv1, norm2, conv2), or None when a module is outside what the kernels
+    cover (dropout p > 0, a BatchNorm without affine parameters / running statistics / momentum, another growth or bottleneck width)"""
+    blocks, feats = [], list(net.features.named_children())
+    ok_bn = lambda m: isinstance(m, torch.nn.BatchNorm3d) and m.affine and m.track_running_stats and m.momentum is not None  # noqa: E731
+    i = 0
+    while i < len(feats):
+        name, mod = feats[i]
+        if not name.startswith("denseblock"):
+            break
+        layers = []
+        for lay in mod.children():
+            n1, c1, n2, c2, dp = lay.norm1, lay.conv1, lay.norm2, lay.conv2, lay.dp
+            if not (ok_bn(n1) and ok_bn(n2) and dp.p == 0 and c1.weight.shape[0] == 128 and tuple(c2.weight.shape[:2]) == (32, 128)
+                    and c1.bias is None and c2.bias is None):
+                return None
+            layers.append((n1, c1, n2, c2))
+        trans = None
+        if i + 1 < len(feats) and feats[i + 1][0].startswith("transition"):
+            trans = feats[i + 1][1]
+            if not (ok_bn(trans.norm) and trans.conv.bias is None and hasattr(trans, "pool")):
+                return None
+            i += 1
+        blocks.append((layers, trans))
+        i += 1
+    if not blocks or feats[i][0] != "norm5" or not ok_bn(feats[i][1]) or net.agg_mode not in ("ap", "fc"):
+        return None
+    return blocks
+
+
+def densenet_ok(x, net):
+    """the dense kernels cover this call: a channels-last stem output or fp32 device planes [N, C, T, H, W]; no dropout"""
+    if isinstance(x, CLTensor):
+        dev_ok = x.data.is_cuda and x.data.dtype == torch.float32
+    else:
+        dev_ok = torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
+    return bool(dev_ok) and _densenet_spec(net) is not None
+
+
+def _dn_bn_fwd(x, ld, rows, Cc, st, bn, out, ldo):
+    _lib.check(lib().m3t_dense_bn_relu_fwd(_p(x), ld, rows, Cc, _p(st[0]), _p(st[1]), _p(bn.weight), _p(bn.bias), float(bn.eps), _p(out), ldo,
+                                           _stream()), "m3t_dense_bn_relu_fwd")
+
+
+def _dn_stats(x, off, ld, rows, Cc, mean, var, moff=0):
+    ws = workspace(mean.device, int(lib().m3t_dense_stats_ws_bytes(rows, Cc)))
+    _lib.check(lib().m3t_dense_col_stats(_p(x, off), rows, ld, Cc, _p(mean, moff), _p(var, moff), _p(ws), ws.numel() * 4, _stream()),
+               "m3t_dense_col_stats")
+
+
+def _dn_running(st, rows, Cc, bn):
+    _lib.check(lib().m3t_dense_bn_running(_p(st[0]), _p(st[1]), rows, Cc, _p(bn.running_mean), _p(bn.running_var), float(bn.momentum),
+                                          _stream()), "m3t_dense_bn_running")
+
+
+def _dn_bn_bwd(dy, ldy, x, ldx, rows, Cc, st, bn, training, dx, lddx, accumulate, dg, db):
+    ws = workspace(dy.device, int(lib().m3t_dense_stats_ws_bytes(rows, Cc)) + 8 * Cc)
+    _lib.check(lib().m3t_dense_bn_relu_bwd(_p(dy), ldy, _p(x), ldx, rows, Cc, _p(st[0]), _p(st[1]), _p(bn.weight), _p(bn.bias), float(bn.eps),
+                                           int(training), _p(dx), lddx, int(accumulate), _p(dg), _p(db), _p(ws), ws.numel() * 4, _stream()),
+               "m3t_dense_bn_relu_bwd")
+
+
+class _DenseNet(torch.autograd.Function):
+    """x0 [N T H W][C_0] (the stem's rows) -> [N T][C] (agg 'ap') or [N T][C H W] (agg 'fc'); *params: every gamma / beta / weight of the
+    feature stack in _densenet_params order"""
+
+    @staticmethod
+    def forward(ctx, x0, geo, *params):
+        N_, T_, H_, W_, blocks, norm5, mode, training = geo
+        dev = x0.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        x0 = _req(x0.contiguous(), "x")
+        P = N_ * T_
+        H, W = H_, W_
+        bufs, stats, saved = [], [], []
+        C0 = x0.shape[1]
+        buf = torch.empty(P * H * W, C0 + 32 * len(blocks[0][0]), **f32)
+        buf[:, :C0].copy_(x0)
+        for b, (layers, trans) in enumerate(blocks):
+            rows, Cf = P * H * W, buf.shape[1]
+            bst = torch.empty(2, Cf, **f32)
+            if training:
+                _dn_stats(buf, 0, Cf, rows, C0, bst[0], bst[1])
+            lay_saved = []
+            for l_, (n1, c1, n2, c2) in enumerate(layers):
+                Cl = C0 + 32 * l_
+                st1 = (bst[0, :Cl], bst[1, :Cl]) if training else (n1.running_mean, n1.running_var)
+                if training:
+                    _dn_running(st1, rows, Cl, n1)
+                a1 = torch.empty(rows, Cl, **f32)
+                _dn_bn_fwd(buf, Cf, rows, Cl, st1, n1, a1, Cl)
+                z1 = torch.empty(rows, 128, **f32)
+                sgemm(0, 1, rows, 128, Cl, a1, 0, Cl, c1.weight.detach(), 0, Cl, z1, 0, 128)
+                del a1
+                if training:
+                    st2 = torch.empty(2, 128, **f32)
+                    _dn_stats(z1, 0, 128, rows, 128, st2[0], st2[1])
+                    _dn_running(st2, rows, 128, n2)
+                else:
+                    st2 = torch.stack((n2.running_mean, n2.running_var))
+                a2 = torch.empty(rows, 128, **f32)
+                _dn_bn_fwd(z1, 128, rows, 128, st2, n2, a2, 128)
+                w2 = c2.weight.detach().permute(2, 3, 4, 1, 0).reshape(27, 128, 32).contiguous()
+                with _Timed("dense_conv333", 1, 2.0 * rows * 27 * 128 * 32) if PROFILE_ON[0] else _NULL:
+                    _lib.check(lib().m3t_dense_conv333(_p(a2), 128, N_, T_, H, W, 128, _p(w2), _p(buf, Cl), Cf, 32, 0, _stream()),
+                               "m3t_dense_conv333")
+                del a2
+                if training:
+                    _dn_stats(buf, Cl, Cf, rows, 32, bst[0], bst[1], Cl)
+                lay_saved.append((z1, st2))
+            bufs.append(buf)
+            stats.append(bst)
+            if trans is not None:
+                st = (bst[0], bst[1]) if training else (trans.norm.running_mean, trans.norm.running_var)
+                if training:
+                    _dn_running(st, rows, Cf, trans.norm)
+                Ho, Wo = H // 2, W // 2
+                pooled = torch.empty(P * Ho * Wo, Cf, **f32)
+                _lib.check(lib().m3t_dense_pool_fwd(_p(buf), Cf, P, H, W, Cf, _p(st[0]), _p(st[1]), _p(trans.norm.weight), _p(trans.norm.bias),
+                                                    float(trans.norm.eps), _p(pooled), _stream()), "m3t_dense_pool_fwd")
+                C0 = trans.conv.weight.shape[0]
+                nbuf = torch.empty(P * Ho * Wo, C0 + 32 * len(blocks[b + 1][0]), **f32)
+                sgemm(0, 1, P * Ho * Wo, C0, Cf, pooled, 0, Cf, trans.conv.weight.detach(), 0, Cf, nbuf, 0, nbuf.shape[1])
+                saved.append((lay_saved, pooled, (H, W)))
+                buf, H, W = nbuf, Ho, Wo
+            else:
+                saved.append((lay_saved, None, (H, W)))
+        rows, Cf = P * H * W, buf.shape[1]
+        st = (stats[-1][0], stats[-1][1]) if training else (norm5.running_mean, norm5.running_var)
+        if training:
+            _dn_running(st, rows, Cf, norm5)
+        y = torch.empty(P, Cf * (H * W if mode else 1), **f32)
+        _lib.check(lib().m3t_dense_mean_fwd(_p(buf), Cf, P, H * W, Cf, _p(st[0]), _p(st[1]), _p(norm5.weight), _p(norm5.bias), float(norm5.eps),
+                                            mode, _p(y), _stream()), "m3t_dense_mean_fwd")
+        ctx.geo, ctx.saved = geo, saved
+        ctx.save_for_backward(*bufs, *stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        N_, T_, H_, W_, blocks, norm5, mode, training = ctx.geo
+        nb = len(blocks)
+        tens = ctx.saved_tensors
+        bufs, stats = tens[:nb], tens[nb:]
+        dy = _req(dy.contiguous(), "dy")
+        dev = dy.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        P = N_ * T_
+        grads = []                                       # in _densenet_params order, built back to front
+        H, W = ctx.saved[-1][2]
+        buf = bufs[-1]
+        rows, Cf = P * H * W, buf.shape[1]
+        dbuf = torch.empty(rows, Cf, **f32)
+        _lib.check(lib().m3t_dense_mean_spread(_p(dy), P, H * W, Cf, mode, _p(dbuf), _stream()), "m3t_dense_mean_spread")
+        st = (stats[-1][0], stats[-1][1]) if training else (norm5.running_mean, norm5.running_var)
+        g5 = torch.empty(2, Cf, **f32)
+        _dn_bn_bwd(dbuf, Cf, buf, Cf, rows, Cf, st, norm5, training, dbuf, Cf, 0, g5[0], g5[1])
+        grads_rev = [g5[1], g5[0]]                       # (beta, gamma) reversed
+        for b in range(nb - 1, -1, -1):
+            layers, trans = blocks[b]
+            lay_saved, pooled, (H, W) = ctx.saved[b]
+            buf, bst = bufs[b], stats[b]
+            rows, Cf = P * H * W, buf.shape[1]
+            if trans is not None:
+                # dbuf: the gradient of the NEXT block's buffer; its columns [0, C0') are the gradient of this transition's GEMM output
+                nH, nW = H // 2, W // 2
+                nrows, nCf = P * nH * nW, dbuf.shape[1]
+                C0n = trans.conv.weight.shape[0]
+                dwt = torch.empty(C0n, Cf, **f32)
+                sgemm(1, 0, C0n, Cf, nrows, dbuf, 0, nCf, pooled, 0, Cf, dwt, 0, Cf)
+                dpool = torch.empty(nrows, Cf, **f32)
+                sgemm(0, 0, nrows, Cf, C0n, dbuf, 0, nCf, trans.conv.weight.detach(), 0, Cf, dpool, 0, Cf)
+                dcur = torch.empty(rows, Cf, **f32)
+                _lib.check(lib().m3t_dense_pool_spread(_p(dpool), P, H, W, Cf, _p(dcur), _stream()), "m3t_dense_pool_spread")
+                del dpool
+                st = (bst[0], bst[1]) if training else (trans.norm.running_mean, trans.norm.running_var)
+                gt = torch.empty(2, Cf, **f32)
+                _dn_bn_bwd(dcur, Cf, buf, Cf, rows, Cf, st, trans.norm, training, dcur, Cf, 0, gt[0], gt[1])
+                grads_rev += [dwt.view_as(trans.conv.weight), gt[1], gt[0]]
+                dbuf = dcur
+            C0 = Cf - 32 * len(layers)
+            for l_ in range(len(layers) - 1, -1, -1):
+                n1, c1, n2, c2 = layers[l_]
+                z1, st2 = lay_saved[l_]
+                Cl = C0 + 32 * l_
+                a2 = torch.empty(rows, 128, **f32)
+                _dn_bn_fwd(z1, 128, rows, 128, st2, n2, a2, 128)
+                ws = workspace(dev, int(lib().m3t_dense_wgrad_ws_bytes(rows, 128, 32)))
+                dw2 = torch.empty(27, 128, 32, **f32)
+                with _Timed("dense_conv333_wgrad", 2, 2.0 * rows * 27 * 128 * 32) if PROFILE_ON[0] else _NULL:
+                    _lib.check(lib().m3t_dense_conv333_wgrad(_p(a2), 128, _p(dbuf, Cl), Cf, N_, T_, H, W, 128, 32, _p(dw2), _p(ws),
+                                                             ws.numel() * 4, _stream()), "m3t_dense_conv333_wgrad")
+                w2f = c2.weight.detach().flip(2, 3, 4).permute(2, 3, 4, 0, 1).reshape(27, 32, 128).contiguous()
+                da2 = a2                                  # (a2 is dead once the weight gradient has read it: stream order)
+                with _Timed("dense_conv333_dgrad", 1, 2.0 * rows * 27 * 128 * 32) if PROFILE_ON[0] else _NULL:
+                    _lib.check(lib().m3t_dense_conv333(_p(dbuf, Cl), Cf, N_, T_, H, W, 32, _p(w2f), _p(da2), 128, 128, 0, _stream()),
+                               "m3t_dense_conv333")
+                g2 = torch.empty(2, 128, **f32)
+                _dn_bn_bwd(da2, 128, z1, 128, rows, 128, st2, n2, training, da2, 128, 0, g2[0], g2[1])
+                dz1 = da2
+                st1 = (bst[0, :Cl], bst[1, :Cl]) if training else (n1.running_mean, n1.running_var)
+                a1 = torch.empty(rows, Cl, **f32)
+                _dn_bn_fwd(buf, Cf, rows, Cl, st1, n1, a1, Cl)
+                dw1 = torch.empty(128, Cl, **f32)
+                sgemm(1, 0, 128, Cl, rows, dz1, 0, 128, a1, 0, Cl, dw1, 0, Cl)
+                da1 = a1
+                sgemm(0, 0, rows, Cl, 128, dz1, 0, 128, c1.weight.detach(), 0, Cl, da1, 0, Cl)
+                g1 = torch.empty(2, Cl, **f32)
+                _dn_bn_bwd(da1, Cl, buf, Cf, rows, Cl, st1, n1, training, dbuf, Cf, 1, g1[0], g1[1])
+                del a1, a2
+                grads_rev += [dw2.permute(2, 1, 0).reshape(c2.weight.shape), g2[1], g2[0], dw1.view_as(c1.weight), g1[1], g1[0]]
+        dx0 = dbuf[:, :C0].contiguous()
+        return (dx0, None) + tuple(reversed(grads_rev))
+
+
+def _densenet_params(blocks, norm5):
+    out = []
+    for layers, trans in blocks:
+        for n1, c1, n2, c2 in layers:
+            out += [n1.weight, n1.bias, c1.weight, n2.weight, n2.bias, c2.weight]
+        if trans is not None:
+            out += [trans.norm.weight, trans.norm.bias, trans.conv.weight]
+    return out + [norm5.weight, norm5.bias]
+
+
+def densenet(x, net):
+    """DenseNet52_3D.forward (reference models/densenet.py:76-93) on the dense kernels: x a CLTensor of the stem's rows or planes [N, C, T, H, W]
+    -> [N, T, C] (agg 'ap') or net.fc of the (c, h, w)-ordered final map (agg 'fc')"""
+    blocks = _densenet_spec(net)
+    norm5 = net.features.norm5
+    if isinstance(x, CLTensor):
+        N_, T_, H_, W_ = x.N, x.T, x.H, x.W
+        x0 = x.data
+    else:
+        N_, Cc, T_, H_, W_ = x.shape
+        x0 = bct_to_btc(x.reshape(N_, Cc, T_ * H_ * W_)).reshape(N_ * T_ * H_ * W_, Cc)
+    training = bool(net.training)
+    if training:
+        for layers, trans in blocks:
+            for n1, _, n2, _ in layers:
+                count_batch(n1.num_batches_tracked)
+                count_batch(n2.num_batches_tracked)
+            if trans is not None:
+                count_batch(trans.norm.num_batches_tracked)
+        count_batch(norm5.num_batches_tracked)
+    mode = 1 if net.agg_mode == "fc" else 0
+    geo = (N_, T_, H_, W_, blocks, norm5, mode, training)
+    y = _DenseNet.apply(x0, geo, *_densenet_params(blocks, norm5))
+    if mode:
+        return linear(y.view(N_, T_, -1), net.fc.weight, net.fc.bias, 0)
+    return y.view(N_, T_, -1)

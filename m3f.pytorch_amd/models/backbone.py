@@ -6,8 +6,9 @@ north_star path: `VA_3DVGGM` (:62-161), `VA_3DVGGM_Split` (:164-311, the default
 and data gradient: tap-walk implicit GEMMs, rounds 5-6; the VGG-M stems as a channels-last chain),
 BatchNorm3d + ReLU and spatial pooling, the temporal back-ends (BiGRU stacks, TCN) and the CBAM
 gates / BatchNorm2d inside the ResNet run in the HIP library; a configuration the library does not
-cover takes the stock op and says so once on stderr (m3t.ops.stock_fallback).  `VA_3DDenseNet` / `VA_VGGFace` are
-out of scope (not reachable from AffWild2VA.forward).
+cover takes the stock op and says so once on stderr (m3t.ops.stock_fallback).  `VA_3DDenseNet` (:375-423, `--backbone
+densenet`): the ResNet3D stem as a channels-last chain feeding models/densenet.py's DenseNet52_3D, whose dense blocks run as one
+operator on csrc/dense.hip.  `VA_VGGFace` is out of scope.
 """
 import math
 
@@ -17,6 +18,7 @@ from torch.nn.modules.utils import _triple
 
 from m3t import ops
 from .resnet import ResNet, ResNetV2, BasicBlock, BasicBlockV2
+from .densenet import DenseNet52_3D
 from .rnn import GRU, run_grus
 from .tcn import TemporalConvNet, WeightNormConv1d
 
@@ -303,3 +305,30 @@ class VA_3DResNet(nn.Module):
         if self.backend == 'gru':
             x = self.gru(x)
         return x
+
+
+class VA_3DDenseNet(nn.Module):
+    """reference models/backbone.py:375-423: the ResNet3D stem -> DenseNet52_3D(inputDim) -> [B, T, inputDim] -> GRU (backend 'gru')"""
+
+    def __init__(self, inputDim=392, hiddenDim=512, nLayers=2, nClasses=2, frameLen=16, backend='gru', frontend_agg_mode='ap', nFCs=1):
+        super().__init__()
+        self.inputDim, self.hiddenDim, self.nClasses = inputDim, hiddenDim, nClasses
+        self.frameLen, self.nLayers, self.backend, self.nFCs = frameLen, nLayers, backend, nFCs
+        final_fmap_size = 3
+        c1 = Conv3d(3, 64, kernel_size=(5, 7, 7), stride=(1, 2, 2), padding=(2, 3, 3), bias=False)
+        c1.cl_chain = True                 # the stem's rows go to the first dense block channels-last, without a transpose
+        self.c3d = nn.Sequential(
+            c1, BatchNorm3dReLU(64), nn.Identity(),
+            SpatialMaxPool3d(kernel_size=(1, 3, 3), stride=(1, 2, 2), padding=(0, 1, 1)))
+        self.densenet = DenseNet52_3D(self.inputDim, agg_mode=frontend_agg_mode, fmap_out_size=final_fmap_size)
+        if self.backend == 'gru':
+            self.gru = GRU(self.inputDim, self.hiddenDim, self.nLayers, self.nClasses, self.nFCs)
+        _init_like_reference(self)
+
+    def forward(self, x):
+        with ops.batch_counters():          # (the stem's and the DenseNet's 53 num_batches_tracked in one launch)
+            x = self.c3d(x)
+            x = self.densenet(x)
+            if self.backend == 'gru':
+                x = self.gru(x)
+            return x
