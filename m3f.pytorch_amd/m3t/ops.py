@@ -695,11 +695,18 @@ class batch_counters:
         if _NBT_PENDING[1] == 0:
             pending, _NBT_PENDING[0] = _NBT_PENDING[0], None
             if pending:
-                if len(pending) > 1 and all(t.is_cuda for t in pending):
-                    torch._foreach_add_(pending, 1)
+                # a BatchNorm applied k times in the block queued its counter k times: ONE add of k per distinct counter (the same tensor twice
+                # in a multi-tensor launch is two workgroups racing on one element)
+                counts = {}
+                for t in pending:
+                    e = counts.setdefault((t.device, t.data_ptr()), [t, 0])
+                    e[1] += 1
+                ts, ks = [e[0] for e in counts.values()], [e[1] for e in counts.values()]
+                if len(ts) > 1 and all(t.is_cuda for t in ts):
+                    torch._foreach_add_(ts, 1 if max(ks) == 1 else ks)
                 else:
-                    for t in pending:
-                        t.add_(1)
+                    for t, k in zip(ts, ks):
+                        t.add_(k)
         return False
 
 
@@ -2789,6 +2796,8 @@ class _Conv3dGemmWgrad(torch.autograd.Function):
         # weight / bias gradients straight into the flat gradient buffer where FlatGradDDP registered sinks (no AccumulateGrad add kernel)
         w_sink = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[1] and ctx.sink_refs[0] is not None) else None
         b_sink = _take_sink(ctx.sink_refs[1]) if (ctx.has_bias and ctx.needs_input_grad[2] and ctx.sink_refs[1] is not None) else None
+        if ctx.needs_input_grad[1] and ctx.sink_refs[0] is not None and w_sink is None:
+            join_wgrad(dy.device)      # (the sink was taken already this step: autograd adds the tensor returned below onto a slice a weight-gradient stream may still write -- see _Linear)
         # round 5: the data gradient of a stride-1 layer as a tap-walk contraction over dy channels-last (m3t_conv3d_taps: an implicit GEMM, no
         # patch matrix, no col2im) -- MIOpen's data gradient (Col2Im3dU + Tensile GEMMs) was ~5 ms of a C5 step
         taps_dx = (ctx.needs_input_grad[0] and CONV3D_TAPS[0] and ctx.pat is not None and tuple(st) == (1, 1, 1) and Co % 32 == 0 and Ci % 64 == 0
