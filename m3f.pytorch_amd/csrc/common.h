@@ -131,3 +131,4 @@ static __device__ __forceinline__ void m3t_block_raise_slot(unsigned long long* 
     }
 }
 bool m3t_f16x3_enabled();                                                      // env M3T_GEMM_F16X3 != 0
+bool m3t_gemm_tr_enabled();                                                    // env M3T_GEMM_TR != 0 (gemm.hip)

@@ -614,6 +614,18 @@ bool m3t_f16x3_enabled() {
     return on == 1;
 }
 
+// M3T_GEMM_TR=0: the fp16x3 tile kernels stage their row-contiguous operands (A of a TN product, B of an NN one) as 16-B records through
+// cross-lane swaps, and no transA = 1 / transB = 0 call takes the 128 x 256 tile -- the path before the transposed LDS reads (A/B runs, the
+// identity test: both paths hand every MFMA the same operands, the results are bit-identical)
+bool m3t_gemm_tr_enabled() {
+    static int on = -1;
+    if (on < 0) {
+        const char* e = getenv("M3T_GEMM_TR");
+        on = (e && e[0] == '0') ? 0 : 1;
+    }
+    return on == 1;
+}
+
 // fp16x3 GEMMs that run alone take the software-pipelined kernel too (measured, slots given: 9600 x 1024 x 1536 NN 140 -> 129 us,
 // 1536 x 1024 x 9600 TN 145 -> 138, 9600 x 1536 x 1024 NT 126 -> 122; C3 step 14.66 -> 14.57 ms)
 static bool f16x3_on_x6d() { return true; }
@@ -629,7 +641,8 @@ static bool x6_enabled() {
 
 // Kernel and split-K choice of one m3t_sgemm call.  kernel: 0 fp32-MFMA (gemm.hip), 1 the 16-bit-term 128-tile kernels
 // (gemm_x6.hip / gemm_x6d.hip: fp16x3, bf16x6, "high", bf16).
-// (internal flag of plan_gemm: the call is not an NT product -- measured, tools/gemm_one.py: the wide tile wins on the NT forms (+9..+21 %:
+// (internal flag of plan_gemm: the call is not an NT product: its plan (tile AND split-K count) stays the 128 tile's; m3t_sgemm_scaled moves
+// it to the wide tile with that same split-K count where tr_wide_wins says so.  Before the transposed-read image -- measured, tools/gemm_one.py: the wide tile wins on the NT forms (+9..+21 %:
 // 9600 x 1536 x 1024 122 -> 115 us, 9600 x 512 x 2048 112 -> 92), loses on NN 9600 x 2048 x 512 (86 -> 104: its row-contiguous B path spills
 // five registers) and is level on the TN weight gradients)
 constexpr int GEMM_NO_WIDE = 1 << 20;
@@ -643,6 +656,15 @@ static bool x6w_enabled() {
     if (on < 0) { const char* e = getenv("M3T_GEMM_X6W"); on = (e && e[0] == '0') ? 0 : 1; }
     return on == 1;
 }
+
+// The 128 x 256 tile for the fp16x3 products with a row-contiguous operand (NN, TN, segmented TN; the transposed-read image of gemm_x6w.hip,
+// M3T_GEMM_TR).  The call keeps the split-K count and the slabs of its 128-tile plan, and the wide tile sums k in the same order: the result
+// is bit-identical.  Taken for the calls issued beside a persistent scan (M3T_GEMM_BESIDE_SCAN): those find ~96 free CUs, so the wide grid's
+// thin last round costs nothing there and a quarter less LDS traffic per MFMA is what is left (C3 step, three alternating runs each,
+// profiles/gemm_tr_bench_ab.txt: no wide tile 11.99 ms, TN + segmented TN 11.86, + NN 11.80; parent 12.15).  Not for the calls that run alone:
+// on the empty chip 300 wide workgroups for 512 slots lose (NN 9600 x 1024 x 1536 130 -> 145 us, TN 1536 x 1024 x 9600 124 -> 130,
+// profiles/gemm_tr_ab.txt)
+static bool tr_wide_wins(int flags) { return (flags & M3T_GEMM_BESIDE_SCAN) != 0; }
 
 static GemmPlan plan_gemm(int transA, int M, int N, int K, int seg_len, bool vec, size_t ws_bytes, int flags) {
     GemmPlan g;
@@ -702,7 +724,8 @@ static GemmPlan plan_gemm(int transA, int M, int N, int K, int seg_len, bool vec
 
 extern "C" int m3t_sgemm_plan(int transA, int M, int N, int K, int seg_len, size_t ws_bytes, int flags, int* kernel, int* splits) {
     if (M <= 0 || N <= 0 || K < 0 || !kernel || !splits) return M3T_EINVAL;
-    // (the 128 x 256 tile exists for NT products only: a transA = 1 call never takes it; with transA = 0 this reports the NT form's plan)
+    // (the planner takes the 128 x 256 tile for NT products only: a transA = 1 call keeps its 128-tile plan, whichever tile m3t_sgemm_scaled
+    // then runs it on; with transA = 0 this reports the NT form's plan)
     const GemmPlan g = plan_gemm(transA, M, N, K, seg_len, true, ws_bytes, flags | (transA ? GEMM_NO_WIDE : 0));
     *kernel = g.kernel; *splits = g.splits;
     return 0;
@@ -756,6 +779,8 @@ extern "C" int m3t_sgemm_scaled(int transA, int transB, int M, int N, int K, con
     if (g.kernel != 0) {
         int rc;
         const int f16x3 = (!p.bf16 && !(flags & M3T_GEMM_HIGH) && (flags & M3T_GEMM_F16X3) && m3t_f16x3_enabled()) ? 1 : 0;
+        const bool wide_tr = f16x3 && !g.wide && !g.narrow && !(transA == 0 && transB == 1) && !(flags & M3T_GEMM_BACKGROUND) && N % 256 == 0 &&
+                             K % 32 == 0 && x6w_enabled() && m3t_gemm_tr_enabled() && tr_wide_wins(flags);
         const unsigned long long* use_a = nullptr; const unsigned long long* use_b = nullptr;
         if (f16x3) {
             // operands without a caller's magnitude slot are measured here, over the rows x columns each one spans in memory
@@ -768,7 +793,7 @@ extern "C" int m3t_sgemm_scaled(int transA, int transB, int M, int N, int K, con
             const int rm = m3t_f16x3_measure(ra, amax_a, rb, amax_b, &use_a, &use_b, s);
             if (rm) return rm;
         }
-        if (g.wide)
+        if (g.wide || wide_tr)
             rc = m3t_sgemm_x6w_launch(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, act, accumulate, seg_len, seg_stride,
                                       a_off, b_off, ws, splits, kchunk, f16x3 ? 3 : 0, use_a, use_b, s);
         else if (!g.narrow && K % 32 == 0 && (!f16x3 || f16x3_on_x6d()) && !(flags & (M3T_GEMM_BACKGROUND | M3T_GEMM_HIGH)) && (x6d_mode() == 1 || (x6d_mode() == 2 && !(flags & M3T_GEMM_BESIDE_SCAN))))      // ("high": measured better on gemm_x6.hip)

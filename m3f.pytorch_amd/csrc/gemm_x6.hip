@@ -28,6 +28,13 @@ constexpr int XM = 128, XN = 128, XK = 32;
 constexpr int PLANE = XM * 16 + 64;                // one k-octet plane: 128 rows x 16 B (+64 B: conflict-free K-contiguous stores)
 constexpr int SPLIT_BYTES = 4 * PLANE;             // one split of one operand: 4 k-octets
 constexpr int OPER_BYTES = 3 * SPLIT_BYTES;        // 24.75 KiB
+// TR (NS = 4): a row-contiguous operand lies in LDS as it lies in memory -- per term [k 32][128 rows] halves, a k-row every 320 B (256 + 64:
+// the four k-rows of one transposed read, and the two 16-row blocks of a 32-lane half, cover the 64 banks once) -- and a fragment is two
+// ds_read_b64_tr_b16 (four k each).  Two terms of 10 240 B fit the operand's 25 344.
+constexpr int TRROW = XM * 2 + 64;
+constexpr int TRTERM = XK * TRROW;
+static_assert(2 * TRTERM <= OPER_BYTES, "the transposed-read image must fit the operand's LDS");
+typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 struct X6Params {
     const float* A; const float* B; float* C; const float* bias; float* ws;
@@ -185,6 +192,35 @@ __device__ __forceinline__ void mc_store(unsigned char* __restrict__ S, const fl
     }
 }
 
+// TR form of mc_store (same thread map: k-quad tid >> 5, 4 rows at (tid & 31) * 4): the four rows' terms at one k are one 8-byte store per
+// term, a half-wave writes one whole 256-B k-row -- no cross-lane traffic.  PRE: an image's 16 bytes are already {hi r0..r3, lo r0..r3}: a copy
+template <int NS, bool PRE = false>
+__device__ __forceinline__ void mc_store_tr(unsigned char* __restrict__ S, const float4 (&r)[4], float scale = 1.f) {
+    const int tid = threadIdx.x & 255;
+    unsigned char* q = S + 4 * (tid >> 5) * TRROW + (tid & 31) * 8;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        unsigned a[3], b[3];
+        if (PRE) {
+            a[0] = __float_as_uint(r[e].x); b[0] = __float_as_uint(r[e].y); a[1] = __float_as_uint(r[e].z); b[1] = __float_as_uint(r[e].w);
+        } else {
+            split3_pair<NS>((f32x2){r[e].x, r[e].y}, a, scale);
+            split3_pair<NS>((f32x2){r[e].z, r[e].w}, b, scale);
+        }
+#pragma unroll
+        for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * TRTERM + e * TRROW) = (u32x2){a[s], b[s]};
+    }
+}
+// the 32x32x16 operand (lane: row lane & 31, k 8 (lane >> 5) ..+7) from a TR image: per 16-lane group a 4 k x 16 row block, lane 4 q + p of the
+// group addressing k-row q, rows 4 p ..+3; `at` = this lane's address for the first four k, the next four lie 4 k-rows on.  (EXEC is all ones
+// at every call: the callers sit in uniform control flow.)  The same eight halves in the same order as the 16-B record of the permlane path.
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* at) {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at + 4 * TRROW));
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // NS = 3: fp32-accurate product from 3 bf16 terms per operand (6 MFMAs per tile step);
 // NS = 1: plain bf16 operands (round to nearest even), fp32 accumulate -- the mixed-precision mode (M3T_GEMM_BF16)
 // CONV (TA == 0): the product is a dilated 1-D convolution over channel-last rows (models/tcn.py:16-46, the tcn_simple stages of
@@ -210,8 +246,11 @@ __device__ __forceinline__ void mc_store(unsigned char* __restrict__ S, const fl
 // k-quads are the eight pixels w .. w + 7 of one source row, a thread's quad one pixel's four channels -- so the A tile is again whole
 // 16-byte loads from shifted rows, 21 of 32 k useful (the patch matrix of this layer was 4.9 GB at 512 frames of 112 x 112).
 // PRE (NS == 4, K-contiguous operands): bit 0 -- A is a pre-split image, bit 1 -- B is (see kc_store)
-template <int TA, int TB, bool SEG, int NS, bool CONV = false, int XNT = 128, bool MW = false, int C3 = 0, int PRE = 0>
+// TR (NS == 4, M3T_GEMM_TR): the row-contiguous operands (A when TA == 1, B when TB == 0) take the transposed-read image
+template <int TA, int TB, bool SEG, int NS, bool CONV = false, int XNT = 128, bool MW = false, int C3 = 0, int PRE = 0, bool TR = false>
 __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt) {
+    static_assert(!TR || NS == 4, "the transposed-read image is sized for two terms");
+    constexpr bool TRA = TR && TA == 1, TRB = TR && TB == 0;
     if (MW) {                                            // this workgroup's problem of the batch
         const int z = blockIdx.z;
         p.A = bt.A[z]; p.B = bt.B[z]; p.C = bt.C[z]; p.bias = bt.bias[z];
@@ -417,10 +456,15 @@ __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt
         }
     };
     auto sstore = [&]() {
-        if (TA == 0) kc_store<NS, 4, (PRE & 1) != 0>(As, ra, sc_a); else mc_store<NS, (PRE & 1) != 0>(As, ra, sc_a);
-        if (TB == 1) kc_store<NS, BR, (PRE & 2) != 0>(Bs, rb, sc_b); else mc_store<NS, (PRE & 2) != 0>(Bs, rb, sc_b);
+        if (TA == 0) kc_store<NS, 4, (PRE & 1) != 0>(As, ra, sc_a);
+        else if (TRA) mc_store_tr<NS, (PRE & 1) != 0>(As, ra, sc_a);
+        else mc_store<NS, (PRE & 1) != 0>(As, ra, sc_a);
+        if (TB == 1) kc_store<NS, BR, (PRE & 2) != 0>(Bs, rb, sc_b);
+        else if (TRB) mc_store_tr<NS, (PRE & 2) != 0>(Bs, rb, sc_b);
+        else mc_store<NS, (PRE & 2) != 0>(Bs, rb, sc_b);
     };
 
+    const int tro = (8 * hi + ((lane >> 2) & 3)) * TRROW + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;      // TR: this lane's block address
     if (ntiles > 0) { gload(); sstore(); }
     __syncthreads();
     for (int t = 0; t < ntiles; ++t) {
@@ -434,8 +478,12 @@ __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt
             for (int s = 0; s < NP; ++s)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    fa[s][i] = *reinterpret_cast<const bf16x8*>(As + s * SPLIT_BYTES + (kh * 2 + hi) * PLANE + (wm * 64 + i * 32 + l31) * 16);
-                    if (i < NJ) fb[s][i] = *reinterpret_cast<const bf16x8*>(Bs + s * SPLIT_BYTES + (kh * 2 + hi) * PLANE + (wn * 32 * NJ + i * 32 + l31) * 16);
+                    if (TRA) fa[s][i] = tr_frag(As + tro + s * TRTERM + kh * 16 * TRROW + (wm * 64 + i * 32) * 2);
+                    else fa[s][i] = *reinterpret_cast<const bf16x8*>(As + s * SPLIT_BYTES + (kh * 2 + hi) * PLANE + (wm * 64 + i * 32 + l31) * 16);
+                    if (i < NJ) {
+                        if (TRB) fb[s][i] = tr_frag(Bs + tro + s * TRTERM + kh * 16 * TRROW + (wn * 32 * NJ + i * 32) * 2);
+                        else fb[s][i] = *reinterpret_cast<const bf16x8*>(Bs + s * SPLIT_BYTES + (kh * 2 + hi) * PLANE + (wn * 32 * NJ + i * 32 + l31) * 16);
+                    }
                 }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -573,21 +621,23 @@ int m3t_sgemm_x6_launch(int transA, int transB, int M, int N, int K, const float
     p.mw_len = p.mw_stride = p.mw_off = 0;
     p.c3_T = p.c3_H = p.c3_W = p.c3_To = p.c3_Ho = p.c3_Wo = p.c3_kt = p.c3_kh = p.c3_kw = p.c3_bt = p.c3_bh = p.c3_bw = p.c3_sg = p.c3_C = 0; p.c3_st = p.c3_sh = p.c3_sw = 1; p.tr_S = 0;
     dim3 grid(N / (narrow ? 64 : XN), M / XM, splits), block(256);
-#define M3T_X6_DISPATCH(NS_, XNT_)                                                                                                  \
-    do {                                                                                                                           \
-        if (seg_len > 0) sgemm_x6_kernel<1, 0, true, NS_, false, XNT_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);                            \
-        else if (transA == 0 && transB == 1) sgemm_x6_kernel<0, 1, false, NS_, false, XNT_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);      \
-        else if (transA == 0 && transB == 0) sgemm_x6_kernel<0, 0, false, NS_, false, XNT_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);      \
-        else if (transA == 1 && transB == 0) sgemm_x6_kernel<1, 0, false, NS_, false, XNT_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);      \
-        else sgemm_x6_kernel<1, 1, false, NS_, false, XNT_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);                                       \
+#define M3T_X6_DISPATCH(NS_, XNT_, TR_)                                                                                                                 \
+    do {                                                                                                                                               \
+        if (seg_len > 0) sgemm_x6_kernel<1, 0, true, NS_, false, XNT_, false, 0, 0, TR_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);                  \
+        else if (transA == 0 && transB == 1) sgemm_x6_kernel<0, 1, false, NS_, false, XNT_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);               \
+        else if (transA == 0 && transB == 0) sgemm_x6_kernel<0, 0, false, NS_, false, XNT_, false, 0, 0, TR_><<<grid, block, dyn_lds, s>>>(p, g_no_batch); \
+        else if (transA == 1 && transB == 0) sgemm_x6_kernel<1, 0, false, NS_, false, XNT_, false, 0, 0, TR_><<<grid, block, dyn_lds, s>>>(p, g_no_batch); \
+        else sgemm_x6_kernel<1, 1, false, NS_, false, XNT_, false, 0, 0, TR_><<<grid, block, dyn_lds, s>>>(p, g_no_batch);                             \
     } while (0)
     // bf16_operands: 1 = bf16 mode (one product), 2 = "high" mode (two bf16 terms per operand, four products), 0 = fp32-accurate (bf16x6)
     // 3 = fp16x3 (two fp16 terms per scaled operand, three products; amax = the operands' magnitude slots)
     if (bf16_operands == 3 && (!amax_a || !amax_b)) return M3T_EINVAL;
-    if (bf16_operands == 1) { if (narrow) M3T_X6_DISPATCH(1, 64); else M3T_X6_DISPATCH(1, 128); }
-    else if (bf16_operands == 2) { if (narrow) M3T_X6_DISPATCH(2, 64); else M3T_X6_DISPATCH(2, 128); }
-    else if (bf16_operands == 3) { if (narrow) M3T_X6_DISPATCH(4, 64); else M3T_X6_DISPATCH(4, 128); }
-    else { if (narrow) M3T_X6_DISPATCH(3, 64); else M3T_X6_DISPATCH(3, 128); }
+    const bool tr = m3t_gemm_tr_enabled();
+    if (bf16_operands == 1) { if (narrow) M3T_X6_DISPATCH(1, 64, false); else M3T_X6_DISPATCH(1, 128, false); }
+    else if (bf16_operands == 2) { if (narrow) M3T_X6_DISPATCH(2, 64, false); else M3T_X6_DISPATCH(2, 128, false); }
+    else if (bf16_operands == 3 && tr) { if (narrow) M3T_X6_DISPATCH(4, 64, true); else M3T_X6_DISPATCH(4, 128, true); }
+    else if (bf16_operands == 3) { if (narrow) M3T_X6_DISPATCH(4, 64, false); else M3T_X6_DISPATCH(4, 128, false); }
+    else { if (narrow) M3T_X6_DISPATCH(3, 64, false); else M3T_X6_DISPATCH(3, 128, false); }
 #undef M3T_X6_DISPATCH
     hipError_t e = hipGetLastError();
     return (int)e;
@@ -614,13 +664,14 @@ int m3t_sgemm_x6_window_launch(int n, const m3t_window_problem* pr, int transB, 
     p.cv_amax = nullptr;
     p.mw_len = mw_len; p.mw_stride = mw_stride; p.mw_off = mw_off;
     dim3 grid(N / (narrow ? 64 : XN), M / XM, n), block(256);
-#define M3T_X6W_GO(NS_, XNT_)                                                                             \
-    do {                                                                                                  \
-        if (transB) sgemm_x6_kernel<0, 1, false, NS_, false, XNT_, true><<<grid, block, 0, s>>>(p, bt);   \
-        else sgemm_x6_kernel<0, 0, false, NS_, false, XNT_, true><<<grid, block, 0, s>>>(p, bt);          \
+#define M3T_X6W_GO(NS_, XNT_, TR_)                                                                                  \
+    do {                                                                                                            \
+        if (transB) sgemm_x6_kernel<0, 1, false, NS_, false, XNT_, true><<<grid, block, 0, s>>>(p, bt);             \
+        else sgemm_x6_kernel<0, 0, false, NS_, false, XNT_, true, 0, 0, TR_><<<grid, block, 0, s>>>(p, bt);         \
     } while (0)
-    if (f16x3) { if (narrow) M3T_X6W_GO(4, 64); else M3T_X6W_GO(4, 128); }
-    else { if (narrow) M3T_X6W_GO(3, 64); else M3T_X6W_GO(3, 128); }
+    if (f16x3 && m3t_gemm_tr_enabled()) { if (narrow) M3T_X6W_GO(4, 64, true); else M3T_X6W_GO(4, 128, true); }
+    else if (f16x3) { if (narrow) M3T_X6W_GO(4, 64, false); else M3T_X6W_GO(4, 128, false); }
+    else { if (narrow) M3T_X6W_GO(3, 64, false); else M3T_X6W_GO(3, 128, false); }
 #undef M3T_X6W_GO
     return (int)hipGetLastError();
 }
@@ -670,16 +721,18 @@ int m3t_conv3d_taps_launch(const float* src, const float* w_taps, float* dst, in
     const int tm = (p.M + XM - 1) / XM;                        // (round 6: a ragged last row tile)
     const bool narrow = (Cd % 128 != 0) || (Cd / XN) * tm * splits <= 384;
     dim3 grid(Cd / (narrow ? 64 : XN), tm, splits), block(256);
-#define M3T_C3_GO(NS_)                                                                                                  \
-    do {                                                                                                               \
-        if (narrow) sgemm_x6_kernel<0, 0, false, NS_, false, 64, false, 1><<<grid, block, 0, s>>>(p, g_no_batch);   \
-        else sgemm_x6_kernel<0, 0, false, NS_, false, 128, false, 1><<<grid, block, 0, s>>>(p, g_no_batch);         \
+#define M3T_C3_GO(NS_, TR_)                                                                                                  \
+    do {                                                                                                                     \
+        if (narrow) sgemm_x6_kernel<0, 0, false, NS_, false, 64, false, 1, 0, TR_><<<grid, block, 0, s>>>(p, g_no_batch);    \
+        else sgemm_x6_kernel<0, 0, false, NS_, false, 128, false, 1, 0, TR_><<<grid, block, 0, s>>>(p, g_no_batch);          \
     } while (0)
     if (pre) {
         if (narrow) sgemm_x6_kernel<0, 1, false, 4, false, 64, false, 1, 3><<<grid, block, 0, s>>>(p, g_no_batch);
         else sgemm_x6_kernel<0, 1, false, 4, false, 128, false, 1, 3><<<grid, block, 0, s>>>(p, g_no_batch);
     }
-    else if (f16x3) M3T_C3_GO(4); else M3T_C3_GO(3);
+    else if (f16x3 && m3t_gemm_tr_enabled()) M3T_C3_GO(4, true);
+    else if (f16x3) M3T_C3_GO(4, false);
+    else M3T_C3_GO(3, false);
 #undef M3T_C3_GO
     return (int)hipGetLastError();
 }
@@ -734,9 +787,16 @@ int m3t_conv3d_wgrad_launch(const float* x_cl, const float* dy_cl, float* dwt, i
     p.c3_st = stride3[0]; p.c3_sh = stride3[1]; p.c3_sw = stride3[2]; p.tr_S = 0;
     const bool narrow = (Co % 128 != 0) || (Co / XN) * (Mp / XM) * splits <= 384;
     dim3 grid(Co / (narrow ? 64 : XN), Mp / XM, splits), block(256);
-    if (f16x3 && pre) {
+    const bool tr = m3t_gemm_tr_enabled();
+    if (f16x3 && pre && tr) {
+        if (narrow) sgemm_x6_kernel<1, 0, false, 4, false, 64, false, 2, 3, true><<<grid, block, 0, s>>>(p, g_no_batch);
+        else sgemm_x6_kernel<1, 0, false, 4, false, 128, false, 2, 3, true><<<grid, block, 0, s>>>(p, g_no_batch);
+    } else if (f16x3 && pre) {
         if (narrow) sgemm_x6_kernel<1, 0, false, 4, false, 64, false, 2, 3><<<grid, block, 0, s>>>(p, g_no_batch);
         else sgemm_x6_kernel<1, 0, false, 4, false, 128, false, 2, 3><<<grid, block, 0, s>>>(p, g_no_batch);
+    } else if (f16x3 && tr) {
+        if (narrow) sgemm_x6_kernel<1, 0, false, 4, false, 64, false, 2, 0, true><<<grid, block, 0, s>>>(p, g_no_batch);
+        else sgemm_x6_kernel<1, 0, false, 4, false, 128, false, 2, 0, true><<<grid, block, 0, s>>>(p, g_no_batch);
     } else if (f16x3) {
         if (narrow) sgemm_x6_kernel<1, 0, false, 4, false, 64, false, 2><<<grid, block, 0, s>>>(p, g_no_batch);
         else sgemm_x6_kernel<1, 0, false, 4, false, 128, false, 2><<<grid, block, 0, s>>>(p, g_no_batch);
@@ -768,15 +828,17 @@ int m3t_conv_x6_launch(const float* x, const float* w_t, const float* bias, cons
     // 128 x 64 tiles when 128 x 128 ones would leave most CUs with one workgroup (Co = 512 at B*T = 9600: 300 tiles)
     const bool narrow = (Co / XN) * (p.M / XM) <= 384;
     dim3 grid(Co / (narrow ? 64 : XN), p.M / XM, 1), block(256);
-#define M3T_CONV_GO(TB_, NS_)                                                                          \
-    do {                                                                                               \
-        if (narrow) sgemm_x6_kernel<0, TB_, false, NS_, true, 64><<<grid, block, 0, s>>>(p, g_no_batch); \
-        else sgemm_x6_kernel<0, TB_, false, NS_, true, 128><<<grid, block, 0, s>>>(p, g_no_batch);     \
+#define M3T_CONV_GO(TB_, NS_, TR_)                                                                                       \
+    do {                                                                                                                 \
+        if (narrow) sgemm_x6_kernel<0, TB_, false, NS_, true, 64, false, 0, 0, TR_><<<grid, block, 0, s>>>(p, g_no_batch); \
+        else sgemm_x6_kernel<0, TB_, false, NS_, true, 128, false, 0, 0, TR_><<<grid, block, 0, s>>>(p, g_no_batch);     \
     } while (0)
     if (anti) {
-        if (bf16_operands == 1) M3T_CONV_GO(0, 1); else if (bf16_operands == 2) M3T_CONV_GO(0, 2); else if (bf16_operands == 3) M3T_CONV_GO(0, 4); else M3T_CONV_GO(0, 3);
+        if (bf16_operands == 1) M3T_CONV_GO(0, 1, false); else if (bf16_operands == 2) M3T_CONV_GO(0, 2, false);
+        else if (bf16_operands == 3 && m3t_gemm_tr_enabled()) M3T_CONV_GO(0, 4, true);
+        else if (bf16_operands == 3) M3T_CONV_GO(0, 4, false); else M3T_CONV_GO(0, 3, false);
     } else {
-        if (bf16_operands == 1) M3T_CONV_GO(1, 1); else if (bf16_operands == 2) M3T_CONV_GO(1, 2); else if (bf16_operands == 3) M3T_CONV_GO(1, 4); else M3T_CONV_GO(1, 3);
+        if (bf16_operands == 1) M3T_CONV_GO(1, 1, false); else if (bf16_operands == 2) M3T_CONV_GO(1, 2, false); else if (bf16_operands == 3) M3T_CONV_GO(1, 4, false); else M3T_CONV_GO(1, 3, false);
     }
 #undef M3T_CONV_GO
     return (int)hipGetLastError();

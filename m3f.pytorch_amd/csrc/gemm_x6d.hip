@@ -28,6 +28,14 @@ constexpr int PLANEB = BM * 16 + 128;              // one k-octet plane: 128 row
 constexpr int SPLITB = 2 * PLANEB;
 constexpr int OPERB = 3 * SPLITB;
 constexpr int STAGEB = 2 * OPERB;                  // 26 112 B
+// TR (NS = 4): a row-contiguous operand lies in LDS as it lies in memory -- per term [k 16][128 rows] halves, a k-row every 320 B (256 + 64:
+// the four k-rows of one transposed read, and the two 16-row blocks of a 32-lane half, cover the 64 banks once) -- and a fragment is two
+// ds_read_b64_tr_b16 (four k each).  Two terms of 5 120 B fit the operand's 13 056.
+constexpr int TRROW = BM * 2 + 64;
+constexpr int TRTERM = BKS * TRROW;
+static_assert(2 * TRTERM <= OPERB, "the transposed-read image must fit the operand's LDS");
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 struct X6DParams {
     const float* A; const float* B; float* C; const float* bias; float* ws;
@@ -112,11 +120,38 @@ __device__ __forceinline__ void mc_store_c(unsigned char* __restrict__ S, const 
     }
 }
 
+// TR form of mc_store_c (same thread map): the four rows' terms at one k are one 8-byte store per term, no cross-lane traffic
+template <int NS>
+__device__ __forceinline__ void mc_store_tr(unsigned char* __restrict__ S, const f32x4 (&r)[2], float scale) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned char* q = S + (8 * (w >> 1) + 2 * (lane >> 4)) * TRROW + ((w & 1) * 64 + (lane & 15) * 4) * 2;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        unsigned a[3], b[3];
+        split3_pair<NS>((f32x2){r[e].x, r[e].y}, a, scale);
+        split3_pair<NS>((f32x2){r[e].z, r[e].w}, b, scale);
+#pragma unroll
+        for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * TRTERM + e * TRROW) = (u32x2){a[s], b[s]};
+    }
+}
+// the 32x32x16 operand (lane: row lane & 31, k 8 (lane >> 5) ..+7) from a TR image: per 16-lane group a 4 k x 16 row block, lane 4 q + p of the
+// group addressing k-row q, rows 4 p ..+3; `at` = this lane's address for the first four k, the next four lie 4 k-rows on.  (EXEC is all ones
+// at every call: the callers sit in uniform control flow.)  The same eight halves in the same order as the 16-B record of the permlane path.
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* at) {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at + 4 * TRROW));
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // CONV (TA == 0): k = (tap j, channel c), A[m][k] = x[m + off_j][c] with rows whose source frame falls outside the clip read as zero
 // (a 16-deep stage lies inside one tap: C % 32 == 0); TB == 1: B = one [Co][Ci] plane per tap; TB == 0 (data gradient): the
 // row-major [K*Ci][Co] matrix.  Epilogue: bias, pre-activation copy, ReLU x dropout mask, residual add + ReLU, as gemm_x6.hip's.
-template <int TA, int TB, bool SEG, int NS, bool CONV = false>
+// TR (NS = 4, M3T_GEMM_TR): the row-contiguous operands (A when TA == 1, B when TB == 0) take the transposed-read image
+template <int TA, int TB, bool SEG, int NS, bool CONV = false, bool TR = false>
 __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
+    static_assert(!TR || NS == 4, "the transposed-read image is sized for two terms");
+    constexpr bool TRA = TR && TA == 1, TRB = TR && TB == 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];     // stage 0 | stage 1, each A | B
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;                  // 2 x 2 waves: 64 x 64 of the tile each
@@ -234,8 +269,8 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
         ++loaded;
     };
     auto sstore = [&](unsigned char* st, const f32x4 (&ra)[2], const f32x4 (&rb)[2]) {
-        if (TA == 0) kc_store_c<NS>(st, ra, sc_a); else mc_store_c<NS>(st, ra, sc_a);
-        if (TB == 1) kc_store_c<NS>(st + OPERB, rb, sc_b); else mc_store_c<NS>(st + OPERB, rb, sc_b);
+        if (TA == 0) kc_store_c<NS>(st, ra, sc_a); else if (TRA) mc_store_tr<NS>(st, ra, sc_a); else mc_store_c<NS>(st, ra, sc_a);
+        if (TB == 1) kc_store_c<NS>(st + OPERB, rb, sc_b); else if (TRB) mc_store_tr<NS>(st + OPERB, rb, sc_b); else mc_store_c<NS>(st + OPERB, rb, sc_b);
     };
 
     // the products, smallest first.  NS = 3: (a3,b1) (a2,b2) (a1,b3) (a2,b1) (a1,b2) (a1,b1); NS = 2 ("high" mode): the last four
@@ -243,8 +278,9 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
     constexpr int NSB = NS == 4 ? 2 : NS;             // (the bf16 product table; unused when NS = 4)
     constexpr int PA[6] = {NSB - 1, NSB / 2, NSB == 2 ? 1 : 0, NSB == 2 ? 1 : NSB / 2, 0, 0};
     constexpr int PB[6] = {0, NSB / 2, NSB == 2 ? 1 : NSB - 1, 0, NSB == 2 ? 1 : NSB / 2, 0};
-    const int fro_a = hi * PLANEB + (wm * 64 + l31) * 16;
-    const int fro_b = OPERB + hi * PLANEB + (wn * 64 + l31) * 16;
+    const int tro = (8 * hi + ((lane >> 2) & 3)) * TRROW + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;      // TR: this lane's block address
+    const int fro_a = TRA ? tro + wm * 128 : hi * PLANEB + (wm * 64 + l31) * 16;
+    const int fro_b = OPERB + (TRB ? tro + wn * 128 : hi * PLANEB + (wn * 64 + l31) * 16);
     // one stage, straight-line: the fragments of `cur`, the split + store of the held stage into `nxt`, the 24 MFMAs -- no
     // scheduling fence between them: the split's VALU / LDS instructions go into the shadow of the dependent MFMA chains
     auto stage = [&](const unsigned char* cur, unsigned char* nxt, const f32x4 (&ua)[2], const f32x4 (&ub)[2]) {
@@ -254,8 +290,10 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
         for (int s = 0; s < NP; ++s)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                fa[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_a + s * SPLITB + i * 512);
-                fb[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_b + s * SPLITB + i * 512);
+                if (TRA) fa[s][i] = tr_frag(cur + fro_a + s * TRTERM + i * 64);
+                else fa[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_a + s * SPLITB + i * 512);
+                if (TRB) fb[s][i] = tr_frag(cur + fro_b + s * TRTERM + i * 64);
+                else fb[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_b + s * SPLITB + i * 512);
             }
         sstore(nxt, ua, ub);                                  // (after the last stage: a stage nobody reads)
 #pragma unroll
@@ -347,29 +385,30 @@ int m3t_sgemm_x6d_launch(int transA, int transB, int M, int N, int K, const floa
     p.cv_drop = m3t_make_drop(0.f, 0ull);
     dim3 grid(N / BN, M / BM, splits), block(NTH);
     const size_t lds = 2 * (size_t)STAGEB;
-#define M3T_X6D_GO(TA_, TB_, SEG_, NS_)                                                                               \
+    const bool tr = m3t_gemm_tr_enabled();
+#define M3T_X6D_GO(TA_, TB_, SEG_, NS_, TR_)                                                                          \
     do {                                                                                                               \
         static bool attr_set = false;                                                                                  \
         if (!attr_set) {                                                                                               \
-            hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6d_kernel<TA_, TB_, SEG_, NS_>,                    \
+            hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6d_kernel<TA_, TB_, SEG_, NS_, false, TR_>,        \
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
             if (ea != hipSuccess) return (int)ea;                                                                      \
             attr_set = true;                                                                                           \
         }                                                                                                              \
-        sgemm_x6d_kernel<TA_, TB_, SEG_, NS_><<<grid, block, lds, s>>>(p);                                             \
+        sgemm_x6d_kernel<TA_, TB_, SEG_, NS_, false, TR_><<<grid, block, lds, s>>>(p);                                 \
     } while (0)
-#define M3T_X6D_DISPATCH(NS_)                                                                                        \
+#define M3T_X6D_DISPATCH(NS_, TR_)                                                                                   \
     do {                                                                                                               \
-        if (seg_len > 0) M3T_X6D_GO(1, 0, true, NS_);                                                                  \
-        else if (transA == 0 && transB == 1) M3T_X6D_GO(0, 1, false, NS_);                                             \
-        else if (transA == 0 && transB == 0) M3T_X6D_GO(0, 0, false, NS_);                                             \
-        else if (transA == 1 && transB == 0) M3T_X6D_GO(1, 0, false, NS_);                                             \
-        else M3T_X6D_GO(1, 1, false, NS_);                                                                             \
+        if (seg_len > 0) M3T_X6D_GO(1, 0, true, NS_, TR_);                                                             \
+        else if (transA == 0 && transB == 1) M3T_X6D_GO(0, 1, false, NS_, false);                                      \
+        else if (transA == 0 && transB == 0) M3T_X6D_GO(0, 0, false, NS_, TR_);                                        \
+        else if (transA == 1 && transB == 0) M3T_X6D_GO(1, 0, false, NS_, TR_);                                        \
+        else M3T_X6D_GO(1, 1, false, NS_, TR_);                                                                        \
     } while (0)
-    if (bf16_operands == 1) M3T_X6D_DISPATCH(1);
-    else if (bf16_operands == 2) M3T_X6D_DISPATCH(2);
-    else if (bf16_operands == 3) M3T_X6D_DISPATCH(4);       // fp16x3
-    else M3T_X6D_DISPATCH(3);
+    if (bf16_operands == 1) M3T_X6D_DISPATCH(1, false);
+    else if (bf16_operands == 2) M3T_X6D_DISPATCH(2, false);
+    else if (bf16_operands == 3) { if (tr) M3T_X6D_DISPATCH(4, true); else M3T_X6D_DISPATCH(4, false); }      // fp16x3
+    else M3T_X6D_DISPATCH(3, false);
 #undef M3T_X6D_DISPATCH
 #undef M3T_X6D_GO
     return (int)hipGetLastError();

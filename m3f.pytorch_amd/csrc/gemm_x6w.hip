@@ -33,6 +33,14 @@ constexpr int planes_of(int NS) { return NS == 4 ? 2 : NS; }
 constexpr int opera(int NS) { return planes_of(NS) * 2 * PLA; }
 constexpr int operb(int NS) { return planes_of(NS) * 2 * PLB; }
 constexpr int stageb(int NS) { return opera(NS) + operb(NS); }
+// TR (NS = 4): a row-contiguous operand lies in LDS as it lies in memory -- per term [k 16][rows] halves, a k-row every 2 x rows + 64 B (the
+// four k-rows of one transposed read, and the two 16-row blocks of a 32-lane half, cover the 64 banks once) -- and a fragment is two
+// ds_read_b64_tr_b16 (four k each): gemm_x6d.hip's image, B's k-rows 256 wide
+constexpr int TRROWA = WM * 2 + 64, TRROWB = WN * 2 + 64;
+constexpr int opera_of(int NS, bool tr) { return tr ? 2 * WKS * TRROWA : opera(NS); }
+constexpr int operb_of(int NS, bool tr) { return tr ? 2 * WKS * TRROWB : operb(NS); }
+constexpr int stageb_of(int NS, int TA, int TB, bool tr) { return opera_of(NS, tr && TA == 1) + operb_of(NS, tr && TB == 0); }
+typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 struct X6WParams {
     const float* A; const float* B; float* C; const float* bias; float* ws;
@@ -104,15 +112,45 @@ __device__ __forceinline__ void mc_store_w(unsigned char* __restrict__ S, const 
     }
 }
 
+// TR form of mc_store_w (same thread map): the four rows' terms at one k are one 8-byte store per term, no cross-lane traffic; ROW = the
+// image's k-row stride
+template <int NS, int ROW>
+__device__ __forceinline__ void mc_store_wtr(unsigned char* __restrict__ S, const f32x4& r0, const f32x4& r1, float scale, int half) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    unsigned char* q = S + (8 * (w >> 1) + 2 * (lane >> 4)) * ROW + (half * 128 + (w & 1) * 64 + (lane & 15) * 4) * 2;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const f32x4& r = e ? r1 : r0;
+        unsigned a[3], b[3];
+        split3_pair<NS>((f32x2){r.x, r.y}, a, scale);
+        split3_pair<NS>((f32x2){r.z, r.w}, b, scale);
+#pragma unroll
+        for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * WKS * ROW + e * ROW) = (u32x2){a[s], b[s]};
+    }
+}
+// the 32x32x16 operand (lane: row lane & 31, k 8 (lane >> 5) ..+7) from a TR image: per 16-lane group a 4 k x 16 row block, lane 4 q + p of the
+// group addressing k-row q, rows 4 p ..+3; `at` = this lane's address for the first four k, the next four lie 4 k-rows on.  (EXEC is all ones
+// at every call: the callers sit in uniform control flow.)  The same eight halves in the same order as the 16-B record of the permlane path.
+template <int ROW>
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* at) {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at + 4 * ROW));
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // BD (TA = 0, TB = 1, NS = 4): the B operand is a STAGED IMAGE of the weights (m3t_f16x3_image_b: [N / 64][K / 8][term][64 rows][16 B] -- one
 // 1-KiB piece per (64-row block, k-octet, term)) and reaches LDS by LDS-DMA (global_load_lds_dwordx4: one piece per wave instruction, no
 // registers, no conversion, no ds_write): wave w fetches row block w of the 256-row tile, four pieces per 16-k stage.  Why (NOTEBOOK R5.4b):
 // of the 134 us of a 128-tile launch 28 are the register -> LDS store path of the split operands; the 256-row B tile is two thirds of them.
-template <int TA, int TB, bool SEG, int NS, int BD = 0>
+// TR (NS = 4, M3T_GEMM_TR): the row-contiguous operands (A when TA == 1, B when TB == 0) take the transposed-read image
+template <int TA, int TB, bool SEG, int NS, int BD = 0, bool TR = false>
 __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
+    static_assert(!TR || (NS == 4 && !BD), "the transposed-read image is sized for two terms");
+    constexpr bool TRA = TR && TA == 1, TRB = TR && TB == 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];     // stage 0 | stage 1, each A | B
     constexpr int NP = planes_of(NS);
-    constexpr int OPA = opera(NS), STG = stageb(NS);
+    constexpr int OPA = opera_of(NS, TRA), STG = stageb_of(NS, TA, TB, TR);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;                  // 2 x 2 waves: 64 x 128 of the tile each
     const int l31 = lane & 31, hi = lane >> 5;
@@ -170,17 +208,13 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
             for (int e = 0; e < 2; ++e) pb[2 * h + e] = p.B + (size_t)(k_begin + mck + e) * p.ldb + bn + 128 * h + mcr;
         b_step = (size_t)WKS * p.ldb;
     }
-    int sq[2] = {0, 0}, sr[2] = {0, 0};                       // segmented K: (segment, offset) of this lane's two k
+    int srow = 0, sr = 0;                                     // segmented K: storage row and offset in its segment of this lane's first k (its second is the next k)
     if (SEG) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int k = k_begin + mck + e;
-            sq[e] = k / p.seg_len; sr[e] = k % p.seg_len;
-        }
+        const int k = k_begin + mck;
+        srow = (k / p.seg_len) * p.seg_stride + k % p.seg_len; sr = k % p.seg_len;
         pa[0] = p.A + (size_t)p.a_off * p.lda + bm + mcr;
         pb[0] = p.B + (size_t)p.b_off * p.ldb + bn + mcr;
     }
-
     f32x4 ra0[2], rb0[4], ra1[2], rb1[4];                    // raw fp32 values of two stages in flight
     int loaded = 0;
     auto gload = [&](f32x4 (&ra)[2], f32x4 (&rb)[4]) {        // fetch the next stage; past the end: re-fetch the last one (unused)
@@ -188,13 +222,14 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
         if (SEG) {
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                const size_t row = (size_t)sq[e] * p.seg_stride + sr[e];
+                const size_t row = (size_t)(srow + e + ((e && sr + 1 >= p.seg_len) ? p.seg_stride - p.seg_len : 0));
                 ra[e] = *reinterpret_cast<const f32x4*>(pa[0] + row * p.lda);
                 rb[e] = *reinterpret_cast<const f32x4*>(pb[0] + row * p.ldb);
                 rb[2 + e] = *reinterpret_cast<const f32x4*>(pb[0] + row * p.ldb + 128);
-                int r = sr[e] + (adv ? WKS : 0), q = sq[e];
-                if (r >= p.seg_len) { r -= p.seg_len; ++q; }   // seg_len >= 32 > WKS: at most one wrap
-                sr[e] = r; sq[e] = q;
+            }
+            if (adv) {                                         // seg_len >= 32 > WKS: at most one wrap
+                sr += WKS; srow += WKS;
+                if (sr >= p.seg_len) { sr -= p.seg_len; srow += p.seg_stride - p.seg_len; }
             }
         } else {
 #pragma unroll
@@ -227,25 +262,35 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
         }
     };
     auto sstore = [&](unsigned char* st, const f32x4 (&ra)[2], const f32x4 (&rb)[4]) {
-        if (TA == 0) kc_store_w<NS, 2, PLA>(st, ra, sc_a); else mc_store_w<NS, PLA>(st, ra[0], ra[1], sc_a, 0);
+        if (TA == 0) kc_store_w<NS, 2, PLA>(st, ra, sc_a);
+        else if (TRA) mc_store_wtr<NS, TRROWA>(st, ra[0], ra[1], sc_a, 0);
+        else mc_store_w<NS, PLA>(st, ra[0], ra[1], sc_a, 0);
         if (BD) {}
         else if (TB == 1) kc_store_w<NS, 4, PLB>(st + OPA, rb, sc_b);
+        else if (TRB) { mc_store_wtr<NS, TRROWB>(st + OPA, rb[0], rb[1], sc_b, 0); mc_store_wtr<NS, TRROWB>(st + OPA, rb[2], rb[3], sc_b, 1); }
         else { mc_store_w<NS, PLB>(st + OPA, rb[0], rb[1], sc_b, 0); mc_store_w<NS, PLB>(st + OPA, rb[2], rb[3], sc_b, 1); }
     };
 
     // the products, smallest first (NS = 3: (a3,b1) (a2,b2) (a1,b3) (a2,b1) (a1,b2) (a1,b1); NS = 4: lo hi, hi lo, hi hi)
     constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
     constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
-    const int fro_a = hi * PLA + (wm * 64 + l31) * 16;
-    const int fro_b = OPA + hi * PLB + (wn * 128 + l31) * 16;
+    const int trk = 8 * hi + ((lane >> 2) & 3), trc = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;      // TR: this lane's k-row and column bytes of a block
+    const int fro_a = TRA ? trk * TRROWA + trc + wm * 128 : hi * PLA + (wm * 64 + l31) * 16;
+    const int fro_b = OPA + (TRB ? trk * TRROWB + trc + wn * 256 : hi * PLB + (wn * 128 + l31) * 16);
     auto stage = [&](const unsigned char* cur, unsigned char* nxt, const f32x4 (&ua)[2], const f32x4 (&ub)[4]) {
         bf16x8 fa[NP][2], fb[NP][4];
 #pragma unroll
         for (int s = 0; s < NP; ++s) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) fa[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_a + s * 2 * PLA + i * 512);
+            for (int i = 0; i < 2; ++i) {
+                if (TRA) fa[s][i] = tr_frag<TRROWA>(cur + fro_a + s * WKS * TRROWA + i * 64);
+                else fa[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_a + s * 2 * PLA + i * 512);
+            }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) fb[s][j] = *reinterpret_cast<const bf16x8*>(cur + fro_b + s * 2 * PLB + j * 512);
+            for (int j = 0; j < 4; ++j) {
+                if (TRB) fb[s][j] = tr_frag<TRROWB>(cur + fro_b + s * WKS * TRROWB + j * 64);
+                else fb[s][j] = *reinterpret_cast<const bf16x8*>(cur + fro_b + s * 2 * PLB + j * 512);
+            }
         }
         sstore(nxt, ua, ub);                                  // (after the last stage: a stage nobody reads)
 #pragma unroll
@@ -358,28 +403,29 @@ int m3t_sgemm_x6w_launch(int transA, int transB, int M, int N, int K, const floa
     dim3 grid(N / WN, M / WM, splits), block(WTH);
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return M3T_EINVAL;
-#define M3T_X6W_GO(TA_, TB_, SEG_, NS_)                                                                               \
+#define M3T_X6W_GO(TA_, TB_, SEG_, NS_, TR_)                                                                          \
     do {                                                                                                               \
-        const size_t lds = 2 * (size_t)stageb(NS_);                                                                    \
+        const size_t lds = 2 * (size_t)stageb_of(NS_, TA_, TB_, TR_);                                                  \
         static std::atomic<unsigned> attr_set{0};           /* one bit per device (was one flag per process) */           \
         if (!(attr_set.load(std::memory_order_relaxed) & (1u << dev))) {                                               \
-            hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6w_kernel<TA_, TB_, SEG_, NS_>,                    \
+            hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6w_kernel<TA_, TB_, SEG_, NS_, 0, TR_>,            \
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
             if (ea != hipSuccess) return (int)ea;                                                                      \
             attr_set.fetch_or(1u << dev, std::memory_order_relaxed);                                                   \
         }                                                                                                              \
-        sgemm_x6w_kernel<TA_, TB_, SEG_, NS_><<<grid, block, lds, s>>>(p);                                             \
+        sgemm_x6w_kernel<TA_, TB_, SEG_, NS_, 0, TR_><<<grid, block, lds, s>>>(p);                                     \
     } while (0)
-#define M3T_X6W_DISPATCH(NS_)                                                                                        \
+#define M3T_X6W_DISPATCH(NS_, TR_)                                                                                   \
     do {                                                                                                               \
-        if (seg_len > 0) M3T_X6W_GO(1, 0, true, NS_);                                                                  \
-        else if (transA == 0 && transB == 1) M3T_X6W_GO(0, 1, false, NS_);                                             \
-        else if (transA == 0 && transB == 0) M3T_X6W_GO(0, 0, false, NS_);                                             \
-        else if (transA == 1 && transB == 0) M3T_X6W_GO(1, 0, false, NS_);                                             \
-        else M3T_X6W_GO(1, 1, false, NS_);                                                                             \
+        if (seg_len > 0) M3T_X6W_GO(1, 0, true, NS_, TR_);                                                             \
+        else if (transA == 0 && transB == 1) M3T_X6W_GO(0, 1, false, NS_, false);                                      \
+        else if (transA == 0 && transB == 0) M3T_X6W_GO(0, 0, false, NS_, TR_);                                        \
+        else if (transA == 1 && transB == 0) M3T_X6W_GO(1, 0, false, NS_, TR_);                                        \
+        else M3T_X6W_GO(1, 1, false, NS_, TR_);                                                                        \
     } while (0)
-    if (bf16_operands == 3) M3T_X6W_DISPATCH(4);
-    else M3T_X6W_DISPATCH(3);
+    if (bf16_operands == 3 && m3t_gemm_tr_enabled()) M3T_X6W_DISPATCH(4, true);
+    else if (bf16_operands == 3) M3T_X6W_DISPATCH(4, false);
+    else M3T_X6W_DISPATCH(3, false);
 #undef M3T_X6W_DISPATCH
 #undef M3T_X6W_GO
     return (int)hipGetLastError();
