@@ -659,7 +659,13 @@ int m3t_cbam_bwd(const float* dy, const float* x, const float* w1, const float* 
  * Data-parallel helpers (train.py:32-41: DDP mean of gradients + clip_grad_norm_(1.0)).
  * After the RCCL all-reduce(sum) of the flat gradient buffer: one pass computes
  * sum(g^2) of g/world (partials[blocks] + final), a second scales by
- * (1/world) * min(1, max_norm/(norm+1e-6)).  norm_out[0] = total norm (pre-clip). */
+ * (1/world) * min(1, max_norm/(norm+1e-6)).  norm_out[0] = total norm (pre-clip).
+ * When that factor is exactly 1 (world 1 and nothing to clip) the buffer is not written at all.  The sum of squares is an
+ * fp32 sum (per-thread partials, a block tree, then <= 1024 block partials).  Edges: an all-zero buffer gives norm 0 and stays
+ * untouched; elements whose squares underflow (|g| < ~1e-23) do not count, so a buffer of such elements reads norm 0 and is
+ * not clipped; a NaN or inf element, or a sum of squares beyond FLT_MAX although the true norm is representable (4099
+ * elements of 1e20), gives a norm that is not finite -- the optimizer steps it guards are then skipped, and the contents of
+ * the buffer are unspecified (max_norm / inf = 0 scales it to zero). */
 int m3t_grad_norm_scale(float* flat, size_t n, float inv_world, float max_norm,
                         float* norm_out, float* ws, size_t ws_bytes, void* stream);
 /* One rank's dead scan must stop every rank: the all-reduce would otherwise spread its garbage while only the failing
@@ -674,14 +680,23 @@ int m3t_grad_dead_check(const float* dead, void* stream);
 /* ---------------------------------------------------------------------------------
  * Optimizer steps over the flat parameter / gradient buffers (reference
  * models/model.py:388-394).  torch.optim semantics: Adam(lr, betas, eps, weight_decay as L2 on the gradient,
- * bias-corrected, `step` counts from 1); SGD(momentum, weight_decay), dampening 0, no Nesterov. */
+ * bias-corrected, `step` counts from 1); SGD(momentum, weight_decay), dampening 0, no Nesterov.
+ * The hyperparameters are the fp32 values passed, and `1 - beta` is formed from them: beta2 = 0.999 arrives as
+ * 0.99900001287..., the kernel runs Adam with that value and the bias corrections are computed (in double) from the same
+ * value.  A float64 reference must round the hyperparameters to fp32 first to agree to rounding level (tests/optim_ref.py).
+ * m3t_adam_step reads and writes float4: p, g, m, v 16-byte aligned, else M3T_EINVAL; m3t_sgd_step takes any alignment.
+ * step < 1: M3T_EINVAL.  Nothing is launched on a refused call. */
 int m3t_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int step, const float* guard, void* stream);
 int m3t_sgd_step(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float weight_decay,
                  int step, const float* guard, void* stream);
 /* guard: optional device scalar (the norm m3t_grad_norm_scale returned).  When it is not finite the kernel changes
  * nothing (parameters and optimizer state keep their values): a step whose gradients came from a failed scan, or
- * overflowed, is skipped on the device. */
+ * overflowed, is skipped on the device.
+ * A skipped step still counts: the host cannot know that the device skipped without synchronising, so m3t.optim's
+ * FlatAdam / FlatSGD advance `step` on every call.  After a skipped step Adam's bias corrections are those of a larger
+ * `step` than the number of updates taken (clean, skipped, clean = the updates of step 1 and step 3); for SGD a skipped
+ * first step is harmless: with buf = 0, momentum * buf + g is the first step's buf = g. */
 
 /* ---------------------------------------------------------------------------------
  * Post-processing of prediction tracks (reference models/utils.py:20-33,
