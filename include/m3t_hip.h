@@ -852,6 +852,36 @@ size_t m3t_dense_wgrad_ws_bytes(size_t rows, int Ci, int Co);
 int m3t_dense_conv333_wgrad(const float* x, int ldx, const float* dy, int ldy, int N, int T, int H, int W, int Ci, int Co, float* dw,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Loss end of the two pre-training tasks (csrc/cls_loss.hip): VoxCeleb2_1k (models/vox2_model.py) and AudioSet
+ * (models/audioset_model.py).  Everything fp32 in memory, labels int64; B, T, C >= 1 and no alignment or divisibility
+ * requirement on C; anything else returns M3T_EINVAL.  Row sums and the loss are accumulated in fp64 in a fixed order, no
+ * atomics: the same bits run to run.
+ *
+ * Temporal pooling of per-frame logits z [B,T,C] into pooled [B,C]: mode 0 = maximum over T (audioset_model.py:34-36,
+ * `torch.max(self.audio(x), dim=1)[0]`), with arg [B,C] = the frame of the FIRST maximum and NaN above every number; mode 1 = mean
+ * over T (the `.mean(dim=1)` of the 'fc' back-end, models/backbone.py:143-145; arg unused, may be NULL).  The backward writes
+ * all of dz [B,T,C] in one pass: dpooled[b,c] at t = arg[b,c] and 0 elsewhere, or dpooled[b,c] / T at every t. */
+int m3t_tpool_fwd(const float* z, int B, int T, int C, int mode, float* pooled, int* arg, void* stream);
+int m3t_tpool_bwd(const float* dpooled, const int* arg, int B, int T, int C, int mode, float* dz, void* stream);
+/* Loss, top-1 statistic and gradient from per-clip logits [B,C], one workgroup per clip plus one small launch for the mean over clips
+ * (per-clip partials added in clip order).
+ *   kind 0: F.cross_entropy(logits, labels) with labels int64 [B] (vox2_model.py:58-67): loss = mean_b (logsumexp(x_b) - x_b[y_b]),
+ *           correct[b] = (argmax_c x_b == y_b), dlogits = (softmax - onehot) / B.  A label outside [0, C) indexes nothing: that clip's
+ *           loss term and gradient are NaN.
+ *   kind 1: F.binary_cross_entropy_with_logits(logits, targets) with targets float [B,C] (audioset_model.py:38-49): mean over all B C
+ *           elements of max(x, 0) - x y + log1p(exp(-|x|)), correct[b] = targets[b, argmax_c x_b], dlogits = (sigmoid(x) - y) / (B C).
+ * The argmax is the first maximum.  out_scalars[2] = {loss, n_correct}; correct [B] fp32; dlogits [B,C] fully written.
+ * ws: m3t_cls_loss_ws_bytes(B) bytes, 8-B aligned. */
+size_t m3t_cls_loss_ws_bytes(int B);
+int m3t_cls_loss(const float* logits, int B, int C, int kind, const void* target, float* out_scalars, float* correct,
+                 float* dlogits, void* ws, size_t ws_bytes, void* stream);
+/* The training path (vox2_model.py:61-67, audioset_model.py:41-49: forward, loss, argmax, accuracy): pooling, loss, statistics and
+ * dz [B,T,C] = dL/dz from the per-frame logits, in the same two launches.  One workgroup per clip pools its clip (pooled and, for the
+ * maximum, arg are outputs), reduces the row and writes its rows of dz: neither dL/dpooled nor a zero-filled buffer exists in memory. */
+int m3t_tpool_cls_loss(const float* z, int B, int T, int C, int mode, int kind, const void* target, float* pooled, int* arg,
+                       float* out_scalars, float* correct, float* dz, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,10 +172,15 @@ SIGNATURES = {
     "m3t_dense_conv333": [_f, _i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _s],
     "m3t_dense_wgrad_ws_bytes": [_z, _i, _i],
     "m3t_dense_conv333_wgrad": [_f, _i, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f, _z, _s],
+    "m3t_tpool_fwd": [_f, _i, _i, _i, _i, _f, _f, _s],
+    "m3t_tpool_bwd": [_f, _f, _i, _i, _i, _i, _f, _s],
+    "m3t_cls_loss_ws_bytes": [_i],
+    "m3t_cls_loss": [_f, _i, _i, _i, _f, _f, _f, _f, _f, _z, _s],
+    "m3t_tpool_cls_loss": [_f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _z, _s],
 }
 
 RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t,
-            "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t}
+            "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t, "m3t_cls_loss_ws_bytes": C.c_size_t}
 
 _lib = None
 

@@ -1902,6 +1902,169 @@ def va_loss(y_hat, valence, arousal, class_expr=None, expr_valid=None, iv=None, 
                          float(expr_w), bool(use_mse))
 
 
+# ----------------------------------------------------------------------------- pre-training tasks: temporal pooling + classification loss
+POOL_MODES = {"max": 0, "mean": 1, 0: 0, 1: 1}
+LOSS_KINDS = {"ce": 0, "bce": 1, 0: 0, 1: 1}
+
+
+def _btc(z, name):
+    if z.dim() != 3 or min(z.shape) < 1:
+        raise ValueError("%s must be [B, T, C] with B, T, C >= 1, got %s" % (name, tuple(z.shape)))
+    return z.shape
+
+
+def _cls_target(logits_shape, target, kind, device):
+    """labels int64 [B] (kind 0) or targets float32 [B, C] (kind 1) on `device`, contiguous"""
+    B, Cc = logits_shape
+    if kind == 0:
+        if target.dim() != 1 or target.shape[0] != B or target.dtype != torch.int64:
+            raise ValueError("cross-entropy labels must be int64 [B], got %s %s" % (target.dtype, tuple(target.shape)))
+    elif tuple(target.shape) != (B, Cc) or target.dtype != torch.float32:
+        raise ValueError("binary cross-entropy targets must be float32 [B, C], got %s %s" % (target.dtype, tuple(target.shape)))
+    if target.device != device:
+        raise M3THipError("the loss target must live on the logits' device")
+    return target.contiguous()
+
+
+class _TemporalPool(torch.autograd.Function):
+    """[B,T,C] -> [B,C]: max over T (reference models/audioset_model.py:36) or mean over T (the 'fc' back-end, models/backbone.py:144)."""
+
+    @staticmethod
+    def forward(ctx, z, mode):
+        z = _req(z.contiguous(), "z")
+        B, T, Cc = z.shape
+        pooled = torch.empty(B, Cc, dtype=torch.float32, device=z.device)
+        arg = torch.empty(B, Cc, dtype=torch.int32, device=z.device) if mode == 0 else None
+        with _Timed("tpool_fwd_kernel", 1, 0, nbytes=4.0 * B * Cc * (T + 2 - mode)):
+            _lib.check(lib().m3t_tpool_fwd(_p(z), B, T, Cc, mode, _p(pooled), arg.data_ptr() if arg is not None else None, _stream()),
+                       "m3t_tpool_fwd")
+        ctx.mode, ctx.dims = mode, (B, T, Cc)
+        ctx.save_for_backward(arg)
+        if arg is None:
+            arg = torch.empty(0, dtype=torch.int32, device=z.device)
+        ctx.mark_non_differentiable(arg)
+        return pooled, arg
+
+    @staticmethod
+    def backward(ctx, dpooled, _darg):
+        (arg,) = ctx.saved_tensors
+        B, T, Cc = ctx.dims
+        dpooled = _req(dpooled.contiguous(), "dpooled")
+        dz = torch.empty(B, T, Cc, dtype=torch.float32, device=dpooled.device)
+        with _Timed("tpool_bwd_kernel", 1, 0, nbytes=4.0 * B * Cc * (T + 2 - ctx.mode)):
+            _lib.check(lib().m3t_tpool_bwd(_p(dpooled), arg.data_ptr() if arg is not None else None, B, T, Cc, ctx.mode, _p(dz), _stream()),
+                       "m3t_tpool_bwd")
+        return dz, None
+
+
+def temporal_pool(z, mode, return_indices=False):
+    """Per-frame logits [B,T,C] -> per-clip logits [B,C]; mode 'max' (first maximum in time, NaN wins) or 'mean'.  Differentiable.
+    return_indices (max only): also the int32 [B,C] frame index of each maximum.  CPU tensors take the stock ops."""
+    mode = POOL_MODES[mode]
+    _btc(z, "z")
+    if not z.is_cuda:
+        if mode:
+            return z.mean(dim=1)
+        pooled, idx = z.max(dim=1)
+        return (pooled, idx.to(torch.int32)) if return_indices else pooled
+    pooled, arg = _TemporalPool.apply(z, mode)
+    return (pooled, arg) if (return_indices and mode == 0) else pooled
+
+
+def _stock_cls_loss(logits, target, kind):
+    """the reference's own composition (vox2_model.py:59,66-67 / audioset_model.py:39,46-49) with this module's return values"""
+    top = torch.argmax(logits.detach(), dim=-1)
+    if kind == 0:
+        loss = torch.nn.functional.cross_entropy(logits, target)
+        correct = (top == target).to(logits.dtype)
+    else:
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, target)
+        correct = torch.gather(target, 1, top.view(-1, 1)).view(-1)
+    return loss, torch.stack([loss.detach(), correct.sum()]), correct
+
+
+class _ClsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, kind):
+        x = _req(logits.contiguous(), "logits")
+        B, Cc = x.shape
+        stats = torch.empty(2, dtype=torch.float32, device=x.device)
+        correct = torch.empty(B, dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        part = torch.empty(2 * B, dtype=torch.float64, device=x.device)
+        # the row is read from HBM once (the second and third sweep hit the cache), the gradient written once
+        with _Timed("cls_loss_kernels", 2, 0, nbytes=4.0 * B * Cc * (2 + kind)):
+            _lib.check(lib().m3t_cls_loss(_p(x), B, Cc, kind, target.data_ptr(), _p(stats), _p(correct), _p(dx), part.data_ptr(),
+                                          part.numel() * 8, _stream()), "m3t_cls_loss")
+        ctx.save_for_backward(dx)
+        ctx.mark_non_differentiable(stats, correct)
+        return stats[0], stats, correct
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_stats, _g_correct):
+        (dx,) = ctx.saved_tensors
+        return dx * g_loss, None, None
+
+
+def cls_loss(logits, target, kind):
+    """Classification loss of the pre-training tasks on per-clip logits [B,C]: kind 'ce' = F.cross_entropy with int64 labels [B]
+    (reference models/vox2_model.py:58-67), kind 'bce' = F.binary_cross_entropy_with_logits with float targets [B,C]
+    (models/audioset_model.py:38-49).  Returns (loss, stats, correct): stats = [loss, n_correct] on the device, correct [B] the
+    per-clip top-1 hit (1/0, or the target at the top-1 class).  The gradient is written by the forward pass."""
+    kind = LOSS_KINDS[kind]
+    if logits.dim() != 2 or min(logits.shape) < 1:
+        raise ValueError("logits must be per-clip [B, C] with B, C >= 1, got %s" % (tuple(logits.shape),))
+    target = _cls_target(tuple(logits.shape), target, kind, logits.device)
+    if not logits.is_cuda:
+        return _stock_cls_loss(logits, target, kind)
+    return _ClsLoss.apply(logits, target, kind)
+
+
+class _PooledClsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, target, mode, kind):
+        z = _req(z.contiguous(), "z")
+        B, T, Cc = z.shape
+        dev = z.device
+        stats = torch.empty(2, dtype=torch.float32, device=dev)
+        correct = torch.empty(B, dtype=torch.float32, device=dev)
+        pooled = torch.empty(B, Cc, dtype=torch.float32, device=dev)
+        arg = torch.empty((B, Cc) if mode == 0 else (0,), dtype=torch.int32, device=dev)
+        dz = torch.empty_like(z)
+        part = torch.empty(2 * B, dtype=torch.float64, device=dev)
+        # z read once, dz written once; pooled (and arg) written and re-read by the thread that wrote them
+        with _Timed("tpool_cls_loss_kernels", 2, 0, nbytes=4.0 * B * Cc * (2 * T + 2 + kind)):
+            _lib.check(lib().m3t_tpool_cls_loss(_p(z), B, T, Cc, mode, kind, target.data_ptr(), _p(pooled),
+                                                arg.data_ptr() if mode == 0 else None, _p(stats), _p(correct), _p(dz),
+                                                part.data_ptr(), part.numel() * 8, _stream()), "m3t_tpool_cls_loss")
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(stats, correct, pooled, arg)
+        return stats[0], stats, correct, pooled, arg
+
+    @staticmethod
+    def backward(ctx, g_loss, *_):
+        (dz,) = ctx.saved_tensors
+        return dz * g_loss, None, None, None
+
+
+def pooled_cls_loss(z, target, mode, kind, return_pooled=False):
+    """The training path of the pre-training tasks: temporal_pool(z, mode) followed by cls_loss(., target, kind) as one operator on the
+    per-frame logits z [B,T,C] -- pooled logits, loss, statistics and dL/dz in two launches (m3t_tpool_cls_loss).  Returns
+    (loss, stats, correct), with return_pooled also (pooled [B,C], arg int32 [B,C] of the maxima; empty for the mean), detached."""
+    mode, kind = POOL_MODES[mode], LOSS_KINDS[kind]
+    B, T, Cc = _btc(z, "z")
+    target = _cls_target((B, Cc), target, kind, z.device)
+    if not z.is_cuda:
+        if mode:
+            pooled, arg = z.mean(dim=1), torch.empty(0, dtype=torch.int32)
+        else:
+            pooled, arg = z.max(dim=1)
+        out = _stock_cls_loss(pooled, target, kind)
+        return out + (pooled.detach(), arg.to(torch.int32)) if return_pooled else out
+    out = _PooledClsLoss.apply(z, target, mode, kind)
+    return out if return_pooled else out[:3]
+
+
 # ----------------------------------------------------------------------------- TCN
 class _BctToBtc(torch.autograd.Function):
     @staticmethod

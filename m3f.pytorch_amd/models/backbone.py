@@ -183,6 +183,22 @@ class VA_3DVGGM(nn.Module):
             return ops.linear(h, self.fc[2].weight, self.fc[2].bias, 0).mean(dim=1)
         return feats
 
+    def frame_logits(self, feats):
+        """the 'fc' back-end WITHOUT its temporal mean: feats [B,512,T] -> per-frame logits [B,T,nClasses] (backbone.py:143-144 up to
+        `.mean(dim=1)`).  The pre-training step pools them inside its loss operator (m3t.ops.pooled_cls_loss); a CPU input takes the
+        stock ops."""
+        if self.backend != 'fc':
+            raise ValueError("frame_logits: the 'fc' back-end only (backend is '%s')" % self.backend)
+        if not feats.is_cuda:
+            return self.fc(feats.transpose(1, 2))
+        h = ops.linear(ops.bct_to_btc(feats), self.fc[0].weight, self.fc[0].bias, 1)
+        return ops.linear(h, self.fc[2].weight, self.fc[2].bias, 0)
+
+    def forward_frames(self, x):
+        """forward() up to the per-frame logits (see frame_logits)"""
+        with ops.batch_counters():
+            return self.frame_logits(_squeeze_hw(self.v2p(x)))
+
     def forward(self, x):
         with ops.batch_counters():          # (every BatchNorm's num_batches_tracked in one launch)
             return self.temporal(_squeeze_hw(self.v2p(x)))
