@@ -437,23 +437,36 @@ int m3t_att_fuse_bwd(const float* df, const float* s_v, const float* s_a,
  * gradient in one pass over y_hat [rows, C]:
  *   L = w_v * (1 - ccc(y[:,iv], valence)) + w_a * (1 - ccc(y[:,ia], arousal))
  *       + expr_w * mean_rows( CE(y[:, :n_expr], class_expr) * expr_valid )     (n_expr>0)
- * (training_step uses w_v = loss_lambda, w_a = 1 - loss_lambda, expr_w = 0.8; a zero weight
- * skips its term entirely)
+ * (training_step uses w_v = loss_lambda, w_a = 1 - loss_lambda, expr_w = 0.8).
+ * A zero weight skips its term entirely: w_v == 0 (w_a == 0) leaves loss_v (loss_a) at 0 and column iv (ia) of dy
+ * untouched by that term, whatever the column holds -- NaN included; expr_w == 0 adds neither the CE term nor its
+ * gradient.  The statistics of a skipped term are still reported (ccc_v / ccc_a, loss_expr, n_valid, n_correct) and
+ * may then be NaN.
  * ccc per models/utils.py:6-17 (unbiased variance, biased covariance).  With
  * use_mse!=0 the two ccc terms become mean squared errors (models/model.py:143-144).
- * The CE term is dropped when no row is valid (model.py:173-174) -- decided on device.
+ * rows == 1: the variances divide by max(rows - 1, 1), so they and the covariance are 0 and ccc = 0 / (y - t)^2:
+ * loss_v = 1 and dL/dy = 0 for y != t, NaN for y == t (torch's unbiased variance of one element is NaN: the reference
+ * gives NaN for every one-row batch).  The mse form and the CE term are unaffected.
+ * The CE term is dropped when no row is valid (model.py:173-174) -- decided on device; it is the mean over ALL rows
+ * of the valid rows' cross entropies.  class_expr is read on valid rows only: an invalid row may carry any marker
+ * (-1, 255).  n_correct counts the valid rows whose FIRST maximum is the label.
  * out_scalars[8] = {loss, loss_v, loss_a, loss_expr, n_valid, n_correct, ccc_v, ccc_a};
- * dy [rows, C] receives dL/dy_hat (fully written).  class_expr int64, expr_valid uint8. */
+ * dy [rows, C] receives dL/dy_hat (fully written: exactly 0 in every column that belongs to no term).
+ * class_expr int64, expr_valid uint8.
+ * Precision: every sum over rows, the closed form and each row's regression gradient are evaluated in fp64 and
+ * rounded to fp32 once; the per-row cross entropy and its gradient are fp32.  All three forms below are held to
+ * 4 x max(fp32 torch's error, 1 ulp) of float64 (tests/test_gpu_fuse_loss.py). */
 int m3t_va_loss(const float* y_hat, int rows, int C, int iv, int ia,
                 const float* valence, const float* arousal,
                 const int64_t* class_expr, const uint8_t* expr_valid, int n_expr,
                 float w_v, float w_a, float expr_w, int use_mse,
                 float* out_scalars, float* dy, float* ws, size_t ws_bytes, void* stream);
-/* ws: 32 floats per 256 rows (m3t_va_loss_ws_bytes), 8-B aligned.  With it, 1024 < rows <= 32768 run as ONE grid-wide launch (round 6): raw
- * moments in fp64 in one sweep, the blocks meet once inside the kernel (agent-scope release + ticket, bounded wait: a wait that expires gives
- * loss = NaN), every block sums all partials in block order (deterministic) and writes its rows of dL/dy; M3T_VA_LOSS_FUSED=0 or more
- * rows: three short launches (sums -> centred moments -> closed form + gradient); without ws, or for rows <= 1024, one workgroup does all
- * passes. */
+/* ws: 32 floats (16 doubles) per 256 rows = m3t_va_loss_ws_bytes(rows), 8-B aligned.  With it, 1024 < rows <= 32768 run as ONE grid-wide
+ * launch (round 6): raw moments in fp64 in one sweep, the blocks meet once inside the kernel (agent-scope release + ticket, bounded wait: a
+ * wait that expires gives loss = NaN), every block sums all partials in block order (deterministic) and writes its rows of dL/dy;
+ * M3T_VA_LOSS_FUSED=0 or more rows: three short launches (sums -> centred moments -> closed form + gradient, fp64 partials per block);
+ * without ws (or with one too small or misaligned), or for rows <= 1024, one workgroup does all passes.  Calls that use the one-launch form
+ * share two ticket words per device: they must not run concurrently on two streams. */
 size_t m3t_va_loss_ws_bytes(int rows);
 
 /* Round 6: channels-last operators of the 3-D VGG-M stems (csrc/stem_cl.hip; reference models/backbone.py:73-103,179-271: Conv3d -> BatchNorm3d ->

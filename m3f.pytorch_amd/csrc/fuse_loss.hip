@@ -19,6 +19,10 @@ __device__ __forceinline__ void fuse_weights(float sv, float sa, float& hv, floa
     w1 = ea * inv;
 }
 
+// w0 v + w1 a with the contraction spelled out: left to the compiler, the float4 loop and the scalar loop fused different products
+// (the same inputs gave f one ulp apart depending on the operands' alignment)
+__device__ __forceinline__ float mix2(float w0, float v, float w1, float a) { return fmaf(w0, v, w1 * a); }
+
 __global__ __launch_bounds__(256) void att_fuse_fwd_kernel(const float* __restrict__ s_v, const float* __restrict__ s_a,
                                                            const float* __restrict__ x_v, const float* __restrict__ x_a,
                                                            float* __restrict__ f, int rows, int D, int vec) {
@@ -34,10 +38,10 @@ __global__ __launch_bounds__(256) void att_fuse_fwd_kernel(const float* __restri
         float4* pf = reinterpret_cast<float4*>(f + base);
         for (int i = lane; i < (D >> 2); i += 64) {
             const float4 v = pv[i], a = pa[i];
-            pf[i] = make_float4(w0 * v.x + w1 * a.x, w0 * v.y + w1 * a.y, w0 * v.z + w1 * a.z, w0 * v.w + w1 * a.w);
+            pf[i] = make_float4(mix2(w0, v.x, w1, a.x), mix2(w0, v.y, w1, a.y), mix2(w0, v.z, w1, a.z), mix2(w0, v.w, w1, a.w));
         }
     } else {
-        for (int i = lane; i < D; i += 64) f[base + i] = w0 * x_v[base + i] + w1 * x_a[base + i];
+        for (int i = lane; i < D; i += 64) f[base + i] = mix2(w0, x_v[base + i], w1, x_a[base + i]);
     }
 }
 
@@ -85,111 +89,158 @@ __global__ __launch_bounds__(256) void att_fuse_bwd_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------ VA loss
-struct CccStats { float mx, mt, cov, vx, vt, den, ccc; };
+// Arithmetic shared by the three forms below (one workgroup / one grid-wide launch / three launches): every sum over rows is
+// accumulated in fp64, the closed form and each row's gradient are evaluated in fp64 and rounded to fp32 ONCE; only the
+// per-row cross entropy (expf / logf) and its gradient are fp32.  The forms differ in how the workgroups meet and in the
+// moments they gather (centred in two passes, or raw in one), not in precision: tests/test_gpu_fuse_loss.py holds each of them
+// to the same bound against float64.  (fp32 sums -- strided per thread in one workgroup, 129 block partials in block order over three
+// launches -- and an fp32 closed form measured 3 - 20 x that bound's unit at 33 000 rows: NOTEBOOK R10.)
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// block_sum of common.h in fp64; `red` >= 16 doubles of LDS
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    v = wave_sum_d(v);
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    for (int i = 0; i < nw; ++i) r += red[i];
+    return r;
+}
+
+// one ccc term: d ccc / dx = c1 (t - mt) - c2 (x - mx) - c3
+struct VaTerm { double mx, mt, ccc, mse, c1, c2, c3; };
+
+// cov: BIASED covariance, vx + vt: the two UNBIASED variances (divisor max(n - 1, 1): one row gives var = cov = 0, ccc = 0 / (mx - mt)^2)
+__device__ __forceinline__ VaTerm va_term(double mx, double mt, double cov, double vsum, double mse, double invn, double nm1) {
+    VaTerm s;
+    const double den = vsum + (mx - mt) * (mx - mt);
+    const double q = 2.0 * cov / (den * den);
+    s.mx = mx; s.mt = mt; s.mse = mse;
+    s.ccc = 2.0 * cov / den;
+    s.c1 = 2.0 * invn / den;
+    s.c2 = q * 2.0 * nm1;
+    s.c3 = q * 2.0 * (mx - mt) * invn;
+    return s;
+}
+
+__device__ __forceinline__ float va_term_grad(const VaTerm& s, float x, float t, float w, int use_mse, double invn) {
+    const double g = use_mse ? 2.0 * ((double)x - (double)t) * invn
+                             : -(s.c1 * ((double)t - s.mt) - s.c2 * ((double)x - s.mx) - s.c3);
+    return (float)((double)w * g);
+}
+
+// cross entropy of one row over its first n_expr logits; *first_max: the index of the first maximum
+__device__ __forceinline__ double va_ce_row(const float* __restrict__ l, int n_expr, int lab, int* first_max) {
+    float m = l[0];
+    int am = 0;
+    for (int k = 1; k < n_expr; ++k)
+        if (l[k] > m) { m = l[k]; am = k; }
+    float se = 0.f;
+    for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
+    *first_max = am;
+    return (double)logf(se) + ((double)m - (double)l[lab]);          // (not m + logf(se) - l[lab] in fp32: that rounds at the magnitude of the logits)
+}
+
+// one row of dL/dy: zero, the masked CE gradient on the first n_expr columns, the two regression terms (a zero weight leaves its
+// column alone, whatever the column holds)
+__device__ __forceinline__ void va_row_grad(const float* __restrict__ l, float* __restrict__ g, int C, int iv, int ia, float b, float e,
+                                            bool ce_row, int lab, int n_expr, float wv, float wa, double sc, int use_mse,
+                                            const VaTerm& sv, const VaTerm& sa, double invn) {
+    for (int k = 0; k < C; ++k) g[k] = 0.f;
+    if (ce_row) {
+        float m = l[0];
+        for (int k = 1; k < n_expr; ++k) m = fmaxf(m, l[k]);
+        float se = 0.f;
+        for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
+        const double r = sc / (double)se;               // expf and its sum are fp32; the quotient, the label's - 1 and the scale are not rounded apart
+        for (int k = 0; k < n_expr; ++k) g[k] = (float)((double)expf(l[k] - m) * r - (k == lab ? sc : 0.0));
+    }
+    if (wv != 0.f) g[iv] += va_term_grad(sv, l[iv], b, wv, use_mse, invn);
+    if (wa != 0.f) g[ia] += va_term_grad(sa, l[ia], e, wa, use_mse, invn);
+}
+
+// the eight scalars; ce: sum of the valid rows' cross entropies.  A zero weight skips its term entirely (its statistics may be NaN).
+__device__ __forceinline__ void va_write_out(float* __restrict__ out, const VaTerm& sv, const VaTerm& sa, double ce, double nvalid,
+                                             double ncorrect, bool use_e, float wv, float wa, float expr_w, int use_mse, double invn,
+                                             bool gave_up) {
+    const double lv = wv == 0.f ? 0.0 : (use_mse ? sv.mse : 1.0 - sv.ccc);
+    const double la = wa == 0.f ? 0.0 : (use_mse ? sa.mse : 1.0 - sa.ccc);
+    const double le = ce * invn;
+    out[0] = gave_up ? __builtin_nanf("") : (float)((double)wv * lv + (double)wa * la + (use_e ? (double)expr_w * le : 0.0));
+    out[1] = (float)lv; out[2] = (float)la; out[3] = (float)le; out[4] = (float)nvalid; out[5] = (float)ncorrect;
+    out[6] = (float)sv.ccc; out[7] = (float)sa.ccc;
+}
 
 __global__ __launch_bounds__(1024) void va_loss_kernel(const float* __restrict__ y, int rows, int C, int iv, int ia,
                                                        const float* __restrict__ val, const float* __restrict__ aro,
                                                        const int64_t* __restrict__ cls, const uint8_t* __restrict__ valid,
                                                        int n_expr, float wv, float wa, float expr_w, int use_mse,
                                                        float* __restrict__ out, float* __restrict__ dy) {
-    __shared__ float red[16];
+    __shared__ double red[16];
     const int tid = threadIdx.x, nt = blockDim.x;
-    const float invn = 1.f / (float)rows;
+    const double invn = 1.0 / (double)rows, nm1 = 1.0 / (double)(rows > 1 ? rows - 1 : 1);
     // pass 1: means
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int i = tid; i < rows; i += nt) {
         s0 += y[(size_t)i * C + iv]; s1 += val[i];
         s2 += y[(size_t)i * C + ia]; s3 += aro[i];
     }
-    const float mxv = block_sum(s0, red) * invn, mtv = block_sum(s1, red) * invn;
-    const float mxa = block_sum(s2, red) * invn, mta = block_sum(s3, red) * invn;
-    // pass 2: centred second moments (or squared errors)
-    float cv = 0.f, xv = 0.f, tv = 0.f, ca = 0.f, xa = 0.f, ta = 0.f, ev = 0.f, ea = 0.f;
+    const double mxv = block_sum_d(s0, red) * invn, mtv = block_sum_d(s1, red) * invn;
+    const double mxa = block_sum_d(s2, red) * invn, mta = block_sum_d(s3, red) * invn;
+    // pass 2: centred second moments and squared errors
+    double cv = 0.0, xv = 0.0, tv = 0.0, ca = 0.0, xa = 0.0, ta = 0.0, ev = 0.0, ea = 0.0;
     for (int i = tid; i < rows; i += nt) {
-        const float a = y[(size_t)i * C + iv], b = val[i];
-        const float c = y[(size_t)i * C + ia], e = aro[i];
+        const double a = y[(size_t)i * C + iv], b = val[i];
+        const double c = y[(size_t)i * C + ia], e = aro[i];
         cv += (a - mxv) * (b - mtv); xv += (a - mxv) * (a - mxv); tv += (b - mtv) * (b - mtv);
         ca += (c - mxa) * (e - mta); xa += (c - mxa) * (c - mxa); ta += (e - mta) * (e - mta);
         ev += (a - b) * (a - b); ea += (c - e) * (c - e);
     }
-    cv = block_sum(cv, red); xv = block_sum(xv, red); tv = block_sum(tv, red);
-    ca = block_sum(ca, red); xa = block_sum(xa, red); ta = block_sum(ta, red);
-    ev = block_sum(ev, red); ea = block_sum(ea, red);
-    const float nm1 = 1.f / (float)(rows > 1 ? rows - 1 : 1);
-    const float covv = cv * invn, covA = ca * invn;
-    const float denv = xv * nm1 + tv * nm1 + (mxv - mtv) * (mxv - mtv);
-    const float dena = xa * nm1 + ta * nm1 + (mxa - mta) * (mxa - mta);
-    const float cccv = 2.f * covv / denv, ccca = 2.f * covA / dena;
+    cv = block_sum_d(cv, red); xv = block_sum_d(xv, red); tv = block_sum_d(tv, red);
+    ca = block_sum_d(ca, red); xa = block_sum_d(xa, red); ta = block_sum_d(ta, red);
+    ev = block_sum_d(ev, red); ea = block_sum_d(ea, red);
+    const VaTerm sv = va_term(mxv, mtv, cv * invn, xv * nm1 + tv * nm1, ev * invn, invn, nm1);
+    const VaTerm sa = va_term(mxa, mta, ca * invn, xa * nm1 + ta * nm1, ea * invn, invn, nm1);
     // pass 3: masked cross entropy on the first n_expr logits
-    float ce = 0.f, nvalid = 0.f, ncorrect = 0.f;
+    double ce = 0.0, nvalid = 0.0, ncorrect = 0.0;
     if (n_expr > 0) {
         for (int i = tid; i < rows; i += nt) {
             if (!valid[i]) continue;
-            const float* l = y + (size_t)i * C;
-            float m = l[0];
-            int am = 0;
-            for (int k = 1; k < n_expr; ++k)
-                if (l[k] > m) { m = l[k]; am = k; }
-            float se = 0.f;
-            for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
             const int lab = (int)cls[i];
-            ce += m + logf(se) - l[lab];
-            nvalid += 1.f;
-            ncorrect += (am == lab) ? 1.f : 0.f;
+            int am;
+            ce += va_ce_row(y + (size_t)i * C, n_expr, lab, &am);
+            nvalid += 1.0;
+            ncorrect += (am == lab) ? 1.0 : 0.0;
         }
-        ce = block_sum(ce, red); nvalid = block_sum(nvalid, red); ncorrect = block_sum(ncorrect, red);
+        ce = block_sum_d(ce, red); nvalid = block_sum_d(nvalid, red); ncorrect = block_sum_d(ncorrect, red);
     }
-    const float loss_e = ce * invn;
-    const bool use_e = n_expr > 0 && nvalid > 0.f;
-    const float lv = wv == 0.f ? 0.f : (use_mse ? ev * invn : 1.f - cccv);
-    const float la = wa == 0.f ? 0.f : (use_mse ? ea * invn : 1.f - ccca);
-    if (tid == 0) {
-        out[0] = wv * lv + wa * la + (use_e ? expr_w * loss_e : 0.f);
-        out[1] = lv; out[2] = la; out[3] = loss_e; out[4] = nvalid; out[5] = ncorrect; out[6] = cccv; out[7] = ccca;
-    }
+    const bool use_e = n_expr > 0 && nvalid > 0.0 && expr_w != 0.f;
+    if (tid == 0) va_write_out(out, sv, sa, ce, nvalid, ncorrect, use_e, wv, wa, expr_w, use_mse, invn, false);
     // gradient
+    const double sc = (double)expr_w * invn;
     for (int i = tid; i < rows; i += nt) {
-        float* g = dy + (size_t)i * C;
-        const float* l = y + (size_t)i * C;
-        for (int k = 0; k < C; ++k) g[k] = 0.f;
-        if (use_e && valid[i]) {
-            float m = l[0];
-            for (int k = 1; k < n_expr; ++k) m = fmaxf(m, l[k]);
-            float se = 0.f;
-            for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
-            const float sc = expr_w * invn;
-            const int lab = (int)cls[i];
-            for (int k = 0; k < n_expr; ++k) g[k] = sc * (expf(l[k] - m) / se - (k == lab ? 1.f : 0.f));
-        }
-        const float a = l[iv], b = val[i], c = l[ia], e = aro[i];
-        float gv, ga;
-        if (use_mse) {
-            gv = 2.f * (a - b) * invn;
-            ga = 2.f * (c - e) * invn;
-        } else {
-            const float dcv = 2.f * (b - mtv) * invn / denv -
-                              (2.f * covv / (denv * denv)) * (2.f * (a - mxv) * nm1 + 2.f * (mxv - mtv) * invn);
-            const float dca = 2.f * (e - mta) * invn / dena -
-                              (2.f * covA / (dena * dena)) * (2.f * (c - mxa) * nm1 + 2.f * (mxa - mta) * invn);
-            gv = -dcv;
-            ga = -dca;
-        }
-        if (wv != 0.f) g[iv] += wv * gv;
-        if (wa != 0.f) g[ia] += wa * ga;
+        const bool ce_row = use_e && valid[i];
+        va_row_grad(y + (size_t)i * C, dy + (size_t)i * C, C, iv, ia, val[i], aro[i], ce_row, ce_row ? (int)cls[i] : 0, n_expr, wv, wa,
+                    sc, use_mse, sv, sa, invn);
     }
 }
 
 // The same loss as three short grid-wide launches for B*T in the thousands (one workgroup took 141 us on 9600 rows,
-// un-overlappable between forward and backward).  256 rows per block, one row per thread; per-block partial sums go to
+// un-overlappable between forward and backward).  256 rows per block, one row per thread; per-block partial sums (fp64) go to
 // ws and are reduced in a fixed order by EVERY block of the next launch (deterministic, no atomics).
 //   part A [nb][8]: sum y_v, sum val, sum y_a, sum aro, CE sum, n_valid, n_correct, -
 //   part B [nb][8]: centred co-moments cv xv tv ca xa ta and squared errors ev ea
 constexpr int LB = 256;
 
-__device__ __forceinline__ void reduce_parts(const float* __restrict__ part, int nb, float* tot /* LDS [8] */) {
+__device__ __forceinline__ void reduce_parts(const double* __restrict__ part, int nb, double* tot /* LDS [8] */) {
     // threads 0..7 each add one column over the blocks in block order
     if (threadIdx.x < 8) {
-        float s = 0.f;
+        double s = 0.0;
         for (int b = 0; b < nb; ++b) s += part[(size_t)b * 8 + threadIdx.x];
         tot[threadIdx.x] = s;
     }
@@ -199,56 +250,51 @@ __device__ __forceinline__ void reduce_parts(const float* __restrict__ part, int
 __global__ __launch_bounds__(LB) void va_loss_sums_kernel(const float* __restrict__ y, int rows, int C, int iv, int ia,
                                                           const float* __restrict__ val, const float* __restrict__ aro,
                                                           const int64_t* __restrict__ cls, const uint8_t* __restrict__ valid,
-                                                          int n_expr, float* __restrict__ partA) {
-    __shared__ float red[16];
+                                                          int n_expr, double* __restrict__ partA) {
+    __shared__ double red[16];
     const int i = blockIdx.x * LB + threadIdx.x;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, ce = 0.f, nvalid = 0.f, ncorrect = 0.f;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, ce = 0.0, nvalid = 0.0, ncorrect = 0.0;
     if (i < rows) {
         const float* l = y + (size_t)i * C;
         s0 = l[iv]; s1 = val[i]; s2 = l[ia]; s3 = aro[i];
         if (n_expr > 0 && valid[i]) {
-            float m = l[0];
-            int am = 0;
-            for (int k = 1; k < n_expr; ++k)
-                if (l[k] > m) { m = l[k]; am = k; }
-            float se = 0.f;
-            for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
             const int lab = (int)cls[i];
-            ce = m + logf(se) - l[lab];
-            nvalid = 1.f;
-            ncorrect = (am == lab) ? 1.f : 0.f;
+            int am;
+            ce = va_ce_row(l, n_expr, lab, &am);
+            nvalid = 1.0;
+            ncorrect = (am == lab) ? 1.0 : 0.0;
         }
     }
-    s0 = block_sum(s0, red); s1 = block_sum(s1, red); s2 = block_sum(s2, red); s3 = block_sum(s3, red);
-    ce = block_sum(ce, red); nvalid = block_sum(nvalid, red); ncorrect = block_sum(ncorrect, red);
+    s0 = block_sum_d(s0, red); s1 = block_sum_d(s1, red); s2 = block_sum_d(s2, red); s3 = block_sum_d(s3, red);
+    ce = block_sum_d(ce, red); nvalid = block_sum_d(nvalid, red); ncorrect = block_sum_d(ncorrect, red);
     if (threadIdx.x == 0) {
-        float* q = partA + (size_t)blockIdx.x * 8;
-        q[0] = s0; q[1] = s1; q[2] = s2; q[3] = s3; q[4] = ce; q[5] = nvalid; q[6] = ncorrect; q[7] = 0.f;
+        double* q = partA + (size_t)blockIdx.x * 8;
+        q[0] = s0; q[1] = s1; q[2] = s2; q[3] = s3; q[4] = ce; q[5] = nvalid; q[6] = ncorrect; q[7] = 0.0;
     }
 }
 
 __global__ __launch_bounds__(LB) void va_loss_moments_kernel(const float* __restrict__ y, int rows, int C, int iv, int ia,
                                                              const float* __restrict__ val, const float* __restrict__ aro,
-                                                             const float* __restrict__ partA, float* __restrict__ partB) {
-    __shared__ float red[16];
-    __shared__ float tot[8];
+                                                             const double* __restrict__ partA, double* __restrict__ partB) {
+    __shared__ double red[16];
+    __shared__ double tot[8];
     reduce_parts(partA, gridDim.x, tot);
-    const float invn = 1.f / (float)rows;
-    const float mxv = tot[0] * invn, mtv = tot[1] * invn, mxa = tot[2] * invn, mta = tot[3] * invn;
+    const double invn = 1.0 / (double)rows;
+    const double mxv = tot[0] * invn, mtv = tot[1] * invn, mxa = tot[2] * invn, mta = tot[3] * invn;
     const int i = blockIdx.x * LB + threadIdx.x;
-    float cv = 0.f, xv = 0.f, tv = 0.f, ca = 0.f, xa = 0.f, ta = 0.f, ev = 0.f, ea = 0.f;
+    double cv = 0.0, xv = 0.0, tv = 0.0, ca = 0.0, xa = 0.0, ta = 0.0, ev = 0.0, ea = 0.0;
     if (i < rows) {
-        const float a = y[(size_t)i * C + iv], b = val[i];
-        const float c = y[(size_t)i * C + ia], e = aro[i];
+        const double a = y[(size_t)i * C + iv], b = val[i];
+        const double c = y[(size_t)i * C + ia], e = aro[i];
         cv = (a - mxv) * (b - mtv); xv = (a - mxv) * (a - mxv); tv = (b - mtv) * (b - mtv);
         ca = (c - mxa) * (e - mta); xa = (c - mxa) * (c - mxa); ta = (e - mta) * (e - mta);
         ev = (a - b) * (a - b); ea = (c - e) * (c - e);
     }
-    cv = block_sum(cv, red); xv = block_sum(xv, red); tv = block_sum(tv, red);
-    ca = block_sum(ca, red); xa = block_sum(xa, red); ta = block_sum(ta, red);
-    ev = block_sum(ev, red); ea = block_sum(ea, red);
+    cv = block_sum_d(cv, red); xv = block_sum_d(xv, red); tv = block_sum_d(tv, red);
+    ca = block_sum_d(ca, red); xa = block_sum_d(xa, red); ta = block_sum_d(ta, red);
+    ev = block_sum_d(ev, red); ea = block_sum_d(ea, red);
     if (threadIdx.x == 0) {
-        float* q = partB + (size_t)blockIdx.x * 8;
+        double* q = partB + (size_t)blockIdx.x * 8;
         q[0] = cv; q[1] = xv; q[2] = tv; q[3] = ca; q[4] = xa; q[5] = ta; q[6] = ev; q[7] = ea;
     }
 }
@@ -257,55 +303,22 @@ __global__ __launch_bounds__(LB) void va_loss_grad_kernel(const float* __restric
                                                           const float* __restrict__ val, const float* __restrict__ aro,
                                                           const int64_t* __restrict__ cls, const uint8_t* __restrict__ valid,
                                                           int n_expr, float wv, float wa, float expr_w, int use_mse,
-                                                          const float* __restrict__ partA, const float* __restrict__ partB,
+                                                          const double* __restrict__ partA, const double* __restrict__ partB,
                                                           float* __restrict__ out, float* __restrict__ dy) {
-    __shared__ float ta_[8], tb_[8];
+    __shared__ double ta_[8], tb_[8];
     reduce_parts(partA, gridDim.x, ta_);
     reduce_parts(partB, gridDim.x, tb_);
-    const float invn = 1.f / (float)rows;
-    const float mxv = ta_[0] * invn, mtv = ta_[1] * invn, mxa = ta_[2] * invn, mta = ta_[3] * invn;
-    const float nm1 = 1.f / (float)(rows > 1 ? rows - 1 : 1);
-    const float covv = tb_[0] * invn, covA = tb_[3] * invn;
-    const float denv = tb_[1] * nm1 + tb_[2] * nm1 + (mxv - mtv) * (mxv - mtv);
-    const float dena = tb_[4] * nm1 + tb_[5] * nm1 + (mxa - mta) * (mxa - mta);
-    const float cccv = 2.f * covv / denv, ccca = 2.f * covA / dena;
-    const float loss_e = ta_[4] * invn, nvalid = ta_[5];
-    const bool use_e = n_expr > 0 && nvalid > 0.f;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const float lv = wv == 0.f ? 0.f : (use_mse ? tb_[6] * invn : 1.f - cccv);
-        const float la = wa == 0.f ? 0.f : (use_mse ? tb_[7] * invn : 1.f - ccca);
-        out[0] = wv * lv + wa * la + (use_e ? expr_w * loss_e : 0.f);
-        out[1] = lv; out[2] = la; out[3] = loss_e; out[4] = nvalid; out[5] = ta_[6]; out[6] = cccv; out[7] = ccca;
-    }
+    const double invn = 1.0 / (double)rows, nm1 = 1.0 / (double)(rows > 1 ? rows - 1 : 1);
+    const VaTerm sv = va_term(ta_[0] * invn, ta_[1] * invn, tb_[0] * invn, tb_[1] * nm1 + tb_[2] * nm1, tb_[6] * invn, invn, nm1);
+    const VaTerm sa = va_term(ta_[2] * invn, ta_[3] * invn, tb_[3] * invn, tb_[4] * nm1 + tb_[5] * nm1, tb_[7] * invn, invn, nm1);
+    const bool use_e = n_expr > 0 && ta_[5] > 0.0 && expr_w != 0.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        va_write_out(out, sv, sa, ta_[4], ta_[5], ta_[6], use_e, wv, wa, expr_w, use_mse, invn, false);
     const int i = blockIdx.x * LB + threadIdx.x;
     if (i >= rows) return;
-    float* g = dy + (size_t)i * C;
-    const float* l = y + (size_t)i * C;
-    for (int k = 0; k < C; ++k) g[k] = 0.f;
-    if (use_e && valid[i]) {
-        float m = l[0];
-        for (int k = 1; k < n_expr; ++k) m = fmaxf(m, l[k]);
-        float se = 0.f;
-        for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
-        const float sc = expr_w * invn;
-        const int lab = (int)cls[i];
-        for (int k = 0; k < n_expr; ++k) g[k] = sc * (expf(l[k] - m) / se - (k == lab ? 1.f : 0.f));
-    }
-    const float a = l[iv], b = val[i], c = l[ia], e = aro[i];
-    float gv, ga;
-    if (use_mse) {
-        gv = 2.f * (a - b) * invn;
-        ga = 2.f * (c - e) * invn;
-    } else {
-        const float dcv = 2.f * (b - mtv) * invn / denv -
-                          (2.f * covv / (denv * denv)) * (2.f * (a - mxv) * nm1 + 2.f * (mxv - mtv) * invn);
-        const float dca = 2.f * (e - mta) * invn / dena -
-                          (2.f * covA / (dena * dena)) * (2.f * (c - mxa) * nm1 + 2.f * (mxa - mta) * invn);
-        gv = -dcv;
-        ga = -dca;
-    }
-    if (wv != 0.f) g[iv] += wv * gv;
-    if (wa != 0.f) g[ia] += wa * ga;
+    const bool ce_row = use_e && valid[i];
+    va_row_grad(y + (size_t)i * C, dy + (size_t)i * C, C, iv, ia, val[i], aro[i], ce_row, ce_row ? (int)cls[i] : 0, n_expr, wv, wa,
+                (double)expr_w * invn, use_mse, sv, sa, invn);
 }
 
 // Round 6: the same loss as ONE launch (three launches for 1.9 MB are three launch latencies on the chain between forward
@@ -330,29 +343,24 @@ __global__ __launch_bounds__(LB) void va_loss_fused_kernel(const float* __restri
     double v[VP];
 #pragma unroll
     for (int k = 0; k < VP; ++k) v[k] = 0.0;
-    float a = 0.f, b = 0.f, c = 0.f, e = 0.f;
+    float b = 0.f, e = 0.f;
     if (i < rows) {
         const float* l = y + (size_t)i * C;
-        a = l[iv]; b = val[i]; c = l[ia]; e = aro[i];
+        const float a = l[iv], c = l[ia];
+        b = val[i]; e = aro[i];
         v[0] = a; v[1] = b; v[2] = (double)a * a; v[3] = (double)b * b; v[4] = (double)a * b; v[5] = ((double)a - b) * ((double)a - b);
         v[6] = c; v[7] = e; v[8] = (double)c * c; v[9] = (double)e * e; v[10] = (double)c * e; v[11] = ((double)c - e) * ((double)c - e);
         if (n_expr > 0 && valid[i]) {
-            float m = l[0];
-            int am = 0;
-            for (int k = 1; k < n_expr; ++k)
-                if (l[k] > m) { m = l[k]; am = k; }
-            float se = 0.f;
-            for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
             const int lab = (int)cls[i];
-            v[12] = m + logf(se) - l[lab];
+            int am;
+            v[12] = va_ce_row(l, n_expr, lab, &am);
             v[13] = 1.0;
             v[14] = (am == lab) ? 1.0 : 0.0;
         }
     }
 #pragma unroll
     for (int k = 0; k < 15; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+        v[k] = wave_sum_d(v[k]);
         if (lane == 0) wred[wave][k] = v[k];
     }
     __syncthreads();
@@ -387,51 +395,19 @@ __global__ __launch_bounds__(LB) void va_loss_fused_kernel(const float* __restri
         tot[threadIdx.x] = s;
     }
     __syncthreads();
-    const double n = (double)rows, invn_d = 1.0 / n, nm1_d = 1.0 / (double)(rows > 1 ? rows - 1 : 1);
-    const double mxv_d = tot[0] * invn_d, mtv_d = tot[1] * invn_d, mxa_d = tot[6] * invn_d, mta_d = tot[7] * invn_d;
-    const double cv = tot[4] - n * mxv_d * mtv_d, xv = tot[2] - n * mxv_d * mxv_d, tv = tot[3] - n * mtv_d * mtv_d;
-    const double ca = tot[10] - n * mxa_d * mta_d, xa = tot[8] - n * mxa_d * mxa_d, ta = tot[9] - n * mta_d * mta_d;
-    const float invn = (float)invn_d, nm1 = (float)nm1_d;
-    const float mxv = (float)mxv_d, mtv = (float)mtv_d, mxa = (float)mxa_d, mta = (float)mta_d;
-    const float covv = (float)(cv * invn_d), covA = (float)(ca * invn_d);
-    const float denv = (float)(xv * nm1_d + tv * nm1_d + (mxv_d - mtv_d) * (mxv_d - mtv_d));
-    const float dena = (float)(xa * nm1_d + ta * nm1_d + (mxa_d - mta_d) * (mxa_d - mta_d));
-    const float cccv = 2.f * covv / denv, ccca = 2.f * covA / dena;
-    const float loss_e = (float)(tot[12] * invn_d), nvalid = (float)tot[13];
-    const bool use_e = n_expr > 0 && nvalid > 0.f;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const float lv = wv == 0.f ? 0.f : (use_mse ? (float)(tot[5] * invn_d) : 1.f - cccv);
-        const float la = wa == 0.f ? 0.f : (use_mse ? (float)(tot[11] * invn_d) : 1.f - ccca);
-        out[0] = gave_up ? __builtin_nanf("") : wv * lv + wa * la + (use_e ? expr_w * loss_e : 0.f);
-        out[1] = lv; out[2] = la; out[3] = loss_e; out[4] = nvalid; out[5] = (float)tot[14]; out[6] = cccv; out[7] = ccca;
-    }
+    const double n = (double)rows, invn = 1.0 / n, nm1 = 1.0 / (double)(rows > 1 ? rows - 1 : 1);
+    const double mxv = tot[0] * invn, mtv = tot[1] * invn, mxa = tot[6] * invn, mta = tot[7] * invn;
+    const double cv = tot[4] - n * mxv * mtv, xv = tot[2] - n * mxv * mxv, tv = tot[3] - n * mtv * mtv;
+    const double ca = tot[10] - n * mxa * mta, xa = tot[8] - n * mxa * mxa, ta = tot[9] - n * mta * mta;
+    const VaTerm sv = va_term(mxv, mtv, cv * invn, xv * nm1 + tv * nm1, tot[5] * invn, invn, nm1);
+    const VaTerm sa = va_term(mxa, mta, ca * invn, xa * nm1 + ta * nm1, tot[11] * invn, invn, nm1);
+    const bool use_e = n_expr > 0 && tot[13] > 0.0 && expr_w != 0.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        va_write_out(out, sv, sa, tot[12], tot[13], tot[14], use_e, wv, wa, expr_w, use_mse, invn, gave_up);
     if (i < rows) {
-        float* g = dy + (size_t)i * C;
-        const float* l = y + (size_t)i * C;
-        for (int k = 0; k < C; ++k) g[k] = 0.f;
-        if (use_e && valid[i]) {
-            float m = l[0];
-            for (int k = 1; k < n_expr; ++k) m = fmaxf(m, l[k]);
-            float se = 0.f;
-            for (int k = 0; k < n_expr; ++k) se += expf(l[k] - m);
-            const float sc = expr_w * invn;
-            const int lab = (int)cls[i];
-            for (int k = 0; k < n_expr; ++k) g[k] = sc * (expf(l[k] - m) / se - (k == lab ? 1.f : 0.f));
-        }
-        float gv, ga;
-        if (use_mse) {
-            gv = 2.f * (a - b) * invn;
-            ga = 2.f * (c - e) * invn;
-        } else {
-            const float dcv = 2.f * (b - mtv) * invn / denv -
-                              (2.f * covv / (denv * denv)) * (2.f * (a - mxv) * nm1 + 2.f * (mxv - mtv) * invn);
-            const float dca = 2.f * (e - mta) * invn / dena -
-                              (2.f * covA / (dena * dena)) * (2.f * (c - mxa) * nm1 + 2.f * (mxa - mta) * invn);
-            gv = -dcv;
-            ga = -dca;
-        }
-        if (wv != 0.f) g[iv] += wv * gv;
-        if (wa != 0.f) g[ia] += wa * ga;
+        const bool ce_row = use_e && valid[i];
+        va_row_grad(y + (size_t)i * C, dy + (size_t)i * C, C, iv, ia, b, e, ce_row, ce_row ? (int)cls[i] : 0, n_expr, wv, wa,
+                    (double)expr_w * invn, use_mse, sv, sa, invn);
     }
     // leave: the last block out resets both words for the next launch (stream order: a kernel boundary lies in between)
     __syncthreads();
@@ -604,7 +580,8 @@ extern "C" int m3t_att_fuse_bwd(const float* df, const float* s_v, const float* 
     return 0;
 }
 
-extern "C" size_t m3t_va_loss_ws_bytes(int rows) { return rows > 0 ? (size_t)cdiv(rows, LB) * 16 * sizeof(float) : 0; }
+// 16 doubles per 256-row block: the fused form's VP raw moments, or the three-launch form's part A + part B
+extern "C" size_t m3t_va_loss_ws_bytes(int rows) { return rows > 0 ? (size_t)cdiv(rows, LB) * 16 * sizeof(double) : 0; }
 
 extern "C" int m3t_va_loss(const float* y_hat, int rows, int C, int iv, int ia, const float* valence,
                            const float* arousal, const int64_t* class_expr, const uint8_t* expr_valid, int n_expr,
@@ -614,22 +591,24 @@ extern "C" int m3t_va_loss(const float* y_hat, int rows, int C, int iv, int ia, 
     if (!y_hat || !valence || !arousal || !out_scalars || !dy) return M3T_EINVAL;
     if (n_expr > 0 && (!class_expr || !expr_valid)) return M3T_EINVAL;
     static const bool fused_on = !(getenv("M3T_VA_LOSS_FUSED") && getenv("M3T_VA_LOSS_FUSED")[0] == '0');
-    if (rows > 1024 && ws && ws_bytes >= m3t_va_loss_ws_bytes(rows) && cdiv(rows, LB) <= 128 && fused_on && ((uintptr_t)ws % 8) == 0) {
+    // both grid-wide forms keep fp64 partials in ws: 8-byte aligned and large enough, else the one-workgroup form
+    const bool ws_ok = ws && ((uintptr_t)ws % 8) == 0 && ws_bytes >= m3t_va_loss_ws_bytes(rows);
+    double* part = reinterpret_cast<double*>(ws);
+    if (rows > 1024 && ws_ok && cdiv(rows, LB) <= 128 && fused_on) {
         // one launch (round 6): the blocks meet once inside the kernel; <= 128 blocks so that all are resident whatever else runs
         VaSync* sync = va_sync_words();
         if (sync) {
             const int nb = cdiv(rows, LB);
             va_loss_fused_kernel<<<nb, LB, 0, (hipStream_t)stream>>>(y_hat, rows, C, iv, ia, valence, arousal, class_expr, expr_valid, n_expr, w_v,
-                                                                     w_a, expr_w, use_mse, reinterpret_cast<double*>(ws), sync, 1 << 22,
-                                                                     out_scalars, dy);
+                                                                     w_a, expr_w, use_mse, part, sync, 1 << 22, out_scalars, dy);
             M3T_LAUNCH_CHECK();
             return 0;
         }
     }
-    if (rows > 1024 && ws && ws_bytes >= m3t_va_loss_ws_bytes(rows)) {
+    if (rows > 1024 && ws_ok) {
         const int nb = cdiv(rows, LB);
-        float* partA = ws;
-        float* partB = ws + (size_t)nb * 8;
+        double* partA = part;
+        double* partB = part + (size_t)nb * 8;
         hipStream_t s = (hipStream_t)stream;
         va_loss_sums_kernel<<<nb, LB, 0, s>>>(y_hat, rows, C, iv, ia, valence, arousal, class_expr, expr_valid, n_expr, partA);
         va_loss_moments_kernel<<<nb, LB, 0, s>>>(y_hat, rows, C, iv, ia, valence, arousal, partA, partB);
