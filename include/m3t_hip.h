@@ -744,6 +744,24 @@ int m3t_power_to_db(const float* s, long long n, float amin, float top_db, float
 int m3t_stack_context(const float* mel, long long n_rows, int n_mels, long long start, int w_len, int step, int width,
                       float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Video ingest: what the reference's two loaders do to pixels between the decoder and the first convolution (models/dataset.py:16-31,46-80
+ * and :312, models/vox2_dataset.py:14-50, models/cv_augment.py:6-37) and the normalisation of models/model.py:106, in one pass over the
+ * uint8 frames as decoded, frames [N][Ts][Hs][Ws][3] (channel order as stored).  For clip n, output frame t, pixel (y, x), channel c:
+ *     f = frame_idx[n][t]                 (device [N][T]; NULL = identity, T <= Ts; -1 = "no frame yet": zeros, dataset.py:68; a missing
+ *                                          frame repeats the previous index, dataset.py:67; a short window repeats its last, dataset.py:312)
+ *     v = f < 0 ? 0 : frames[n][f][cy + y][cx + (mirror ? W-1-x : x)][c]
+ *     o = (cut_y1 <= y < cut_y2 and cut_x1 <= x < cut_x2) ? 0.0f : lut[n][v]
+ * geom: device [N][8] ints = cy, cx, mirror, cut_y1, cut_y2, cut_x1, cut_x2, 0.  lut: device float tables of 256 entries, lut_stride 256
+ * = one per clip, 0 = one for all: (v - 127.5) / 127.5, with the two uint8 tables of cv_augment.py:16,33 composed in front of it for the
+ * VoxCeleb2 colour jitter; the cutout's fill 127.5 (dataset.py:16) normalises to exactly 0.  The kernel only gathers: its values are the
+ * table's bits.  Window and frame index are clamped into range on the device; no byte outside frames[0 .. N Ts Hs Ws 3) is read.
+ * layout 0: out [N T H W][4], fourth channel 0 -- the image m3t_planes_to_cl4 writes; raises the slot armed by m3t_amax_out the same way.
+ * layout 1: out [N][3][T][H][W].  frames and out 16-byte aligned, the tables 4-byte; H <= Hs, W <= Ws (about 1000 pixels per row at most).
+ * M3T_EINVAL: null or misaligned pointers, non-positive sizes; N == 0 or T == 0 returns 0. */
+int m3t_video_ingest(const uint8_t* frames, int N, int Ts, int Hs, int Ws, const int* frame_idx, int T, const int* geom,
+                     const float* lut, int lut_stride, int H, int W, int layout, float* out, void* stream);
+
 
 /* ---------------------------------------------------------------------------------
  * Attention decoder of --fusion_type att_dec (csrc/attdec.hip).  Replaces the decoder loop of AttEncDec.forward with

@@ -3183,6 +3183,51 @@ class CLTensor:
         return btc_to_bct(self.data.view(self.N, self.T * self.H * self.W, self.C)).view(self.N, self.C, self.T, self.H, self.W)
 
 
+class VideoCL(CLTensor):
+    """the video as video_ingest leaves it for a stem's first convolution: `data` [N T H W, 4] (three real channels, the fourth zero -- the image
+    m3t_planes_to_cl4 writes) and the magnitude slot the ingest kernel raised.  conv3d_cl takes it as a first layer's input without the
+    transpose and the measurement."""
+    __slots__ = ()
+
+    def planes(self):
+        """[N, 3, T, H, W]: the three real channels (a layer the chain does not cover)"""
+        p4 = btc_to_bct(self.data.view(self.N, self.T * self.H * self.W, 4))
+        return p4[:, :3].contiguous().view(self.N, 3, self.T, self.H, self.W)
+
+
+def video_ingest(frames, frame_idx, T, geom, lut, H, W, layout):
+    """m3t_video_ingest (include/m3t_hip.h): frames uint8 [N, Ts, Hs, Ws, 3], frame_idx int32 [N, T] or None (identity), geom int32 [N, 8], lut float32
+    [256] (shared) or [N, 256], all contiguous device tensors -> VideoCL (layout "cl") or the planes [N, 3, T, H, W] (layout "planes").  No
+    validation of the tables' contents here (m3t.video.ingest does it on the host); the kernel clamps what it indexes with."""
+    if layout not in ("cl", "planes"):
+        raise ValueError("layout must be 'cl' or 'planes'")
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[4] == 3
+            and frames.is_contiguous()):
+        raise M3THipError("video_ingest: frames must be a contiguous uint8 device tensor [N, Ts, Hs, Ws, 3]")
+    N_, Ts, Hs, Ws = (int(v) for v in frames.shape[:4])
+    dev = frames.device
+    for t_, dt, shp, name in ((frame_idx, torch.int32, (N_, T), "frame_idx"), (geom, torch.int32, (N_, 8), "geom")):
+        if t_ is not None and not (t_.is_cuda and t_.dtype == dt and tuple(t_.shape) == shp and t_.is_contiguous()):
+            raise M3THipError("video_ingest: %s must be a contiguous int32 device tensor %s" % (name, list(shp)))
+    if not (lut.is_cuda and lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) in ((256,), (N_, 256))):
+        raise M3THipError("video_ingest: lut must be a contiguous float32 device tensor [256] or [N, 256]")
+    stride = 256 if lut.dim() == 2 else 0
+    if layout == "cl":
+        out = torch.empty(N_ * T * H * W, 4, dtype=torch.float32, device=dev)
+        slot = amax_slots(1, dev)
+        amax_out(slot.data_ptr())
+    else:
+        out = torch.empty(N_, 3, T, H, W, dtype=torch.float32, device=dev)
+        slot = None
+    try:
+        _lib.check(lib().m3t_video_ingest(_p(frames), N_, Ts, Hs, Ws, _p(frame_idx), T, _p(geom), _p(lut), stride, H, W,
+                                          0 if layout == "cl" else 1, _p(out), _stream()), "m3t_video_ingest")
+    except BaseException:
+        _amax_clear()
+        raise
+    return VideoCL(out, N_, T, H, W, slot) if layout == "cl" else out
+
+
 _GRAD_SLOT = {}          # id of a gradient tensor OBJECT -> (weakref, slot tensor, version): slots of gradients handed from backward to backward
 
 
@@ -3211,6 +3256,8 @@ def conv3d_cl_ok(x, w, stride, padding, groups, dilation, padding_mode):
     Co, Ci, kt, kh, kw = w.shape
     if Co % 64 != 0:
         return False
+    if isinstance(x, VideoCL):                # (m3t.video.ingest: a first layer's input, already the four-channel image)
+        return Ci <= 4 and kw <= 8 and x.slot is not None
     if isinstance(x, CLTensor):
         return Ci % 32 == 0 and x.C == Ci
     return x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and Ci <= 4 and kw <= 8 and not x.requires_grad
@@ -3238,10 +3285,15 @@ class _Conv3dCL(torch.autograd.Function):
             w8 = torch.zeros(Co, kt, kh, 8, 4, dtype=torch.float32, device=x.device)
             w8[:, :, :, :kw, :Ci].copy_(w.detach().permute(0, 2, 3, 4, 1))
             w_t = w8.view(Co, kt * kh * 32)
-            x_cl = torch.empty(srows, 4, dtype=torch.float32, device=x.device)
-            a_x = slots.data_ptr()
-            amax_out(a_x)
-            _lib.check(lib().m3t_planes_to_cl4(_p(_req(x.contiguous(), "x")), _p(x_cl), N_, Ci, T_ * H_ * W_, _stream()), "m3t_planes_to_cl4")
+            if x_slot is not None:                   # (a VideoCL: the ingest kernel wrote the image and raised its slot)
+                x_cl = _req(x, "x")
+                a_x = x_slot.data_ptr()
+                ctx.w_keep.append(x_slot)
+            else:
+                x_cl = torch.empty(srows, 4, dtype=torch.float32, device=x.device)
+                a_x = slots.data_ptr()
+                amax_out(a_x)
+                _lib.check(lib().m3t_planes_to_cl4(_p(_req(x.contiguous(), "x")), _p(x_cl), N_, Ci, T_ * H_ * W_, _stream()), "m3t_planes_to_cl4")
         else:
             cw = Ci
             w_t = None                               # (the [co][(tap, ci)] image is written straight from w: m3t_f16x3_split_perm)
@@ -3355,10 +3407,10 @@ class _Conv3dCL(torch.autograd.Function):
 
 
 def conv3d_cl(x, w, b, stride, padding):
-    """x: CLTensor, or the video planes [N, <= 4, T, H, W] of a stem's first layer -> CLTensor"""
+    """x: CLTensor, or the video of a stem's first layer (its planes [N, <= 4, T, H, W] or a VideoCL) -> CLTensor"""
     stride, padding = tuple(stride), tuple(padding)
     if isinstance(x, CLTensor):
-        geo = (x.N, x.T, x.H, x.W, stride, padding, False, x.slot)
+        geo = (x.N, x.T, x.H, x.W, stride, padding, isinstance(x, VideoCL), x.slot)
         data = x.data
     else:
         geo = (x.shape[0], x.shape[2], x.shape[3], x.shape[4], stride, padding, True, None)

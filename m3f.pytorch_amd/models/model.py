@@ -15,6 +15,9 @@ installed the class derives from pl.LightningModule exactly as the reference doe
 
 `--fusion_type att_dec` (model.py:96-97,119-126) runs the attention encoder-decoder of models/rnn.py (AttEncDec) on the
 decoder kernels of csrc/attdec.hip.  Validation/test window stitching is host glue in m3t/stitch.py.
+`batch['video']` may also be the frames as decoded -- uint8 [N, Ts, Hs, Ws, 3], with the loader's draws in `batch['video_aug']` and the frame
+indices in `batch['video_frame_idx']` (m3t/video.py): crop, mirror, cutout and the normalisation then run as one kernel in front of the first
+convolution; a float32 `video` takes the reference's route.
 Out of scope: dataloaders (need the Aff-Wild2 dataset and cv2), the LR range finder.
 """
 import os
@@ -24,7 +27,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
-from m3t import ops
+from m3t import ops, video
 from .backbone import VA_3DDenseNet, VA_3DResNet, VA_3DVGGM, VA_3DVGGM_Split
 from .rnn import GRU, AttEncDec, run_grus, run_grus_cat
 from .att_fusion import AttFusion
@@ -102,7 +105,11 @@ class AffWild2VA(_Base):
         hp = self.hparams
         if hp.modality == 'audio':
             return self.audio(batch['audio'])
-        x = (batch['video'] - 127.5) / 127.5            # to [-1, 1] (model.py:106)
+        x = batch['video']
+        if x.dtype == torch.uint8:                      # frames as decoded [N, Ts, Hs, Ws, 3]: crop, mirror, cutout and normalisation in one kernel
+            x = video.ingest_for(self.visual, x, batch.get('video_aug'), batch.get('video_frame_idx'))
+        else:
+            x = (x - 127.5) / 127.5                     # to [-1, 1] (model.py:106)
         if 'audio' in hp.modality:
             audio_feats, video_feats = self._encode_av(batch, x)
             video_feats = ops.linear(video_feats, self.proj_v.weight, self.proj_v.bias, 0)

@@ -9,13 +9,14 @@ dL/dz in its forward pass; `train_acc` stays on the device (M3T_STEP_SYNC=1: a P
 The reference evaluates its loss only with `--backbone v2p --backend fc` (its defaults): the other two backbones return per-frame outputs
 [B,T,1000] that the module never pools, and F.cross_entropy rejects them.  The constructor accepts `resnet` and `densenet` as the
 reference's does; their steps raise here too (m3t.ops.cls_loss takes per-clip logits).  m3t/checkpoints.py carries a trained checkpoint
-into AffWild2VA.  Out of scope: the dataloaders (VoxCeleb2, cv2) and the LR range finder.
+into AffWild2VA.  `batch['video']` may be uint8 frames as decoded with the draws in `batch['video_aug']` (m3t/video.py: crop, mirror, colour
+jitter and normalisation in one kernel).  Out of scope: the dataloaders (VoxCeleb2, cv2) and the LR range finder.
 """
 from argparse import ArgumentParser
 
 import torch
 
-from m3t import ops
+from m3t import ops, video
 from .backbone import VA_3DDenseNet, VA_3DResNet, VA_3DVGGM
 from .model import _Base, _STEP_SYNC
 
@@ -42,25 +43,31 @@ class VoxCeleb2_1k(_Base):
         vis = getattr(self, 'visual', None)
         return isinstance(vis, VA_3DVGGM) and vis.backend == 'fc'
 
-    def forward(self, x):
-        x = (x - 127.5) / 127.5                         # to [-1, 1] (vox2_model.py:55)
-        if not x.is_cuda and self._frames():            # host input: the stock ops (the HIP back-end has no CPU path)
+    def _normalised(self, x, aug=None, frame_idx=None):
+        """to [-1, 1] (vox2_model.py:55); uint8 frames as decoded [N, Ts, Hs, Ws, 3] go through m3t.video (crop, mirror, jitter and this in one kernel)"""
+        if x.dtype == torch.uint8:
+            return video.ingest_for(self.visual, x, aug, frame_idx)
+        return (x - 127.5) / 127.5
+
+    def forward(self, x, aug=None, frame_idx=None):
+        x = self._normalised(x, aug, frame_idx)
+        if isinstance(x, torch.Tensor) and not x.is_cuda and self._frames():            # host input: the stock ops (the HIP back-end has no CPU path)
             return ops.temporal_pool(self.visual.forward_frames(x), 'mean')
         return self.visual(x)
 
     def ce_loss(self, y_hat, y):
         return ops.cls_loss(y_hat, y, 'ce')[0]
 
-    def _loss_and_hits(self, x, y):
+    def _loss_and_hits(self, x, y, aug=None, frame_idx=None):
         """(loss, stats = [loss, n_correct], correct [B]) of one batch"""
         if self._frames():
-            z = self.visual.forward_frames((x - 127.5) / 127.5)
+            z = self.visual.forward_frames(self._normalised(x, aug, frame_idx))
             return ops.pooled_cls_loss(z, y, 'mean', 'ce')
-        return ops.cls_loss(self.forward(x), y, 'ce')
+        return ops.cls_loss(self.forward(x, aug, frame_idx), y, 'ce')
 
     def training_step(self, batch, batch_idx):
         x, y = batch['video'], batch['label']
-        loss, stats, _ = self._loss_and_hits(x, y)
+        loss, stats, _ = self._loss_and_hits(x, y, batch.get('video_aug'), batch.get('video_frame_idx'))
         # a 0-dim device tensor (the reference: `.item()`, one host sync per step, vox2_model.py:67)
         acc = float(stats[1]) / x.size(0) if _STEP_SYNC else stats[1] / x.size(0)
         if getattr(self.hparams, 'test_lr', False):
@@ -73,7 +80,7 @@ class VoxCeleb2_1k(_Base):
 
     def validation_step(self, batch, batch_idx):
         with torch.no_grad():
-            loss, _, correct = self._loss_and_hits(batch['video'], batch['label'])
+            loss, _, correct = self._loss_and_hits(batch['video'], batch['label'], batch.get('video_aug'), batch.get('video_frame_idx'))
         return {'val_loss': loss, 'correct': correct > 0}
 
     def validation_end(self, outputs):
