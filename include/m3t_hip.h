@@ -745,6 +745,53 @@ int m3t_stack_context(const float* mel, long long n_rows, int n_mels, long long 
                       float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Batched audio ingest (csrc/audio_ingest.hip): the reference's AudioSet loader (models/audioset_dataset.py:58-87) for a whole batch of
+ * decoded clips, and the AffWild2 loader's stacking of pre-extracted tracks (models/dataset.py:83-95, :276-306).  A batch is a FLAT buffer
+ * plus per-clip tables on the device (the style of m3t_smooth_tracks' offsets); clips are not padded to a common length.  The pipeline of
+ * m3t.audio.ingest: m3t_audio_frame_batch -> m3t_sgemm ([R, n_fft] x [n_fft, 2 bins], one product) -> m3t_audio_power_mel -> m3t_audio_db_stack.
+ * clips: device long long [N][8] = off, len, start, nsamples, hop, nf, row_off, 0.  Clip n owns the samples wave[off .. off + len) of the
+ * n_samples in `wave`; its rows are row_off .. row_off + nf of the R rows of the batch, nf = 1 + nsamples / hop.  No kernel synchronises,
+ * uses float atomics or reduces in a data-dependent order.  A table entry that does not fit the buffers (off + len > n_samples,
+ * row_off + nf > R, a negative or zero size) is caught on the device: that clip's frames are not written / its output is zeros, and no byte
+ * outside the buffers is touched.  Every entry point: M3T_EINVAL for null or misaligned pointers (wave: its element size, tables: 8 bytes,
+ * floats and ints: 4) and non-positive sizes; N == 0 (or no rows / frames to write) returns 0.
+ *
+ * Framing (audioset_dataset.py:63-70 and librosa.stft(center=True), process/extract_melspec.py:13-20).  For clip n, frame f < nf, tap k < n_fft:
+ *     c[j]       = wave[off + (start + j) mod len],  0 <= j < nsamples     (the temporal crop; the modulo is np.pad(y, (0, nsamples - len + 5),
+ *                                                                           'wrap') of :65-68 for any start, and no sample wraps when
+ *                                                                           start + nsamples <= len)
+ *     cpad       = c with n_fft / 2 samples of padding per side (pad_mode 0: zeros, librosa >= 0.10; 1: numpy 'reflect' of the CROP)
+ *     frames[row_off + f][k] = window[k] * cpad[f * hop + k]
+ * dtype 0: wave is float32; 1: int16, scaled by 1 / 32768 (exact in fp32).  n_fft even.  m3t_frame_window on the crop of one clip gives
+ * the same values. */
+int m3t_audio_frame_batch(const void* wave, int dtype, long long n_samples, const long long* clips, int N, long long R, int n_fft,
+                          int pad_mode, const float* window, float* frames, void* stream);
+/* spec [R][2 bins] = (re | im) of the DFT product -> mel [R][n_mels]: mel[r][b] = sum_q weights[bands[b] + q] * |X[r][first_b + q]|^2 for
+ * q < bands[b + 1] - bands[b], an fp32 sum in bin order (librosa.feature.melspectrogram's `mel_basis @ |stft|^2` on the non-zero entries of
+ * the filterbank only: a Slaney band is one run of bins, a bin feeds at most two bands).  bands: device int [2 n_mels + 1] = n_mels + 1
+ * offsets into weights [nnz], then first_b per band; entries are clamped into [0, nnz] / [0, bins] on the device.
+ * Limits: bins <= 2048, n_mels <= 64, nnz <= 4096. */
+int m3t_audio_power_mel(const float* spec, long long R, int bins, int n_mels, const float* weights, const int* bands, int nnz,
+                        float* mel, void* stream);
+/* mel [R][n_mels] -> out [N][T][width n_mels].  Per clip n (one workgroup, two passes), with S = its rows row_off .. row_off + nf:
+ *     mx   = max over ALL nf rows of 10 log10(max(amin, S))         (another clip's rows are never seen; rows no output frame shows count)
+ *     db   = 10 log10(max(amin, S)) - 10 log10(max(amin, 1)),  floored at mx - 10 log10(max(amin, 1)) - top_db when top_db >= 0
+ *            (librosa.power_to_db(S, ref=1.0, amin, top_db), audioset_dataset.py:76)
+ *     out[n][t][k n_mels + c] = t step + k < nf ? db[t step + k][c] : 0.0f         (audioset_dataset.py:77-85 with step 3, width 5: the
+ *                                                                                 reference's zero padding, not the dB floor)
+ * Of `clips` only nf and row_off are read.  T width n_mels < 2^31, amin > 0. */
+int m3t_audio_db_stack(const float* mel, long long R, const long long* clips, int N, int T, int n_mels, int step, int width,
+                       float amin, float top_db, float* out, void* stream);
+/* The AffWild2 route (dataset.py:83-95, :276-278, :302-306) for N pre-extracted tracks in one launch.  mels: flat [total_rows][n_mels];
+ * tracks: device long long [N][4] = row_off, n_rows, start, track_len.  out [N][window][width n_mels]:
+ *     i' = min(i, track_len - 1)                                      (rows track_len .. window-1 repeat the last: np.pad 'edge', :303-304)
+ *     out[n][i][k n_mels + c] = r < n_rows ? mels[row_off + r][c] : 0.0f,  r = (start + i') step + k       (m3t_stack_context's row)
+ * track_len == 0 gives a zero clip (dataset.py:277-278, fps < 15); 0 <= track_len <= window, start >= 0, row_off + n_rows <= total_rows
+ * (a track that violates this is a zero clip). */
+int m3t_stack_context_batch(const float* mels, long long total_rows, int n_mels, const long long* tracks, int N, int window,
+                            int step, int width, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Video ingest: what the reference's two loaders do to pixels between the decoder and the first convolution (models/dataset.py:16-31,46-80
  * and :312, models/vox2_dataset.py:14-50, models/cv_augment.py:6-37) and the normalisation of models/model.py:106, in one pass over the
  * uint8 frames as decoded, frames [N][Ts][Hs][Ws][3] (channel order as stored).  For clip n, output frame t, pixel (y, x), channel c:

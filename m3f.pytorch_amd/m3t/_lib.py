@@ -148,6 +148,10 @@ SIGNATURES = {
     "m3t_power_spectrum": [_f, C.c_longlong, _i, _f, _s],
     "m3t_power_to_db": [_f, C.c_longlong, C.c_float, C.c_float, _f, _f, _z, _s],
     "m3t_stack_context": [_f, C.c_longlong, _i, C.c_longlong, _i, _i, _i, _f, _s],
+    "m3t_audio_frame_batch": [_f, _i, C.c_longlong, _f, _i, C.c_longlong, _i, _i, _f, _f, _s],
+    "m3t_audio_power_mel": [_f, C.c_longlong, _i, _i, _f, _f, _i, _f, _s],
+    "m3t_audio_db_stack": [_f, C.c_longlong, _f, _i, _i, _i, _i, _i, C.c_float, C.c_float, _f, _s],
+    "m3t_stack_context_batch": [_f, C.c_longlong, _i, _f, _i, _i, _i, _i, _f, _s],
     "m3t_video_ingest": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],
     "m3t_grad_norm_scale": [_f, _z, C.c_float, C.c_float, _f, _f, _z, _s],
     "m3t_grad_poison": [_f, _f, _s],

@@ -15,9 +15,22 @@ reflected ('reflect').  The stacking half is pinned on the reference's own funct
 
 Constants (window, DFT matrix, filterbank) are built once on the host in float64; the data path is HIP:
 m3t_frame_window -> m3t_sgemm (DFT, fp32-accurate) -> m3t_power_spectrum -> m3t_sgemm (mel) -> m3t_power_to_db.
+
+The batched ingest (csrc/audio_ingest.hip) is the input stage of the audio tasks: audio AS DECODED (16 kHz PCM, int16 or float32), a whole
+batch of ragged clips at once, to the `[N, T, 200]` rows of the reference's AudioSet loader (`models/audioset_dataset.py:58-87`: random fps,
+temporal crop with np.pad 'wrap', the spectrogram above, the context stack) in three kernels and one GEMM however many clips there are:
+
+  draw_audioset(tot, length, training)   one clip's draws, consuming `random` in the reference's order
+  plan_waves(...)                        host validation + the per-clip table, before anything touches a device
+  ingest(waves, aug, length)             m3t_audio_frame_batch -> m3t_sgemm (ONE DFT product) -> m3t_audio_power_mel -> m3t_audio_db_stack
+  load_audio_batch(mels, starts, ...)    the AffWild2 loader's collate step (`models/dataset.py:83-95, :276-306`): N pre-extracted tracks
+                                         -> [N, window, 200] in one launch, edge padding and the "fps < 15 -> zeros" rule included
+
+Out of scope: wav decoding and resampling (`librosa.load`), which stay on the host.
 """
 import ctypes as C
 import math
+import random
 
 import numpy as np
 import torch
@@ -116,4 +129,168 @@ def load_audio(mel_spec, start_idx, w_len):
     out = torch.empty(int(w_len), 5 * mel.shape[1], dtype=torch.float32, device=dev)
     _lib.check(lib().m3t_stack_context(_p(mel), mel.shape[0], mel.shape[1], int(start_idx), int(w_len), 3, 5, _p(out), _stream()),
                "m3t_stack_context")
+    return out
+
+
+# ---- batched ingest: decoded PCM -> [N, T, 200] (csrc/audio_ingest.hip) ---------------------------------------------------------------
+FPS_VALUES = [15.0, 17.0, 19.0, 22.0, 23.976, 24.0, 25.0, 29.97, 30.0]      # audioset_dataset.py:13
+_MEL_SPARSE = {}
+
+
+def draw_audioset(tot_samples, length, training):
+    """One clip's draws of models/audioset_dataset.py:60-69 for a decoded clip of `tot_samples` samples: random.choice(FPS_VALUES) (training
+    only; 30.0 otherwise), nsamples = int(length / fps * 16000), then random.randint(0, tot' - nsamples) (training) or the centre, where
+    tot' = nsamples + 5 when the clip is shorter than nsamples (the np.pad(..., 'wrap') of :65-68) and tot_samples otherwise."""
+    fps = random.choice(FPS_VALUES) if training else 30.0
+    nsamples = int(length / fps * 16000)
+    tot = int(tot_samples)
+    if nsamples > tot:
+        tot = nsamples + 5
+    start = random.randint(0, tot - nsamples) if training else (tot - nsamples) // 2
+    return {"fps": fps, "hop": hop_length(fps), "start": start, "nsamples": nsamples}
+
+
+def plan_waves(waves, aug=None, length=32, lengths=None):
+    """Host validation of an ingest call, before anything touches a device: returns (wave, table, R) -- the flat sample buffer (a 1-D int16 or
+    float32 tensor on the device `waves` lives on), the per-clip table int64 [N, 8] = off, len, start, nsamples, hop, nf, row_off, 0
+    (include/m3t_hip.h) and the number of spectrogram rows of the batch.  ValueError for a wrong dtype or rank, a draw count different from
+    N, hop <= 0, nsamples <= 0, length <= 0, a start outside [0, max(len, nsamples + 5)), an empty clip."""
+    if int(length) <= 0:
+        raise ValueError("ingest: length must be positive, got %r" % (length,))
+    if isinstance(waves, (list, tuple)):
+        clips = [np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w) for w in waves]
+        if not clips:
+            raise ValueError("ingest: no clips")
+        if lengths is not None:
+            raise ValueError("ingest: `lengths` goes with a [N, S] batch, a list carries its own")
+        if any(c.ndim != 1 for c in clips) or len({c.dtype for c in clips}) != 1:
+            raise ValueError("ingest: a list must hold 1-D arrays of one dtype")
+        lens = np.array([c.shape[0] for c in clips], np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        wave = torch.from_numpy(np.ascontiguousarray(np.concatenate(clips)))
+    else:
+        if isinstance(waves, np.ndarray):
+            waves = torch.from_numpy(np.ascontiguousarray(waves))
+        if not isinstance(waves, torch.Tensor):
+            raise ValueError("ingest: waves must be a tensor, an array or a list of 1-D arrays")
+        if waves.dim() != 2:
+            raise ValueError("ingest: waves must be [N, S], got %s" % (list(waves.shape),))
+        N, S = int(waves.shape[0]), int(waves.shape[1])
+        if lengths is None:
+            lens = np.full(N, S, np.int64)
+        else:
+            lens = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths)
+            if lens.shape != (N,) or not np.issubdtype(lens.dtype, np.integer):
+                raise ValueError("ingest: lengths must be integers [N]")
+            lens = lens.astype(np.int64)
+            if N and lens.max() > S:
+                raise ValueError("ingest: a length beyond the %d stored samples" % S)
+        offs = np.arange(N, dtype=np.int64) * S
+        wave = waves.detach().contiguous().reshape(-1)
+    if wave.dtype not in (torch.int16, torch.float32):
+        raise ValueError("ingest: waves must be int16 or float32, got %s" % wave.dtype)
+    N = int(lens.shape[0])
+    if N == 0 or lens.min() <= 0:
+        raise ValueError("ingest: an empty clip")
+    if aug is None:
+        aug = [draw_audioset(int(n), int(length), False) for n in lens]
+    if len(aug) != N:
+        raise ValueError("ingest: %d draws for %d clips" % (len(aug), N))
+    table = np.zeros((N, 8), np.int64)
+    table[:, 0], table[:, 1] = offs, lens
+    for n, a in enumerate(aug):
+        start, ns, hop = int(a["start"]), int(a["nsamples"]), int(a["hop"])
+        if hop <= 0 or ns <= 0:
+            raise ValueError("ingest: clip %d: hop %d and nsamples %d must be positive" % (n, hop, ns))
+        if not 0 <= start < max(int(lens[n]), ns + 5):
+            raise ValueError("ingest: clip %d: start %d outside [0, %d)" % (n, start, max(int(lens[n]), ns + 5)))
+        table[n, 2:6] = (start, ns, hop, 1 + ns // hop)
+    table[1:, 6] = np.cumsum(table[:-1, 5])
+    return wave, table, int(table[:, 5].sum())
+
+
+def _mel_sparse(device):
+    """the filterbank's non-zero runs: (weights float32 [nnz], bands int32 [2 n_mels + 1] = offsets | first bins, nnz) on `device`"""
+    key = (device.type, device.index)
+    c = _MEL_SPARSE.get(key)
+    if c is None:
+        fb = mel_filterbank()
+        w, offs, first = [], [0], []
+        for b in range(N_MELS):
+            nz = np.nonzero(fb[b])[0]
+            lo, hi = (int(nz[0]), int(nz[-1]) + 1) if nz.size else (0, 0)
+            w.append(fb[b, lo:hi])
+            offs.append(offs[-1] + hi - lo)
+            first.append(lo)
+        w = np.concatenate(w).astype(np.float32)
+        bands = np.array(offs + first, np.int32)
+        c = _MEL_SPARSE[key] = (torch.from_numpy(w).to(device), torch.from_numpy(bands).to(device), int(w.shape[0]))
+    return c
+
+
+def ingest(waves, aug=None, length=32, lengths=None, pad_mode="constant", top_db=80.0):
+    """waves: decoded 16 kHz PCM, int16 or float32: [N, S] (tensor or array; `lengths` int [N] for ragged clips stored in rows of S) or a
+    list of 1-D arrays.  A host tensor is copied to the device with non_blocking=True -- pin it to overlap the copy.  aug: one draw per
+    clip (draw_audioset) or None = the evaluation draws (30 fps, centred crop).  -> float32 device tensor [N, length, 200]: per clip what
+    load_audio(melspec_db(crop, fps), 0, length) gives (audioset_dataset.py:58-87), the dB floor taken from the clip's own maximum.
+    Everything is validated on the host first (ValueError); the per-clip table reaches the device in one copy; three kernels and one GEMM."""
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError("pad_mode must be 'constant' or 'reflect'")
+    wave, table, R = plan_waves(waves, aug, length, lengths)
+    if not torch.cuda.is_available():
+        raise M3THipError("m3t.audio needs the GPU: the M3T path has no CPU fallback")
+    dev = wave.device if wave.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    N, T, bins = table.shape[0], int(length), 1 + N_FFT // 2
+    tab = torch.from_numpy(table.reshape(-1)).to(dev, non_blocking=True)
+    wave = wave.to(dev, non_blocking=True)
+    win, dft, _ = _constants(dev)
+    weights, bands, nnz = _mel_sparse(dev)
+    L, st = lib(), _stream()
+    frames = torch.empty(R, N_FFT, dtype=torch.float32, device=dev)
+    _lib.check(L.m3t_audio_frame_batch(wave.data_ptr(), 1 if wave.dtype == torch.int16 else 0, wave.numel(), tab.data_ptr(), N, R, N_FFT,
+                                       1 if pad_mode == "reflect" else 0, _p(win), _p(frames), st), "m3t_audio_frame_batch")
+    spec = torch.empty(R, 2 * bins, dtype=torch.float32, device=dev)
+    sgemm(0, 0, R, 2 * bins, N_FFT, frames, 0, N_FFT, dft, 0, 2 * bins, spec, 0, 2 * bins, prec=0, exclusive=True)
+    mel = torch.empty(R, N_MELS, dtype=torch.float32, device=dev)
+    _lib.check(L.m3t_audio_power_mel(_p(spec), R, bins, N_MELS, _p(weights), bands.data_ptr(), nnz, _p(mel), st), "m3t_audio_power_mel")
+    out = torch.empty(N, T, 5 * N_MELS, dtype=torch.float32, device=dev)
+    _lib.check(L.m3t_audio_db_stack(_p(mel), R, tab.data_ptr(), N, T, N_MELS, 3, 5, 1e-10, float(top_db), _p(out), st), "m3t_audio_db_stack")
+    return out
+
+
+def load_audio_batch(mels, starts, track_lens, window, valid=None):
+    """The AffWild2 loader's audio half as a collate step (models/dataset.py:83-95, :276-306).  mels: N pre-extracted tracks, a list of
+    [rows_n, 40] arrays or tensors (or one [N, rows, 40]); starts, track_lens: int [N], 0 < track_len <= window; valid: bool [N] or None
+    (the loader's `fps >= 15`).  -> float32 device tensor [N, window, 200]: row i < track_len is load_audio(mel_n, start_n, track_len_n)'s,
+    rows track_len .. window-1 repeat row track_len-1 (np.pad 'edge'), an invalid clip is zeros.  One launch."""
+    window = int(window)
+    if isinstance(mels, (np.ndarray, torch.Tensor)):
+        if mels.ndim != 3:
+            raise ValueError("load_audio_batch: mels must be a list of [rows, n_mels] tracks or one [N, rows, n_mels] batch")
+        mels = list(mels)
+    N = len(mels)
+    starts, track_lens = np.asarray(starts, np.int64).reshape(-1), np.asarray(track_lens, np.int64).reshape(-1)
+    valid = np.ones(N, bool) if valid is None else np.asarray(valid).astype(bool).reshape(-1)
+    if N == 0 or window <= 0 or starts.shape != (N,) or track_lens.shape != (N,) or valid.shape != (N,):
+        raise ValueError("load_audio_batch: %d tracks need %d starts, track lengths and valid flags, and a positive window" % (N, N))
+    if starts.min() < 0 or track_lens.min() <= 0 or track_lens.max() > window:
+        raise ValueError("load_audio_batch: starts must be >= 0 and 0 < track_len <= window")
+    if any(m.ndim != 2 or m.shape[1] != mels[0].shape[1] or m.shape[0] <= 0 for m in mels):
+        raise ValueError("load_audio_batch: every track must be [rows > 0, n_mels]")
+    if not torch.cuda.is_available():
+        raise M3THipError("m3t.audio needs the GPU: the M3T path has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_mels = int(mels[0].shape[1])
+    rows = np.array([m.shape[0] for m in mels], np.int64)
+    table = np.zeros((N, 4), np.int64)
+    table[1:, 0] = np.cumsum(rows[:-1])
+    table[:, 1], table[:, 2], table[:, 3] = rows, starts, np.where(valid, track_lens, 0)
+    tab = torch.from_numpy(table.reshape(-1)).to(dev, non_blocking=True)
+    if all(isinstance(m, torch.Tensor) for m in mels):
+        flat = torch.cat([m.detach().to(dev, torch.float32) for m in mels]).contiguous()
+    else:
+        flat = torch.from_numpy(np.concatenate([np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m, np.float32) for m in mels])).to(dev, non_blocking=True)
+    out = torch.empty(N, window, 5 * n_mels, dtype=torch.float32, device=dev)
+    _lib.check(lib().m3t_stack_context_batch(_p(flat), int(rows.sum()), n_mels, tab.data_ptr(), N, window, 3, 5, _p(out), _stream()),
+               "m3t_stack_context_batch")
     return out

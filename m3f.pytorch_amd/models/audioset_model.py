@@ -7,13 +7,17 @@ epoch-end dicts.  The loss end runs on csrc/cls_loss.hip: `forward` pools with m
 per-frame logits [B,T,527] to ONE operator (m3t.ops.pooled_cls_loss: pooling, BCE-with-logits, top-1 statistic and dL/dz from its forward
 pass); `train_acc` stays on the device (M3T_STEP_SYNC=1: a Python float).  The head's Dropout(0.5) draws its mask inside the GEMM epilogue
 (models/rnn.py, `drop_seeds`), so a train-mode step has no bit-parity with the reference's torch RNG; eval mode has.
-m3t/checkpoints.py carries a trained checkpoint into AffWild2VA.  Out of scope: the dataloaders (AudioSet, librosa) and the LR range finder.
+m3t/checkpoints.py carries a trained checkpoint into AffWild2VA.  `batch['audio']` may be the audio as decoded -- 16 kHz PCM, int16 [N, S] or
+float32 [N, S], with the loader's draws in `batch['audio_aug']` (m3t.audio.draw_audioset) and the clips' lengths in `batch['audio_len']`:
+crop, spectrogram, power_to_db and the context stack of the reference's loader (audioset_dataset.py:58-87) then run on the device
+(m3t.audio.ingest) in front of the BiGRU; a float32 [N, T, 200] batch takes the reference's route.  Out of scope: decoding and the LR range
+finder.
 """
 from argparse import ArgumentParser
 
 import torch
 
-from m3t import ops
+from m3t import audio, ops
 from .model import _Base, _STEP_SYNC
 from .rnn import GRU
 from .vox2_model import _classification_epoch_end, _configure_optimizers
@@ -30,14 +34,20 @@ class AudioSet(_Base):
         self.audio = GRU(200, hparams.num_hidden, 2, 527, hparams.num_fc_layers, dropout=True)
         self.history = {'lr': [], 'loss': []}
 
-    def forward(self, x):
-        return ops.temporal_pool(self.audio(x), 'max')          # temporal max-pooling (audioset_model.py:36)
+    def _features(self, x, aug=None, lengths=None):
+        """[N, T, 200] rows; a waveform batch (int16, or 2-D float32 [N, S]) goes through m3t.audio.ingest with hparams.window frames"""
+        if x.dtype == torch.int16 or (x.dtype == torch.float32 and x.dim() == 2):
+            return audio.ingest(x, aug, self.hparams.window, lengths)
+        return x
+
+    def forward(self, x, aug=None, lengths=None):
+        return ops.temporal_pool(self.audio(self._features(x, aug, lengths)), 'max')          # temporal max-pooling (audioset_model.py:36)
 
     def bce_loss(self, y_hat, y):
         return ops.cls_loss(y_hat, y, 'bce')[0]
 
     def training_step(self, batch, batch_idx):
-        x, y = batch['audio'], batch['label']
+        x, y = self._features(batch['audio'], batch.get('audio_aug'), batch.get('audio_len')), batch['label']
         loss, stats, _ = ops.pooled_cls_loss(self.audio(x), y, 'max', 'bce')
         # top-1 accuracy: a 0-dim device tensor (the reference: `.item()`, one host sync per step, audioset_model.py:49)
         acc = float(stats[1]) / x.size(0) if _STEP_SYNC else stats[1] / x.size(0)
@@ -51,7 +61,8 @@ class AudioSet(_Base):
 
     def validation_step(self, batch, batch_idx):
         with torch.no_grad():
-            loss, _, correct = ops.pooled_cls_loss(self.audio(batch['audio']), batch['label'], 'max', 'bce')
+            x = self._features(batch['audio'], batch.get('audio_aug'), batch.get('audio_len'))
+            loss, _, correct = ops.pooled_cls_loss(self.audio(x), batch['label'], 'max', 'bce')
         return {'val_loss': loss, 'correct': correct}
 
     def validation_end(self, outputs):
