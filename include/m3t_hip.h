@@ -725,6 +725,40 @@ int m3t_smooth_tracks(const float* x, const long long* offsets, int n_tracks, in
  * for p (what the reference computes when the smoothed track is a torch tensor).  out2[1] = number of valid frames. */
 int m3t_ccc_masked(const double* p, const float* g, const float* g2, long long n, int p_unbiased, double* out2,
                    void* stream);
+/* m3t_ccc_masked on n_tracks tracks in one launch (get_smoothed_ccc.py:18-28, the loop over videos): track i = elements
+ * offsets[i] .. offsets[i+1] of p (fp64), g and g2 (fp32; g2 may be null), offsets: n_tracks+1 int64 on the device.
+ * out[i][0] = CCC, out[i][1] = number of valid frames: per track the bits m3t_ccc_masked gives (same passes, same
+ * thread-to-element mapping, same reduction tree). */
+int m3t_ccc_tracks(const double* p, const float* g, const float* g2, const long long* offsets, int n_tracks,
+                   int p_unbiased, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * The evaluation epoch on the device (csrc/evaluate.hip; m3t/evaluate.py): the reference's validation_step /
+ * validation_end / test_step / test_end (models/model.py:226-303, 339-373) without a host read-back per batch.
+ * No kernel uses atomics; every sum is fp64 in a fixed order.
+ *
+ * m3t_eval_append, once per batch (model.py:228-246, 320-337: the slicing of y_hat and the labels by `length`):
+ * y_hat [N][T][C] fp32, C >= 2, valence = channel C-2, arousal = channel C-1 (model.py:230); label_valence /
+ * label_arousal [N][T] fp32, both or neither; length [N] int64 on the device (clamped to [0, T]).
+ * rows [N][Q][T], Q = 4 with labels (v_pred, a_pred, v_gt, a_gt), else 2: frames t >= length[n] are 0 and their inputs
+ * are not read.  With labels, part [N][2][7] fp64 = n, sum p, sum g, sum p^2, sum g^2, sum p g, sum (p-g)^2 of window n
+ * over its valid frames -- t < length, |v_gt| <= 1 and |a_gt| <= 1 (model.py:254; NaN is not valid) -- for valence, arousal. */
+int m3t_eval_append(const float* y_hat, int N, int T, int C, const float* label_valence, const float* label_arousal,
+                    const long long* length, float* rows, double* part, void* stream);
+/* m3t_eval_gather, once per epoch (model.py:261-297, 354-366: group by video, sort by start, overlap-add and halve, or
+ * torch.cat): rows [W][Q][T] = the batches' rows concatenated; tracks [Q][F].  All tables int64 on the device: segment s
+ * puts rows[seg_row[s]][q][0 .. seg_len[s]) at the frames seg_dst[s] .. of its video; video v owns the segments
+ * vid_seg_off[v] .. vid_seg_off[v+1] (ascending seg_dst, no two equal) and the frames vid_frame_off[v] ..
+ * vid_frame_off[v+1] of each track, vid_frame_off[V] = F.  Frame f of a video = 0.f + x_1 + x_2 ... over the segments
+ * covering it in ascending seg_dst order, times 0.5f when f >= halve_from (window / 2 for overlap-add -- the tail covered
+ * once is halved too, as in the reference; any value >= the longest video for concatenation).  Every frame is written once. */
+int m3t_eval_gather(const float* rows, long long W, int Q, int T, const long long* seg_dst, const long long* seg_len,
+                    const long long* seg_row, const long long* vid_seg_off, const long long* vid_frame_off, int V,
+                    long long F, long long halve_from, float* tracks, void* stream);
+/* m3t_eval_metrics, once per epoch (model.py:249-259 with models/utils.py:6-18): part [W][2][7] summed in window order ->
+ * out5 = val_ccc_v, val_ccc_a, val_mse_v, val_mse_a, val_loss (fp64): unbiased variances, biased covariance,
+ * val_loss = 1 - (ccc_v + ccc_a) / 2.  A frame counts once per window that holds it.  No valid frame: NaN. */
+int m3t_eval_metrics(const double* part, long long W, double* out5, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Audio front-end: the glue kernels of the log-Mel pipeline that the reference runs offline with

@@ -144,6 +144,10 @@ SIGNATURES = {
     "m3t_cbam_bwd": [_f] * 23 + [_i] * 6 + [_f, _z, _s],
     "m3t_smooth_tracks": [_f, _f, _i, _i, _i, _f, _s],
     "m3t_ccc_masked": [_f, _f, _f, C.c_longlong, _i, _f, _s],
+    "m3t_eval_append": [_f, _i, _i, _i, _f, _f, _f, _f, _f, _s],
+    "m3t_eval_gather": [_f, C.c_longlong, _i, _i, _f, _f, _f, _f, _f, _i, C.c_longlong, C.c_longlong, _f, _s],
+    "m3t_eval_metrics": [_f, C.c_longlong, _f, _s],
+    "m3t_ccc_tracks": [_f, _f, _f, _f, _i, _i, _f, _s],
     "m3t_frame_window": [_f, C.c_longlong, _i, _i, _i, _f, _f, C.c_longlong, _s],
     "m3t_power_spectrum": [_f, C.c_longlong, _i, _f, _s],
     "m3t_power_to_db": [_f, C.c_longlong, C.c_float, C.c_float, _f, _f, _z, _s],

@@ -12,6 +12,7 @@ training_step, backward, RCCL all-reduce + clip, fused optimizer step -- plus:
     every step: host glue, identical traces by construction;
   * validation after every epoch through the module's own validation_step / validation_end (window stitching,
     SURVEY 8(f) f-1) and a best-`val_loss` checkpoint (Lightning's default ModelCheckpoint monitors val_loss, mode min);
+    `evaluate()` is the same epoch without a read-back per batch (m3t/evaluate.py), beside `validate()`, which `fit()` calls;
   * `{'state_dict': ...}` checkpoints the reference's eval.py loads strictly (eval.py:14-15), with optimizer and
     scheduler state for resume.
 
@@ -120,6 +121,31 @@ class Trainer:
         self.ddp.agree_on_scan_error()               # eval forwards end here: nothing else would report a dead scan (every rank raises or none)
         res = self.model.validation_end(outputs)
         return res
+
+    def evaluate(self, batches, test=False, out_path=None):
+        """validate() without a read-back per batch (m3t/evaluate.py): the forward passes are queued back to back, the windows
+        are stitched and scored on the device, and the epoch ends with one read-back of the five metrics.  Follows the module's
+        hooks: validation_step / validation_end, or with test=True test_step / test_end -- predictions only, overlap-added,
+        saved as predictions_test.pt, result {}; under hparams.test_on_val those are the validation hooks with overlap-add, as
+        in the reference.  Same tracks bit for bit, same file layout (out_path: another file name); the result is
+        validation_end's dict with Python floats.  Each rank scores its own shard, as in validate()."""
+        from .evaluate import Evaluator
+        hp = self.model.hparams
+        test_on_val = bool(getattr(hp, "test_on_val", False))
+        with_gt = test_on_val or not test
+        ev = Evaluator(hp.window, overlap=test_on_val or test, with_gt=with_gt)
+        self.model.eval()
+        with torch.no_grad():
+            for b in batches:
+                ev.add(self.model.forward(b), b)
+        self.ddp.agree_on_scan_error()               # as in validate(): nothing else would report a dead scan
+        res = self.last_eval = ev.finish()           # the tracks stay on the device: self.last_eval.smoothed_report()
+        res.save(out_path or ("predictions_val.pt" if with_gt else "predictions_test.pt"))
+        if not with_gt:
+            return {}
+        m = res.metrics
+        return {"val_loss": m["val_loss"], "progress_bar": {"val_ccc_v": m["val_ccc_v"], "val_ccc_a": m["val_ccc_a"]},
+                "log": dict(m)}
 
     # ------------------------------------------------------------------ rank plumbing
     @property
