@@ -501,6 +501,27 @@ int m3t_pool_cl_fwd(const float* x, size_t P, int H, int W, int C, int kh, int k
 int m3t_pool_cl_bwd(const float* dy, const unsigned char* win, size_t P, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                     float* dx, void* stream);
 
+/* Channels-last operators of the VGGFace front-end (csrc/vggface.hip; reference models/vggface.py:45-50: `x = F.relu(c(x))` after every Conv2d,
+ * `F.max_pool2d(x, 2, 2, 0, ceil_mode=True)` at the end of every block).  C % 4 == 0, C <= 1024 (C / 4 need not divide the block), 16-B aligned
+ * tensors, any number of rows; a refused call (M3T_EINVAL: C % 4 != 0, H < 1, W < 1, a misaligned pointer, a short workspace) launches nothing.
+ * ReLU as torch.relu (NaN stays NaN); its gradient as torch's threshold_backward (0 where y <= 0, dy elsewhere -- a NaN y lets dy through).
+ * m3t_amax_out arms the magnitude slot of y / yp (forward) and of dx (backward): one 64-bit atomic max per workgroup.
+ * dx_colsum [C] (optional): the column sums of dx -- the bias gradient of the convolution in front -- from the dx pass itself: fp64 per thread,
+ *   per workgroup and over the workgroups in a fixed order (no float atomics; reruns are bit-identical); needs ws of m3t_relu_cl_ws_bytes(M, C)
+ *   bytes, 8-B aligned (M = P H W for the pooled operator).
+ * m3t_relu_cl_fwd / _bwd (models/vggface.py:45-50, line 49): y = relu(x) over rows [M][C], y == x allowed; dx = dy where y > 0 (dx == dy allowed).
+ * m3t_relu_pool_cl_fwd / _bwd (models/vggface.py:45-50, lines 49-50): ReLU then a 2 x 2 max pooling with stride 2 and no padding over P frames
+ *   x [P][H][W][C] as ONE operator; Ho = ceil_mode ? (H + 1) / 2 : H / 2 (W alike), a ragged last window covers only the positions inside the
+ *   frame.  relu(x) at full resolution is neither written nor kept: forward writes yp [P][Ho][Wo][C] and one winner byte per element (dh * 2 +
+ *   dw; ties: the first maximum in window order, NaN wins, as torch); backward takes d(yp), yp and the bytes -- not x -- and writes dx
+ *   [P][H][W][C] by a gather over the input positions: d(yp) of the position's window where it won and yp > 0, else 0. */
+size_t m3t_relu_cl_ws_bytes(size_t M, int C);
+int m3t_relu_cl_fwd(const float* x, size_t M, int C, float* y, void* stream);
+int m3t_relu_cl_bwd(const float* dy, const float* y, size_t M, int C, float* dx, float* dx_colsum, float* ws, size_t ws_bytes, void* stream);
+int m3t_relu_pool_cl_fwd(const float* x, size_t P, int H, int W, int C, int ceil_mode, float* yp, unsigned char* win, void* stream);
+int m3t_relu_pool_cl_bwd(const float* dyp, const float* yp, const unsigned char* win, size_t P, int H, int W, int C, int ceil_mode, float* dx,
+                         float* dx_colsum, float* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * TCN (models/tcn.py).  Activations are channel-last [B,T,C] inside the library.
  * weight-norm reparametrisation (torch.nn.utils.weight_norm at models/tcn.py:19-20):

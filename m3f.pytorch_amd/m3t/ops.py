@@ -3246,14 +3246,25 @@ def _grad_slot(t):
     return e[1], e[4]
 
 
+def _cl_chain_on():
+    """the switches of the channels-last chain and the fp16x3 mode its walks are built for"""
+    return bool(STEM_CL[0] and CONV3D_GEMM[0] and CONV3D_IMPLICIT[0] and CONV3D_TAPS[0] and CONV3D_PRESPLIT[0] and _PREC[0] == _lib.M3T_GEMM_F16X3)
+
+
+def _w5_shape(w):
+    """(Co, Ci, kt, kh, kw) of a Conv3d weight -- or of a Conv2d weight [Co, Ci, kh, kw] as a unit time tap (the per-frame convolutions of
+    models/vggface.py)"""
+    return tuple(w.shape) if w.dim() == 5 else (w.shape[0], w.shape[1], 1, w.shape[2], w.shape[3])
+
+
 def conv3d_cl_ok(x, w, stride, padding, groups, dilation, padding_mode):
     """the channels-last chain covers this convolution (an fp32 device input; C_out % 64; C_in % 32, or a first layer with <= 4 channels and
-    <= 8 taps per row; the fp16x3 mode)"""
-    if not (STEM_CL[0] and CONV3D_GEMM[0] and CONV3D_IMPLICIT[0] and CONV3D_TAPS[0] and CONV3D_PRESPLIT[0] and _PREC[0] == _lib.M3T_GEMM_F16X3):
+    <= 8 taps per row; the fp16x3 mode).  w: a Conv3d weight, or a Conv2d weight (stride / padding / dilation then per frame: two values)"""
+    if not _cl_chain_on():
         return False
-    if groups != 1 or tuple(dilation) != (1, 1, 1) or padding_mode != "zeros" or not isinstance(padding, tuple):
+    if groups != 1 or tuple(dilation) != (1,) * (w.dim() - 2) or padding_mode != "zeros" or not isinstance(padding, tuple):
         return False
-    Co, Ci, kt, kh, kw = w.shape
+    Co, Ci, kt, kh, kw = _w5_shape(w)
     if Co % 64 != 0:
         return False
     if isinstance(x, VideoCL):                # (m3t.video.ingest: a first layer's input, already the four-channel image)
@@ -3270,7 +3281,7 @@ class _Conv3dCL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, geo):
         N_, T_, H_, W_, stride, padding, first, x_slot = geo
-        Co, Ci, kt, kh, kw = w.shape
+        Co, Ci, kt, kh, kw = _w5_shape(w)       # (w stays the Parameter object -- the key of the sinks and the magnitude table; a Conv2d weight is a unit time tap)
         To = (T_ + 2 * padding[0] - kt) // stride[0] + 1
         Ho = (H_ + 2 * padding[1] - kh) // stride[1] + 1
         Wo = (W_ + 2 * padding[2] - kw) // stride[2] + 1
@@ -3283,7 +3294,7 @@ class _Conv3dCL(torch.autograd.Function):
         if first:
             cw = 4
             w8 = torch.zeros(Co, kt, kh, 8, 4, dtype=torch.float32, device=x.device)
-            w8[:, :, :, :kw, :Ci].copy_(w.detach().permute(0, 2, 3, 4, 1))
+            w8[:, :, :, :kw, :Ci].copy_(w.detach().view(Co, Ci, kt, kh, kw).permute(0, 2, 3, 4, 1))
             w_t = w8.view(Co, kt * kh * 32)
             if x_slot is not None:                   # (a VideoCL: the ingest kernel wrote the image and raised its slot)
                 x_cl = _req(x, "x")
@@ -3336,7 +3347,7 @@ class _Conv3dCL(torch.autograd.Function):
         w, x_cl, slots = ctx.saved_tensors
         N_, T_, H_, W_, st, pd, first, _ = ctx.geo
         To, Ho, Wo = ctx.out_grid
-        Co, Ci, kt, kh, kw = w.shape
+        Co, Ci, kt, kh, kw = _w5_shape(w)
         # dy's magnitude slot and its column sums (= this layer's bias gradient), both produced by the kernel that wrote dy (BatchNorm's dx pass)
         slot_dy, dy_colsum = _grad_slot(dy) if dy.is_contiguous() else (None, None)
         dy_cl = _req(dy.contiguous(), "dy")
@@ -3361,7 +3372,7 @@ class _Conv3dCL(torch.autograd.Function):
             one = tuple(st) == (1, 1, 1)
             if not one:
                 dx.zero_()
-            plan, imgs = _dgrad_images(ctx, w, st, pd, (T_, H_, W_), ctx.a_w)
+            plan, imgs = _dgrad_images(ctx, w.detach().view(Co, Ci, kt, kh, kw), st, pd, (T_, H_, W_), ctx.a_w)
             for (cls, r, sub, size, base), w_img in zip(plan, imgs):
                 dst = dx if one else torch.empty(N_ * size[0] * size[1] * size[2], Ci, dtype=torch.float32, device=dy.device)
                 _lib.check(lib().m3t_conv3d_taps_pre(_p(dy_img), _p(w_img), _p(dst), N_, Co, Ci, size[0], size[1], size[2], To, Ho, Wo,
@@ -3407,8 +3418,11 @@ class _Conv3dCL(torch.autograd.Function):
 
 
 def conv3d_cl(x, w, b, stride, padding):
-    """x: CLTensor, or the video of a stem's first layer (its planes [N, <= 4, T, H, W] or a VideoCL) -> CLTensor"""
+    """x: CLTensor, or the video of a stem's first layer (its planes [N, <= 4, T, H, W] or a VideoCL) -> CLTensor.  w: a Conv3d weight, or a
+    Conv2d weight [Co, Ci, kh, kw] with per-frame stride / padding (a unit time tap; dw comes back in the Parameter's own shape)"""
     stride, padding = tuple(stride), tuple(padding)
+    if w.dim() == 4:
+        stride, padding = (1,) + stride, (0,) + padding
     if isinstance(x, CLTensor):
         geo = (x.N, x.T, x.H, x.W, stride, padding, isinstance(x, VideoCL), x.slot)
         data = x.data
@@ -3416,7 +3430,7 @@ def conv3d_cl(x, w, b, stride, padding):
         geo = (x.shape[0], x.shape[2], x.shape[3], x.shape[4], stride, padding, True, None)
         data = x
     y = _Conv3dCL.apply(data, w, b, geo)
-    k = w.shape[2:]
+    k = _w5_shape(w)[2:]
     To, Ho, Wo = ((d + 2 * p_ - k_) // s_ + 1 for d, p_, k_, s_ in zip(geo[1:4], padding, k, stride))
     return CLTensor(y, geo[0], To, Ho, Wo, None)
 
@@ -3585,6 +3599,127 @@ def pool_cl(x, k, s, p):
     slot = amax_slots(1, x.data.device)
     y = _PoolCL.apply(x.data, (x.N * x.T, x.H, x.W, k, s, p), slot)
     Ho, Wo = (x.H + 2 * p[0] - k[0]) // s[0] + 1, (x.W + 2 * p[1] - k[1]) // s[1] + 1
+    return CLTensor(y, x.N, x.T, Ho, Wo, slot)
+
+
+# ----------------------------------------------------------------------------- the VGGFace front-end on the chain
+# Reference models/vggface.py:45-50: Conv2d(3x3, pad 1) -> ReLU thirteen times, max_pool2d(2, 2, 0, ceil_mode=True) after every block.  The
+# convolutions are conv3d_cl with a Conv2d weight (a unit time tap, bias in the walk); csrc/vggface.hip adds the plain ReLU and the ReLU +
+# ceil-mode pooling the chain lacked.
+def vggface_ok(x):
+    """the channels-last chain applies to this input of models.vggface.VGGFace: an fp32 device tensor (frames [P, 3, H, W] / clips [B, 3, T, H, W])
+    or a CLTensor, the default fp16x3 mode and the chain's switches on -- the conditions of conv3d_cl_ok"""
+    if not _cl_chain_on():
+        return False
+    if isinstance(x, CLTensor):
+        return True
+    return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (4, 5) and not x.requires_grad
+
+
+def _relu_ws(device, M, Cc):
+    return workspace(device, max(int(lib().m3t_relu_cl_ws_bytes(M, Cc)), 8))
+
+
+class _ReluCL(torch.autograd.Function):
+    """F.relu over channels-last rows (csrc/vggface.hip m3t_relu_cl_*; reference models/vggface.py:49); y's and dx's magnitude slots are raised
+    by the kernels, dx's column sums (the bias gradient of the convolution in front) come from the dx pass"""
+
+    @staticmethod
+    def forward(ctx, x, inplace, y_slot):
+        x = _req(x, "x")
+        M, Cc = x.shape
+        y = x if inplace else torch.empty_like(x)
+        amax_out(y_slot.data_ptr() if y_slot is not None else None)
+        try:
+            with _Timed("relu_cl_fwd", 1, 0, nbytes=8 * M * Cc):
+                _lib.check(lib().m3t_relu_cl_fwd(_p(x), M, Cc, _p(y), _stream()), "m3t_relu_cl_fwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        if inplace:
+            ctx.mark_dirty(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = _req(dy.contiguous(), "dy")
+        M, Cc = y.shape
+        dx = torch.empty_like(y)
+        ws = _relu_ws(y.device, M, Cc)
+        slot = amax_slots(1, y.device)
+        csum = torch.empty(Cc, dtype=torch.float32, device=y.device)
+        amax_out(slot.data_ptr())
+        try:
+            with _Timed("relu_cl_bwd", 2, 0, nbytes=12 * M * Cc):
+                _lib.check(lib().m3t_relu_cl_bwd(_p(dy), _p(y), M, Cc, _p(dx), _p(csum), _p(ws), ws.numel() * 4, _stream()), "m3t_relu_cl_bwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        # the convolution in front takes dx as its dy: its magnitude slot and its column sums (that layer's bias gradient) ride along
+        _note_grad_slot(dx, slot, csum)
+        return dx, None, None
+
+
+def relu_cl(x, inplace=False):
+    """CLTensor -> CLTensor; inplace: x's rows are overwritten (a convolution's output, which its backward does not read)"""
+    slot = amax_slots(1, x.data.device)
+    y = _ReluCL.apply(x.data, bool(inplace), slot)
+    return CLTensor(y, x.N, x.T, x.H, x.W, slot)
+
+
+class _ReluPoolCL(torch.autograd.Function):
+    """F.relu + F.max_pool2d(2, 2, 0, ceil_mode) on channels-last frames as one operator (csrc/vggface.hip m3t_relu_pool_cl_*; reference
+    models/vggface.py:49-50): relu(x) at full resolution is neither written nor kept; backward reads d(yp), yp and the winner bytes"""
+
+    @staticmethod
+    def forward(ctx, x, geo, y_slot):
+        P, H, W, ceil_mode = geo
+        x = _req(x, "x")
+        Cc = x.shape[1]
+        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if ceil_mode else (H // 2, W // 2)
+        yp = torch.empty(P * Ho * Wo, Cc, dtype=torch.float32, device=x.device)
+        win = torch.empty(P * Ho * Wo, Cc, dtype=torch.uint8, device=x.device)
+        amax_out(y_slot.data_ptr() if y_slot is not None else None)
+        try:
+            with _Timed("relu_pool_cl_fwd", 1, 0, nbytes=(4 * P * H * W + 5 * P * Ho * Wo) * Cc):
+                _lib.check(lib().m3t_relu_pool_cl_fwd(_p(x), P, H, W, Cc, int(ceil_mode), _p(yp), C.c_void_p(win.data_ptr()), _stream()),
+                           "m3t_relu_pool_cl_fwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        ctx.save_for_backward(yp, win)
+        ctx.geo = geo
+        return yp
+
+    @staticmethod
+    def backward(ctx, dy):
+        yp, win = ctx.saved_tensors
+        P, H, W, ceil_mode = ctx.geo
+        dy = _req(dy.contiguous(), "dy")
+        Cc = yp.shape[1]
+        dx = torch.empty(P * H * W, Cc, dtype=torch.float32, device=yp.device)
+        ws = _relu_ws(yp.device, P * H * W, Cc)
+        slot = amax_slots(1, yp.device)
+        csum = torch.empty(Cc, dtype=torch.float32, device=yp.device)
+        amax_out(slot.data_ptr())
+        try:
+            with _Timed("relu_pool_cl_bwd", 2, 0, nbytes=(4 * P * H * W + 9 * yp.shape[0]) * Cc):
+                _lib.check(lib().m3t_relu_pool_cl_bwd(_p(dy), _p(yp), C.c_void_p(win.data_ptr()), P, H, W, Cc, int(ceil_mode), _p(dx), _p(csum),
+                                                      _p(ws), ws.numel() * 4, _stream()), "m3t_relu_pool_cl_bwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        _note_grad_slot(dx, slot, csum)
+        return dx, None, None
+
+
+def relu_pool_cl(x, ceil_mode=True):
+    """CLTensor -> CLTensor: relu then a 2 x 2 / stride 2 / no padding max pooling of every frame"""
+    slot = amax_slots(1, x.data.device)
+    y = _ReluPoolCL.apply(x.data, (x.N * x.T, x.H, x.W, bool(ceil_mode)), slot)
+    Ho, Wo = ((x.H + 1) // 2, (x.W + 1) // 2) if ceil_mode else (x.H // 2, x.W // 2)
     return CLTensor(y, x.N, x.T, Ho, Wo, slot)
 
 

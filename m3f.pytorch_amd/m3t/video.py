@@ -207,8 +207,12 @@ def ingest(frames_u8, aug=None, frame_idx=None, layout="cl", norm=None):
 
 def ingest_for(visual, frames_u8, aug=None, frame_idx=None):
     """the task modules' uint8 route: ingest for the front-end `visual` -- layout "cl" where its first Conv3d runs on the channels-last chain
-    (models.backbone.Conv3d.cl_chain), planes otherwise -- with the normalisation table of the device, so that the result has the bits of
-    the modules' float32 route, `(x - 127.5) / 127.5` evaluated by torch on that device."""
-    first = next((m for m in visual.modules() if isinstance(m, torch.nn.Conv3d)), None)
-    cl = first is not None and getattr(first, "cl_chain", False) and ops.STEM_CL[0]
+    (models.backbone.Conv3d.cl_chain; a models.backbone.VA_VGGFace on the chain), planes otherwise -- with the normalisation table of the
+    device, so that the result has the bits of the modules' float32 route, `(x - 127.5) / 127.5` evaluated by torch on that device."""
+    on_chain = getattr(visual, "on_chain", None)             # (models.backbone.VA_VGGFace: Conv2d layers, the whole front-end is the chain)
+    if on_chain is not None:
+        cl = bool(on_chain())
+    else:
+        first = next((m for m in visual.modules() if isinstance(m, torch.nn.Conv3d)), None)
+        cl = first is not None and getattr(first, "cl_chain", False) and ops.STEM_CL[0]
     return ingest(frames_u8, aug, frame_idx, "cl" if cl else "planes", norm="device")

@@ -8,7 +8,9 @@ BatchNorm3d + ReLU and spatial pooling, the temporal back-ends (BiGRU stacks, TC
 gates / BatchNorm2d inside the ResNet run in the HIP library; a configuration the library does not
 cover takes the stock op and says so once on stderr (m3t.ops.stock_fallback).  `VA_3DDenseNet` (:375-423, `--backbone
 densenet`): the ResNet3D stem as a channels-last chain feeding models/densenet.py's DenseNet52_3D, whose dense blocks run as one
-operator on csrc/dense.hip.  `VA_VGGFace` is out of scope.
+operator on csrc/dense.hip.  `VA_VGGFace` (:16-59, `--backbone vggface`): the per-frame VGGFace of models/vggface.py -- thirteen
+Conv2d + ReLU and five ceil-mode poolings as a channels-last chain (the tap walks with a unit time tap, csrc/vggface.hip for ReLU and
+ReLU + pooling) -- feeding the BiGRU back-end.
 """
 import math
 
@@ -19,6 +21,7 @@ from torch.nn.modules.utils import _triple
 from m3t import ops
 from .resnet import ResNet, ResNetV2, BasicBlock, BasicBlockV2
 from .densenet import DenseNet52_3D
+from .vggface import VGGFace
 from .rnn import GRU, run_grus
 from .tcn import TemporalConvNet, WeightNormConv1d
 
@@ -348,3 +351,42 @@ class VA_3DDenseNet(nn.Module):
             if self.backend == 'gru':
                 x = self.gru(x)
             return x
+
+
+class VA_VGGFace(nn.Module):
+    """reference models/backbone.py:16-59: VGGFace on every frame -> [B, T, 4096] -> GRU (the reference builds the 'gru' back-end only)"""
+
+    def __init__(self, inputDim=4096, hiddenDim=512, nLayers=2, nClasses=2, frameLen=16, backend='gru', nFCs=1):
+        super().__init__()
+        self.inputDim, self.hiddenDim, self.nClasses = inputDim, hiddenDim, nClasses
+        self.frameLen, self.nLayers, self.backend, self.nFCs = frameLen, nLayers, backend, nFCs
+        self.vgg = VGGFace()
+        if self.backend == 'gru':
+            self.gru = GRU(self.inputDim, self.hiddenDim, self.nLayers, self.nClasses, self.nFCs)
+        self._initialize_weights()
+
+    def on_chain(self):
+        """the front-end runs as a channels-last chain (m3t.video.ingest_for: the uint8 route then ingests straight into that layout)"""
+        return ops._cl_chain_on()
+
+    def forward(self, x, se=None, au=None):
+        """x: [B, 3, T, H, W] or a VideoCL.  (se, au: what models.model.AffWild2VA hands every front-end; unused here, as in the reference's
+        one-argument forward.)"""
+        b = x.N if isinstance(x, ops.CLTensor) else x.size(0)
+        # the clips go in as they are: on the chain the first walk reads [B, 3, T, H, W] (or the ingest kernel's rows) frame by frame -- the
+        # reference's transpose(1, 2).contiguous() copy (backbone.py:38-39) never happens
+        x = self.vgg(x)
+        x = x.view(b, -1, x.size(1))
+        if self.backend == 'gru':
+            x = self.gru(x)
+        return x
+
+    def _initialize_weights(self):
+        """the reference's pass over self.modules() (backbone.py:46-59), whose order fixes the RNG draws: every Conv2d xavier-normal with a
+        standard-normal bias, every Linear (fc1, then the GRU head's) xavier-normal with a zero bias.  (Its Conv1d / BatchNorm1d branches
+        meet no module here.)"""
+        for mod in self.modules():
+            if isinstance(mod, (nn.Conv2d, nn.Linear)):
+                nn.init.xavier_normal_(mod.weight)
+                if mod.bias is not None:
+                    nn.init.normal_(mod.bias) if isinstance(mod, nn.Conv2d) else nn.init.zeros_(mod.bias)

@@ -28,7 +28,7 @@ import torch.nn as nn
 from torch.nn import functional as F
 
 from m3t import ops, video
-from .backbone import VA_3DDenseNet, VA_3DResNet, VA_3DVGGM, VA_3DVGGM_Split
+from .backbone import VA_3DDenseNet, VA_3DResNet, VA_3DVGGM, VA_3DVGGM_Split, VA_VGGFace
 from .rnn import GRU, AttEncDec, run_grus, run_grus_cat
 from .att_fusion import AttFusion
 from .utils import concordance_cc2, mse  # noqa: F401  (re-exported like the reference)
@@ -71,6 +71,8 @@ class AffWild2VA(_Base):
                 self.visual = VA_3DVGGM_Split(split_layer=hp.split_layer, use_mtl=use_mtl, **common)
             elif hp.backbone == 'densenet':
                 self.visual = VA_3DDenseNet(**common)
+            elif hp.backbone == 'vggface':
+                self.visual = VA_VGGFace(**common)
             else:
                 raise NotImplementedError("backbone '%s' is outside the MI355X hot path (SURVEY.md section 2.1)" % hp.backbone)
         if 'audio' in hp.modality:
