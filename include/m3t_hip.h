@@ -863,6 +863,17 @@ int m3t_stack_context_batch(const float* mels, long long total_rows, int n_mels,
  * M3T_EINVAL: null or misaligned pointers, non-positive sizes; N == 0 or T == 0 returns 0. */
 int m3t_video_ingest(const uint8_t* frames, int N, int Ts, int Hs, int Ws, const int* frame_idx, int T, const int* geom,
                      const float* lut, int lut_stride, int H, int W, int layout, float* out, void* stream);
+/* The same with the reference's 256-pixel branch in front (dataset.py:61,73: crop 224 x 224, cv2.resize to 112 x 112).  H, W are the OUTPUT
+ * size; the crop window in the source is 2H x 2W at (cy, cx); mirror and cutout are in output coordinates:
+ *     xs = mirror ? W-1-x : x
+ *     s  = frames[n][f][cy+2y][cx+2xs][c] + frames[n][f][cy+2y][cx+2xs+1][c] + frames[n][f][cy+2y+1][cx+2xs][c] + frames[n][f][cy+2y+1][cx+2xs+1][c]
+ *     v  = f < 0 ? 0 : (s + 2) >> 2
+ *     o  = inside the cutout ? 0.0f : lut[n][v]
+ * (s + 2) >> 2 is what OpenCV's resize gives 8-bit images at an exact factor of 2 on both axes (INTER_LINEAR takes the integer INTER_AREA
+ * path there, by its published source; not checked against a run of it here).  Averaging then mirroring equals the reference's
+ * resize-then-flip.  Everything else as m3t_video_ingest; M3T_EINVAL also for 2H > Hs or 2W > Ws. */
+int m3t_video_ingest_half(const uint8_t* frames, int N, int Ts, int Hs, int Ws, const int* frame_idx, int T, const int* geom,
+                          const float* lut, int lut_stride, int H, int W, int layout, float* out, void* stream);
 
 
 /* ---------------------------------------------------------------------------------

@@ -3195,7 +3195,7 @@ class VideoCL(CLTensor):
         return p4[:, :3].contiguous().view(self.N, 3, self.T, self.H, self.W)
 
 
-def video_ingest(frames, frame_idx, T, geom, lut, H, W, layout):
+def video_ingest(frames, frame_idx, T, geom, lut, H, W, layout, _entry="m3t_video_ingest"):
     """m3t_video_ingest (include/m3t_hip.h): frames uint8 [N, Ts, Hs, Ws, 3], frame_idx int32 [N, T] or None (identity), geom int32 [N, 8], lut float32
     [256] (shared) or [N, 256], all contiguous device tensors -> VideoCL (layout "cl") or the planes [N, 3, T, H, W] (layout "planes").  No
     validation of the tables' contents here (m3t.video.ingest does it on the host); the kernel clamps what it indexes with."""
@@ -3220,12 +3220,19 @@ def video_ingest(frames, frame_idx, T, geom, lut, H, W, layout):
         out = torch.empty(N_, 3, T, H, W, dtype=torch.float32, device=dev)
         slot = None
     try:
-        _lib.check(lib().m3t_video_ingest(_p(frames), N_, Ts, Hs, Ws, _p(frame_idx), T, _p(geom), _p(lut), stride, H, W,
-                                          0 if layout == "cl" else 1, _p(out), _stream()), "m3t_video_ingest")
+        _lib.check(getattr(lib(), _entry)(_p(frames), N_, Ts, Hs, Ws, _p(frame_idx), T, _p(geom), _p(lut), stride, H, W,
+                                          0 if layout == "cl" else 1, _p(out), _stream()), _entry)
     except BaseException:
         _amax_clear()
         raise
     return VideoCL(out, N_, T, H, W, slot) if layout == "cl" else out
+
+
+def video_ingest_half(frames, frame_idx, T, geom, lut, H, W, layout):
+    """m3t_video_ingest_half (include/m3t_hip.h): video_ingest with the reference's 256-pixel branch in front -- H, W are the output size, the
+    crop window in the source is 2H x 2W, every output channel the rounded mean (a + b + c + d + 2) >> 2 of its 2 x 2 block.  Same arguments,
+    same checks, same result types."""
+    return video_ingest(frames, frame_idx, T, geom, lut, H, W, layout, _entry="m3t_video_ingest_half")
 
 
 _GRAD_SLOT = {}          # id of a gradient tensor OBJECT -> (weakref, slot tensor, version): slots of gradients handed from backward to backward

@@ -11,8 +11,15 @@ task modules normalise on the device (`models/model.py:106`: `(x - 127.5) / 127.
   ingest                     frames + draws -> ops.VideoCL (layout "cl") or float32 planes [N, 3, T, H, W] (layout "planes")
 
 Every value the kernel writes is an entry of a table built here, so the result has the bits of the reference's float32 arithmetic.
-Out of scope: the `cv2.resize` branch of `dataset.py:73` (`input_size > 128`; cv2's fixed-point bilinear is not pinned) -- the draws raise
-ValueError for it -- and decoding, which stays on the host.
+The `cv2.resize` branch of `dataset.py:73` (`input_size > 128`) is covered for the reference's default, the 256-pixel face tracks:
+`draw_affwild(256, ..., resize=True)` crops 224 x 224 and m3t_video_ingest_half halves it to 112 x 112 (a draw with `"scale": 2`).  224 -> 112
+is an exact factor of 2 on both axes, where OpenCV's `resize` replaces INTER_LINEAR for 8-bit images by its integer INTER_AREA path: every
+output channel is `(a + b + c + d + 2) >> 2` over its 2 x 2 source block, a uint8 again, so the table gather follows unchanged.  That rule is
+taken from OpenCV's published source (modules/imgproc/src/resize.cpp: `resize` switches INTER_LINEAR to INTER_AREA when both integer
+factors are 2, noting that the two agree there, and the 2 x 2 case of its fast area kernel sums four values, adds 2 and shifts by 2); cv2 is
+not installed where this project is developed, so it has NOT been checked against a run of the real `cv2.resize` -- tests/test_ingest_resize_host.py holds that check for whoever has OpenCV.
+Out of scope: every other resize factor (an `input_size > 128` whose crop is not 224 would need cv2's general fixed-point bilinear, which
+is not pinned) -- the draws raise ValueError for it, as does the default `resize=False` -- and decoding, which stays on the host.
 """
 import random
 
@@ -20,7 +27,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .ops import M3THipError, video_ingest
+from .ops import M3THipError, video_ingest, video_ingest_half
 
 
 def norm_lut(device=None):
@@ -55,13 +62,16 @@ def jitter_lut(brightness, contrast, norm=None):
     return norm[jitter_table(brightness, contrast)]
 
 
-def _crop(input_size, training, crop):
-    """(crop_x, crop_y, size) of dataset.py:54-61 / vox2_dataset.py:21-27"""
+def _crop(input_size, training, crop, resize=False):
+    """(crop_x, crop_y, size) of dataset.py:54-61 / vox2_dataset.py:21-27.  resize: the caller takes the 224 -> 112 halving of dataset.py:73"""
     if not crop:
         return 0, 0, int(input_size)
-    if input_size > 128:
-        raise ValueError("input_size %d > 128: the reference resizes the crop with cv2.resize (dataset.py:73), which the ingest does not cover"
-                         % input_size)
+    if input_size > 128 and not resize:
+        raise ValueError("input_size %d > 128: the reference resizes the crop with cv2.resize (dataset.py:73), which the ingest covers only "
+                         "for a 224-pixel crop halved to 112 (input_size 256), on request: draw_affwild(..., resize=True)" % input_size)
+    if input_size > 128 and input_size * 7 // 8 != 224:
+        raise ValueError("input_size %d > 128: the reference resizes the %d-pixel crop to 112 with cv2.resize (dataset.py:73); only the exact "
+                         "halving of a 224-pixel crop is covered" % (input_size, input_size * 7 // 8))
     if training:
         cx = random.randint(0, input_size // 8)
         cy = random.randint(0, input_size // 8)
@@ -70,18 +80,25 @@ def _crop(input_size, training, crop):
     return cx, cy, input_size * 7 // 8
 
 
-def draw_affwild(input_size, training, crop, cutout, mirror=False):
+def draw_affwild(input_size, training, crop, cutout, mirror=False, resize=False):
     """One clip's draws of models/dataset.py:46-80.  `mirror` is the caller's `random.random() > 0.5`, drawn BEFORE this call as at
-    dataset.py:258; then crop_x, crop_y (random.randint), then the cutout's y, x (np.random.randint).  Frames are input_size squares."""
-    cx, cy, size = _crop(input_size, training, crop)
+    dataset.py:258; then crop_x, crop_y (random.randint), then the cutout's y, x (np.random.randint).  Frames are input_size squares.
+    resize=True admits the reference's 256-pixel branch (dataset.py:61,73; input_size > 128 with a 224-pixel crop): the draw then carries
+    `"scale": 2`, its `size` is the 224-pixel window in the source and its cutout is drawn on the 112 x 112 output, which is what
+    sequence_cutout sees.  Any other input_size > 128 raises, with or without it."""
+    cx, cy, size = _crop(input_size, training, crop, resize)
+    scale = 2 if (crop and resize and input_size > 128) else 1
     cut = None
     if cutout and training:                                   # sequence_cutout, dataset.py:16-31 (one hole)
-        h = w = size
+        h = w = size // scale
         length = h // 2
         y = np.random.randint(h)
         x = np.random.randint(w)
         cut = (int(np.clip(y - length, 0, h)), int(np.clip(y + length, 0, h)), int(np.clip(x - length, 0, w)), int(np.clip(x + length, 0, w)))
-    return {"cy": cy, "cx": cx, "size": size, "mirror": bool(mirror and training), "cutout": cut, "table": None}
+    d = {"cy": cy, "cx": cx, "size": size, "mirror": bool(mirror and training), "cutout": cut, "table": None}
+    if scale != 1:
+        d["scale"] = scale
+    return d
 
 
 def draw_vox2(input_size, training, crop):
@@ -114,10 +131,25 @@ def frame_index(present, start, length, window):
     return out
 
 
+def batch_scale(aug):
+    """the one scale of a batch's draws (1: m3t_video_ingest; 2: m3t_video_ingest_half); ValueError for mixed or unknown scales"""
+    if not aug:
+        return 1
+    scales = {a.get("scale", 1) for a in aug}
+    if len(scales) != 1:
+        raise ValueError("ingest: the clips of a batch must share one scale, got %s" % sorted(scales, key=str))
+    scale = scales.pop()
+    if scale not in (1, 2):
+        raise ValueError("ingest: scale must be 1 or 2, got %r" % (scale,))
+    return int(scale)
+
+
 def plan(shape, dtype, aug=None, frame_idx=None):
     """Host validation of an ingest call, before anything touches a device: returns (T, H, W, geom int32 [N, 8], frame_idx int32 [N, T] or
     None, tables: list of per-clip uint8 [256] or None).  ValueError for a wrong shape or dtype, a crop window outside the frame, clips of
-    different output sizes, a cutout outside the output, a frame index outside [-1, Ts)."""
+    different output sizes, a cutout outside the output, a frame index outside [-1, Ts).  A draw may carry "scale" (absent: 1; 2: the
+    window `size` in the source is halved, m3t_video_ingest_half): one scale per batch, an even size, H = W = size // scale; the window is
+    checked with `size`, the cutout with the output size."""
     if dtype != torch.uint8 or len(shape) != 5 or shape[4] != 3:
         raise ValueError("ingest: frames must be uint8 [N, Ts, Hs, Ws, 3], got %s %s" % (dtype, list(shape)))
     N, Ts, Hs, Ws = (int(v) for v in shape[:4])
@@ -132,11 +164,15 @@ def plan(shape, dtype, aug=None, frame_idx=None):
         sizes = {int(a["size"]) for a in aug}
         if len(sizes) != 1:
             raise ValueError("ingest: the clips of a batch must share one output size, got %s" % sorted(sizes))
-        H = W = sizes.pop()
+        size = sizes.pop()
+        scale = batch_scale(aug)
+        if size % scale:
+            raise ValueError("ingest: scale %d needs an even crop window, got %d" % (scale, size))
+        H = W = size // scale
         for n, a in enumerate(aug):
             cy, cx = int(a["cy"]), int(a["cx"])
-            if H <= 0 or cy < 0 or cx < 0 or cy + H > Hs or cx + W > Ws:
-                raise ValueError("ingest: clip %d: crop window (%d, %d) + %d outside the %d x %d frame" % (n, cy, cx, H, Hs, Ws))
+            if H <= 0 or cy < 0 or cx < 0 or cy + size > Hs or cx + size > Ws:
+                raise ValueError("ingest: clip %d: crop window (%d, %d) + %d outside the %d x %d frame" % (n, cy, cx, size, Hs, Ws))
             cut = a.get("cutout") or (0, 0, 0, 0)
             if not (0 <= cut[0] <= cut[1] <= H and 0 <= cut[2] <= cut[3] <= W):
                 raise ValueError("ingest: clip %d: cutout %s outside the %d x %d output" % (n, tuple(cut), H, W))
@@ -162,7 +198,7 @@ def plan(shape, dtype, aug=None, frame_idx=None):
 def ingest(frames_u8, aug=None, frame_idx=None, layout="cl", norm=None):
     """frames_u8: uint8 [N, Ts, Hs, Ws, 3] as decoded (tensor or array; a host tensor is copied to the device with non_blocking=True -- pin
     it to overlap the copy; a non-contiguous or misaligned one is made contiguous).  aug: one draw per clip (draw_affwild / draw_vox2) or
-    None = no crop, mirror, cutout, plain normalisation.  frame_idx: integers [N, T] (frame_index) or None = the stored frames in order.
+    None = no crop, mirror, cutout, plain normalisation; draws with "scale": 2 (draw_affwild(..., resize=True)) halve the window.  frame_idx: integers [N, T] (frame_index) or None = the stored frames in order.
     norm: the 256-entry normalisation table the jitter tables are composed in front of (default norm_lut(); "device": norm_lut(device)).
     -> ops.VideoCL (layout "cl": a channels-last stem's first convolution takes it as it is) or float32 [N, 3, T, H, W] ("planes").
     Everything is validated on the host first (ValueError); the small tables reach the device in one copy."""
@@ -202,7 +238,8 @@ def ingest(frames_u8, aug=None, frame_idx=None, layout="cl", norm=None):
         fr = fr.contiguous()
     if fr.data_ptr() % 16 != 0:
         fr = fr.clone()
-    return video_ingest(fr, f_d, T, g_d, l_d, H, W, layout)
+    entry = video_ingest_half if batch_scale(aug) == 2 else video_ingest
+    return entry(fr, f_d, T, g_d, l_d, H, W, layout)
 
 
 def ingest_for(visual, frames_u8, aug=None, frame_idx=None):

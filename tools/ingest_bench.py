@@ -4,13 +4,16 @@
   float32 route  what the reference's loader hands over: float32 [N, 3, T, H, W] -> copy to the device -> (x - 127.5) / 127.5 (stock torch)
                  -> m3t_planes_to_cl4 with the magnitude slot armed (the first convolution's own first step)
   uint8 route    the frames as decoded: uint8 [N, T, H, W, 3] -> copy to the device -> m3t.video.ingest (one kernel; with --crop from
-                 128 x 128 frames, with per-clip draws: crop, mirror, cutout)
+                 128 x 128 frames, with per-clip draws: crop, mirror, cutout; with --input-size 256 from the reference's default
+                 256 x 256 face tracks: crop 224, halve to 112 (m3t_video_ingest_half), mirror, cutout -- the float32 route is then fed
+                 frames ALREADY cropped and resized, so the comparison leaves out the host's cv2.resize of every frame (and its
+                 crop, flip, transpose and cast), which the uint8 route does not need and which cannot be timed without cv2)
 
 and the full C5 training step (bench.py's c5 leg: AffWild2VA audiovisual / attention / v2p_split, training_step + backward + clip) fed
 each way, the host-to-device copy of the video included.  The two routes are run alternately in one process; each sample is a host
 clock around `--inner` repetitions that end in a device synchronise; medians and the spread (min .. max) are printed as one JSON line.
 
-    python tools/ingest_bench.py [--clips 8] [--frames 64] [--samples 15] [--inner 5] [--step-samples 9] [--crop]
+    python tools/ingest_bench.py [--clips 8] [--frames 64] [--samples 15] [--inner 5] [--step-samples 9] [--crop | --input-size 256]
 """
 import argparse
 import json
@@ -57,7 +60,11 @@ def main():
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--step-samples", type=int, default=9)
     ap.add_argument("--crop", action="store_true", help="uint8 frames of 128 x 128 with per-clip crop / mirror / cutout draws")
+    ap.add_argument("--input-size", type=int, default=None, choices=[256],
+                    help="uint8 frames of 256 x 256 with per-clip crop (224) / halve (112) / mirror / cutout draws: the halving kernel")
     a = ap.parse_args()
+    if a.crop and a.input_size:
+        raise SystemExit("--crop and --input-size are two cases: give one")
     if not torch.cuda.is_available():
         raise SystemExit("ingest_bench needs the GPU: a timing taken anywhere else says nothing")
     from m3t import _lib, ops, video
@@ -66,13 +73,17 @@ def main():
     dev = torch.device("cuda", 0)
     N, T, S = a.clips, a.frames, 112
     rs = np.random.RandomState(0)
-    src = 128 if a.crop else S
+    src = a.input_size or (128 if a.crop else S)
     frames = torch.from_numpy(rs.randint(0, 256, (N, T, src, src, 3)).astype(np.uint8)).pin_memory()
     aug = None
     if a.crop:
         random.seed(0)
         np.random.seed(0)
         aug = [video.draw_affwild(128, True, True, True, random.random() > 0.5) for _ in range(N)]
+    if a.input_size:
+        random.seed(0)
+        np.random.seed(0)
+        aug = [video.draw_affwild(a.input_size, True, True, True, random.random() > 0.5, resize=True) for _ in range(N)]
     x32_host = torch.from_numpy(rs.randint(0, 256, (N, 3, T, S, S)).astype(np.float32)).pin_memory()
     lib = ops.lib()
 
@@ -118,15 +129,18 @@ def main():
 
     steps = alternate([f32_step, u8_step], a.step_samples, 3)
     px = N * T * S * S
+    half = {"halved": True, "left_out": "the float32 route's host work: crop, cv2.resize 224 -> 112, flip, transpose, cast (cv2 is not timed)"} \
+        if a.input_size else {}
     print(json.dumps({
-        "tool": "ingest_bench", "clips": N, "frames": T, "source": src, "crop_mirror_cutout": bool(a.crop),
+        "tool": "ingest_bench", "clips": N, "frames": T, "source": src, "crop_mirror_cutout": bool(a.crop or a.input_size), **half,
         "host_bytes_f32": px * 12, "host_bytes_u8": int(frames.numel()),
         "input_stage_f32": summary(stage[0]), "input_stage_u8": summary(stage[1]),
         "copy_only_f32": summary(stage[2]), "copy_only_u8": summary(stage[3]),
         "c5_step_f32": summary(steps[0]), "c5_step_u8": summary(steps[1]),
-        "note": "pinned host batch -> device; input stage = copy + normalise + m3t_planes_to_cl4 (float32 route) against copy + m3t_video_ingest "
+        "note": "pinned host batch -> device; input stage = copy + normalise + m3t_planes_to_cl4 (float32 route) against copy + %s "
                 "(uint8 route); c5_step = the same stage inside the AffWild2VA training step (training_step + backward + clip); routes run "
-                "alternately in one process, %d samples x %d calls (steps: %d x 3)" % (a.samples, a.inner, a.step_samples)}), flush=True)
+                "alternately in one process, %d samples x %d calls (steps: %d x 3)" % ("m3t_video_ingest_half" if a.input_size else "m3t_video_ingest", a.samples, a.inner, a.step_samples)}),
+        flush=True)
 
 
 if __name__ == "__main__":
