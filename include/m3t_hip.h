@@ -875,6 +875,37 @@ int m3t_video_ingest(const uint8_t* frames, int N, int Ts, int Hs, int Ws, const
 int m3t_video_ingest_half(const uint8_t* frames, int N, int Ts, int Hs, int Ws, const int* frame_idx, int T, const int* geom,
                           const float* lut, int lut_stride, int H, int W, int layout, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Window collate (csrc/collate.hip): the rest of the AffWild2 loader's __getitem__ (models/dataset.py:241-343 minus load_video) for a whole
+ * batch in ONE launch, from side tracks that live on the device (m3t.dataset.TrackStore uploads them once).
+ * The store: flat read-only arrays, one per track kind, the rows of the videos one after the other:
+ *     se [se_rows][se_stride], au [au_rows][au_stride], mel [mel_rows][n_mels], va [va_rows][2] float32; expr [expr_rows] long long.
+ * videos: device long long [n_videos][12] = se_off, se_n, au_off, au_n, mel_off, mel_n, va_off, va_n, expr_off, expr_n, flags, 0
+ *     (row offset and row count per kind; flags bit 0: the video has expression labels, bit 1: its audio is valid, fps >= 15).
+ * items:  device int [N][3] = video, start, track_len (1 <= track_len <= window) -- the only per-batch table.
+ * With i' = min(i, track_len - 1) (np.pad 'edge' up to `window`, dataset.py:308-319), for item n and i < window:
+ *     se_out [N][se_dim][window]       = se[se_off + min(start + i', se_n - 1)][c], c < se_dim <= se_stride   (a feature track shorter than
+ *                                        the window pads from its own last row, dataset.py:263-270); au_out the same over au_dim <= au_stride
+ *     audio_out [N][window][width n_mels] = m3t_stack_context_batch's: r = (start + i') step + k; r < mel_n ? mel[mel_off + r][c] : 0;
+ *                                        an audio-invalid video gives zeros (dataset.py:276-278)
+ *     valence_out, arousal_out [N][window] = va[va_off + start + i'][0 | 1], as stored
+ *     expr_out [N][window] (long long), expr_valid_out [N][window] (bytes 0 / 1): e = expr[expr_off + start + i']: valid = e >= 0,
+ *                                        out = min(max(e, 0), 6); a video without expression labels: 0 and 0   (dataset.py:285-291)
+ * Every output is optional (NULL; valence with arousal, expr with expr_valid) and every value is a copy: bit-exact, no atomics, no order.
+ * Indices are clamped on the device: start below 0 counts as 0, track_len is clamped into [1, window], a label row past the end reads
+ * the last row, a table entry that does not fit its array counts as an empty track (zeros), a video index outside [0, n_videos) writes
+ * zeros: no byte outside the arrays is read whatever the tables hold.  The host validates first (m3t.dataset.plan).
+ * Rows are read 16 bytes a lane where the stride is a multiple of 4 floats and the array 16-byte aligned, else by the float.
+ * M3T_EINVAL: null / misaligned pointers of a requested output's inputs (floats and ints 4 bytes, long long 8), dim > stride,
+ * non-positive sizes; N == 0 or window == 0 returns 0. */
+int m3t_window_collate(const float* se, long long se_rows, int se_stride, int se_dim,
+                       const float* au, long long au_rows, int au_stride, int au_dim,
+                       const float* mel, long long mel_rows, int n_mels, int step, int width,
+                       const float* va, long long va_rows, const long long* expr, long long expr_rows,
+                       const long long* videos, int n_videos, const int* items, int N, int window,
+                       float* se_out, float* au_out, float* audio_out, float* valence_out, float* arousal_out,
+                       long long* expr_out, unsigned char* expr_valid_out, void* stream);
+
 
 /* ---------------------------------------------------------------------------------
  * Attention decoder of --fusion_type att_dec (csrc/attdec.hip).  Replaces the decoder loop of AttEncDec.forward with

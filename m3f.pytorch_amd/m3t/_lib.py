@@ -163,6 +163,8 @@ SIGNATURES = {
     "m3t_stack_context_batch": [_f, C.c_longlong, _i, _f, _i, _i, _i, _i, _f, _s],
     "m3t_video_ingest": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],
     "m3t_video_ingest_half": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],
+    "m3t_window_collate": [_f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _i, _f, C.c_longlong, _f, C.c_longlong,
+                           _f, _i, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _s],
     "m3t_grad_norm_scale": [_f, _z, C.c_float, C.c_float, _f, _f, _z, _s],
     "m3t_grad_poison": [_f, _f, _s],
     "m3t_grad_dead_check": [_f, _s],
