@@ -876,6 +876,40 @@ int m3t_video_ingest_half(const uint8_t* frames, int N, int Ts, int Hs, int Ws, 
                           const float* lut, int lut_stride, int H, int W, int layout, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Batched baseline-JPEG decode (csrc/jpeg.hip, rules in csrc/jpeg_core.h): the first line of the reference's load_video
+ * (models/dataset.py:64, `cv2.imread` of one JPEG per frame) for a whole batch, writing the uint8 frames m3t_video_ingest takes.
+ * Streams: baseline sequential DCT (SOF0), 8 bits, Huffman, one interleaved scan, gray or YCbCr with luma 1x1 / 2x1 / 2x2 and chroma 1x1,
+ * optional restart intervals; all n images H x W.  The bits are libjpeg's: jpeg_idct_islow, "fancy" upsampling over the component's real
+ * size (replication where the chroma width is <= 2), jdcolor's 16-bit fixed-point colour.  m3t.jpeg.pack builds the arguments:
+ *   stream_d  device bytes: the entropy-coded data of every image, 16-byte aligned, stream_bytes a multiple of 16 (zero padded)
+ *   tables    ONE int array, given twice -- tables_h on the host (validated here, before any launch) and tables_d, the same ints on the
+ *             device (read by the kernels, which clamp what they index with):
+ *               images   [n][16]      flags (bit 0 present, bit 1 restart markers miscounted), components, luma h, luma v, MCUs per segment,
+ *                                     first segment, segments, quant table of each component [3], DC table [3], AC table [3]
+ *               segments [n_segs][4]  image, byte offset, byte length, restart marker in front (-1 first segment, -2 none found, 0..7);
+ *                                     segment k of an image holds its MCUs [k Ri, (k + 1) Ri): exactly ceil(MCUs / Ri) rows per image
+ *               slots    [n]          destination frame of each image, in [0, dst_slots)
+ *               quant    [n_quant][32]  64 uint16 in natural order
+ *               huff     [n_huff][384]  uint16 lut[512] (length << 8 | symbol for codes of <= 9 bits, else 0) | int maxcode[18] (-1: none) |
+ *                                     int valoff[18] (symbol index minus first code of the length) | uint8 symbols[256]
+ *   dst       device uint8 [dst_slots][H][W][3]; order 0 = b, g, r (what cv2.imread returns), 1 = r, g, b.  Only the n named frames are
+ *             written; an image that is not present writes zeros (the reference's `img is None`).
+ *   workspace device, 16-byte aligned, at least m3t_jpeg_workspace_bytes(n, H, W) (the component planes); contents undefined afterwards
+ *   status    device int [n], zeroed here and OR-ed by the kernels: M3T_JPEG_TRUNC | _CODE | _RST | _EXTRA.  A damaged segment keeps
+ *             decoding with zero bits or stops with zero coefficients; nothing outside the image's frame and workspace slot is written.
+ * Two launches on `stream` (one wave per segment: entropy decode + IDCT; then upsampling + colour), no host synchronisation.
+ * M3T_EINVAL: n <= 0, null or misaligned pointers, any table entry out of range (a segment outside the stream buffer, a slot outside
+ * dst, a table index past its count, an unsupported sampling, a segment count that does not match the MCU count), a short workspace. */
+#define M3T_JPEG_TRUNC 1     /* a segment ended before its MCUs did */
+#define M3T_JPEG_CODE 2      /* no such Huffman code, a coefficient past 63, a DC size above 15 */
+#define M3T_JPEG_RST 4       /* a restart marker missing, extra or out of order, or a marker inside a segment */
+#define M3T_JPEG_EXTRA 8     /* whole bytes left in a segment after its last MCU */
+size_t m3t_jpeg_workspace_bytes(int n, int H, int W);
+int m3t_jpeg_decode(const uint8_t* stream_d, long long stream_bytes, const int* tables_h, const int* tables_d, int n, int n_segs,
+                    int n_quant, int n_huff, int H, int W, uint8_t* dst, long long dst_slots, int order, uint8_t* workspace,
+                    long long workspace_bytes, int* status, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Window collate (csrc/collate.hip): the rest of the AffWild2 loader's __getitem__ (models/dataset.py:241-343 minus load_video) for a whole
  * batch in ONE launch, from side tracks that live on the device (m3t.dataset.TrackStore uploads them once).
  * The store: flat read-only arrays, one per track kind, the rows of the videos one after the other:

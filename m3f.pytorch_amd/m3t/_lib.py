@@ -21,6 +21,7 @@ M3T_SCAN_WHH = 8
 M3T_SCAN_FAULT = 16
 M3T_SCAN_WIDE = 32        # room for a second persistent scan beside this one (include/m3t_hip.h)
 M3T_MAX_SCANS = 8
+M3T_JPEG_TRUNC, M3T_JPEG_CODE, M3T_JPEG_RST, M3T_JPEG_EXTRA = 1, 2, 4, 8      # status bits of m3t_jpeg_decode (include/m3t_hip.h)
 
 _f = C.c_void_p      # device pointer
 _i = C.c_int
@@ -163,6 +164,8 @@ SIGNATURES = {
     "m3t_stack_context_batch": [_f, C.c_longlong, _i, _f, _i, _i, _i, _i, _f, _s],
     "m3t_video_ingest": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],
     "m3t_video_ingest_half": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],
+    "m3t_jpeg_workspace_bytes": [_i, _i, _i],
+    "m3t_jpeg_decode": [_f, C.c_longlong, C.c_void_p, _f, _i, _i, _i, _i, _i, _i, _f, C.c_longlong, _i, _f, C.c_longlong, _f, _s],
     "m3t_window_collate": [_f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _i, _f, C.c_longlong, _f, C.c_longlong,
                            _f, _i, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _s],
     "m3t_grad_norm_scale": [_f, _z, C.c_float, C.c_float, _f, _f, _z, _s],
@@ -197,7 +200,7 @@ SIGNATURES = {
 }
 
 RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_relu_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t,
-            "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t, "m3t_cls_loss_ws_bytes": C.c_size_t}
+            "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t, "m3t_cls_loss_ws_bytes": C.c_size_t, "m3t_jpeg_workspace_bytes": C.c_size_t}
 
 _lib = None
 
