@@ -909,6 +909,44 @@ int m3t_jpeg_decode(const uint8_t* stream_d, long long stream_bytes, const int* 
                     int n_quant, int n_huff, int H, int W, uint8_t* dst, long long dst_slots, int order, uint8_t* workspace,
                     long long workspace_bytes, int* status, void* stream);
 
+/* The same decode with a choice of how launch 1 walks a segment's symbols (the first line of models/dataset.py:64's load_video again:
+ * the dataset's files carry no restart markers, a frame is ONE segment, and one lane walking its 45 KB is what bounds m3t_jpeg_decode).
+ * Every argument up to `status` as m3t_jpeg_decode; the workspace is the same size.
+ *   walk           0: the sequential walk for every segment -- m3t_jpeg_decode, byte for byte.  1: per segment, the PARALLEL walk
+ *                  (jpeg_par_kernel, rules in csrc/jpeg_par.h) where par_min_bytes <= segment bytes <= min(par_max_bytes,
+ *                  m3t_jpeg_par_max_bytes()) and the segment has at most 4 096 blocks, the sequential walk elsewhere; both kernels are
+ *                  launched over all segments and each takes its own.  Any other value: M3T_EINVAL.
+ *   sub_bytes      the parallel walk's sub-sequence, a multiple of 16 in [16, 4096]; anything else M3T_EINVAL (whatever `walk` is)
+ *   par_min_bytes, par_max_bytes   >= 0, else M3T_EINVAL
+ *   walk_stats     NULL, or device int [n_segs][2], 4-byte aligned: (sub-sequences, exchange passes executed) of a segment the parallel walk
+ *                  took, 1 <= passes <= sub-sequences; (0, 0) of a segment it did not take
+ * The parallel walk: one workgroup per segment (m3t_jpeg_par_lanes lanes), no communication between workgroups, no spinning.  The segment
+ * is unstuffed into LDS; lane i walks sub-sequence i (sub_bytes of the unstuffed bytes) leniently from (its first bit, block 0, DC next);
+ * then every sub-sequence whose left neighbour's exit state changed is walked again from it, until none changes; a strict walk per
+ * sub-sequence records each block's first bit and DC difference; prefix sums give the predictors; one lane per block decodes, eight lanes per
+ * block transform.  Bounds of its loops, all from host-validated quantities: staging -- the segment's 16-byte granules; a lenient walk --
+ * 8 sub_bytes + 1 steps (each consumes a bit); the exchange -- `sub-sequences` passes (pass r makes the exit state of sub-sequence r true
+ * at the latest); closing a block begun in an earlier sub-sequence -- 4 096 steps; the strict walks -- the segment's blocks x 64 symbols,
+ * also for the last sub-sequence's lane, which carries on over the zero bits behind a truncated segment.  Every read of the stream lies
+ * inside the segment's granules, every read of the unstuffed image is checked against its word count, every write goes to the image's own
+ * planes in the workspace.
+ * Results: frames AND status words equal those of walk = 0 for every input, valid or damaged, whatever sub_bytes, the lane count or the
+ * neighbours in the batch.  Status of a parallel segment: the first strict error in block order raises M3T_JPEG_CODE and leaves every
+ * later block zero, as the sequential walk does; TRUNC where the walk consumed bits behind the last byte, EXTRA where 8 or more bits are
+ * left; a segment with a marker or a lone FF inside (damage; staging sees it wherever it lies, the sequential reader only if its
+ * look-ahead reaches it) has one lane repeat the sequential reader's walk for the status alone, so RST and EXTRA are that reader's.
+ * All validation happens before any launch.  M3T_EINVAL: as m3t_jpeg_decode, and the cases above.
+ * m3t_jpeg_par_max_bytes: the largest segment the parallel walk takes in this build (49 152: the unstuffed segment, the tables, the
+ * per-block records and the exchange states share the 160 KiB of LDS of one CU).
+ * m3t_jpeg_par_lanes(lanes): 64, 128 or 256 sets the workgroup size of later calls (process-wide; default 256) and returns it; 0 returns
+ * the current one; anything else returns -M3T_EINVAL.  Results do not depend on it. */
+int m3t_jpeg_decode_walk(const uint8_t* stream_d, long long stream_bytes, const int* tables_h, const int* tables_d, int n, int n_segs,
+                         int n_quant, int n_huff, int H, int W, uint8_t* dst, long long dst_slots, int order, uint8_t* workspace,
+                         long long workspace_bytes, int* status, int walk, int sub_bytes, int par_min_bytes, int par_max_bytes,
+                         int* walk_stats, void* stream);
+int m3t_jpeg_par_max_bytes(void);
+int m3t_jpeg_par_lanes(int lanes);
+
 /* ---------------------------------------------------------------------------------
  * Window collate (csrc/collate.hip): the rest of the AffWild2 loader's __getitem__ (models/dataset.py:241-343 minus load_video) for a whole
  * batch in ONE launch, from side tracks that live on the device (m3t.dataset.TrackStore uploads them once).

@@ -166,6 +166,10 @@ SIGNATURES = {
     "m3t_video_ingest_half": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],
     "m3t_jpeg_workspace_bytes": [_i, _i, _i],
     "m3t_jpeg_decode": [_f, C.c_longlong, C.c_void_p, _f, _i, _i, _i, _i, _i, _i, _f, C.c_longlong, _i, _f, C.c_longlong, _f, _s],
+    "m3t_jpeg_decode_walk": [_f, C.c_longlong, C.c_void_p, _f, _i, _i, _i, _i, _i, _i, _f, C.c_longlong, _i, _f, C.c_longlong, _f, _i, _i, _i, _i,
+                             _f, _s],
+    "m3t_jpeg_par_max_bytes": [],
+    "m3t_jpeg_par_lanes": [_i],
     "m3t_window_collate": [_f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _i, _f, C.c_longlong, _f, C.c_longlong,
                            _f, _i, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _s],
     "m3t_grad_norm_scale": [_f, _z, C.c_float, C.c_float, _f, _f, _z, _s],

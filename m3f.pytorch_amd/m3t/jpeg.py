@@ -9,6 +9,9 @@ later stage takes:
   pack         a flat list of files (bytes or None) -> JpegBatch: ONE byte buffer of scan data, the segment and image tables, the
                quantisation and Huffman tables deduplicated by content (a dataset batch carries two and four), the lookup form built here
   decode       JpegBatch -> (frames uint8 [n, H, W, 3] on the device, or into a caller's `out` at `slots`; status int32 [n] on the device)
+               walk="sequential": one lane walks a segment's symbols; walk="parallel": a workgroup walks it, every lane a sub-sequence
+               of `sub_bytes` (self-synchronising Huffman decoding, csrc/jpeg_par.h); walk="auto": by segment size, the thresholds
+               AUTO_MIN_BYTES / AUTO_SUB_BYTES below.  Both walks give the same frames and the same status for every input.
   load_clips   clips[n][t] of bytes / paths / None -> (frames [N, Ts, H, W, 3], present [N, Ts], status); `present` is what
                video.frame_index takes, an absent frame is zeros (the reference's `img is None`)
 
@@ -45,6 +48,15 @@ IMG_COLS, SEG_COLS, QUANT_INTS, HUFF_INTS, LUT_BITS = 16, 4, 32, 384, 9       # 
 MODES = {(1, 1, 1): "gray", (3, 1, 1): "444", (3, 2, 1): "422", (3, 2, 2): "420"}
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+
+
+WALKS = ("sequential", "parallel", "auto")
+# what walk="auto" does, chosen by measurement on the MI355X (NOTEBOOK section 16; tools/jpeg_bench.py --sweep --crossover prints the
+# tables): segments of at least AUTO_MIN_BYTES take the parallel walk with sub-sequences of AUTO_SUB_BYTES.  512 dataset frames (45 KB a
+# segment) decode in 2.8 ms instead of 24.1 and from 4 KB up the parallel walk won at every size measured; under 2 KB a segment the two
+# walks are within a third of each other with either sign.  (AUTO_MIN_BYTES = None would make "auto" sequential.)
+AUTO_MIN_BYTES = 4096
+AUTO_SUB_BYTES = 256
 
 
 class Unsupported(ValueError):
@@ -333,14 +345,52 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def decode(batch, out=None, slots=None, order="bgr"):
+def par_max_bytes():
+    """the largest segment (bytes) the parallel walk takes in this build; larger ones go to the sequential walk"""
+    return int(_lib.load().m3t_jpeg_par_max_bytes())
+
+
+def par_lanes(lanes=None):
+    """the workgroup size of the parallel walk (64, 128 or 256 lanes; results do not depend on it): set it, or read it with None"""
+    rc = int(_lib.load().m3t_jpeg_par_lanes(0 if lanes is None else int(lanes)))
+    if lanes is not None and (int(lanes) == 0 or rc < 0):
+        raise ValueError("jpeg.par_lanes: 64, 128 or 256")
+    return rc
+
+
+def _walk_args(walk, sub_bytes, par_min_bytes, par_max_bytes):
+    """-> the (walk, sub_bytes, par_min_bytes, par_max_bytes) ints of m3t_jpeg_decode_walk; ValueError for what it would refuse"""
+    if walk not in WALKS:
+        raise ValueError("jpeg.decode: walk must be one of %s" % ", ".join(repr(w) for w in WALKS))
+    if sub_bytes is None:
+        sub_bytes = AUTO_SUB_BYTES
+    if not (isinstance(sub_bytes, (int, np.integer)) and 16 <= sub_bytes <= 4096 and sub_bytes % 16 == 0):
+        raise ValueError("jpeg.decode: sub_bytes must be a multiple of 16 in [16, 4096]")
+    for name, v in (("par_min_bytes", par_min_bytes), ("par_max_bytes", par_max_bytes)):
+        if v is not None and not (isinstance(v, (int, np.integer)) and 0 <= v < 2 ** 31):
+            raise ValueError("jpeg.decode: %s must be a non-negative int" % name)
+    if walk == "sequential" or (walk == "auto" and AUTO_MIN_BYTES is None and par_min_bytes is None):
+        return 0, int(sub_bytes), 0, 0
+    if par_min_bytes is None:
+        par_min_bytes = 0 if walk == "parallel" else AUTO_MIN_BYTES
+    if par_max_bytes is None:
+        par_max_bytes = 2 ** 31 - 1
+    return 1, int(sub_bytes), int(par_min_bytes), int(par_max_bytes)
+
+
+def decode(batch, out=None, slots=None, order="bgr", walk="auto", sub_bytes=None, par_min_bytes=None, par_max_bytes=None, stats=False):
     """JpegBatch -> (frames, status).  out=None: frames is a new uint8 [n, H, W, 3] on the current device.  With `out`, a contiguous uint8
     device tensor [N, Ts, H, W, 3], and slots (n pairs (clip, frame), all different): image i goes to out[slots[i]], every other frame of
     `out` is left as it is, and frames is `out`.  An absent item writes zeros.  order: "bgr" (cv2.imread's) or "rgb".  status: int32 [n]
     on the device (0, or TRUNC | CODE | RST | EXTRA).  Everything runs on the current stream without a host synchronisation; the stream
-    bytes and the tables travel in one copy each."""
+    bytes and the tables travel in one copy each.
+    walk: "sequential" (every segment on one lane), "parallel" (every segment of par_min_bytes <= bytes <= min(par_max_bytes,
+    par_max_bytes()) by a workgroup in sub-sequences of sub_bytes, the rest sequentially; par_min_bytes defaults to 0) or "auto" (the
+    same routing with the measured defaults: par_min_bytes = AUTO_MIN_BYTES, sub_bytes = AUTO_SUB_BYTES).  Frames and status do not depend on any of it.  stats=True: -> (frames, status, walk_stats), the last an int32
+    [n_segs, 2] device tensor: (sub-sequences, exchange passes) of a segment the parallel walk took, (0, 0) of any other."""
     if order not in ("bgr", "rgb"):
         raise ValueError("jpeg.decode: order must be 'bgr' or 'rgb'")
+    walk_i, sub_i, min_i, max_i = _walk_args(walk, sub_bytes, par_min_bytes, par_max_bytes)
     if not isinstance(batch, JpegBatch):
         raise ValueError("jpeg.decode: batch must be a JpegBatch (jpeg.pack)")
     n, H, W = batch.n, batch.height, batch.width
@@ -378,10 +428,12 @@ def decode(batch, out=None, slots=None, order="bgr"):
         ws_bytes = int(lib.m3t_jpeg_workspace_bytes(n, H, W))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        _lib.check(lib.m3t_jpeg_decode(s_d.data_ptr(), s_d.numel(), tables.ctypes.data, t_d.data_ptr(), n, batch.n_segs, batch.n_quant,
-                                       batch.n_huff, H, W, out.data_ptr(), dst_slots, 0 if order == "bgr" else 1, ws.data_ptr(), ws_bytes,
-                                       status.data_ptr(), _stream()), "m3t_jpeg_decode")
-    return out, status
+        walk_stats = torch.empty(batch.n_segs, 2, dtype=torch.int32, device=dev) if stats else None
+        _lib.check(lib.m3t_jpeg_decode_walk(s_d.data_ptr(), s_d.numel(), tables.ctypes.data, t_d.data_ptr(), n, batch.n_segs, batch.n_quant,
+                                            batch.n_huff, H, W, out.data_ptr(), dst_slots, 0 if order == "bgr" else 1, ws.data_ptr(), ws_bytes,
+                                            status.data_ptr(), walk_i, sub_i, min_i, max_i,
+                                            walk_stats.data_ptr() if stats and batch.n_segs else None, _stream()), "m3t_jpeg_decode_walk")
+    return (out, status, walk_stats) if stats else (out, status)
 
 
 def _read(item):
@@ -394,11 +446,11 @@ def _read(item):
         return None                                     # the reference's `img is None`
 
 
-def load_clips(clips, order="bgr", threads=8, pin=False):
+def load_clips(clips, order="bgr", threads=8, pin=False, walk="auto", sub_bytes=None):
     """clips[n][t]: bytes, a path, or None, every clip of one length Ts -> (frames uint8 [N, Ts, H, W, 3] on the device, present bool
     [N, Ts] (numpy), status int32 [N Ts] on the device, clip-major).  A None entry or a file that does not exist is absent: present is
     False and its frame zero -- what video.frame_index(present[n], ...) then routes around (dataset.py:64-68).  Files are read by a
-    small thread pool (at most 16 threads)."""
+    small thread pool (at most 16 threads).  walk, sub_bytes: decode's."""
     clips = [list(c) for c in clips]
     if not clips or not clips[0] or any(len(c) != len(clips[0]) for c in clips):
         raise ValueError("jpeg.load_clips: clips must be a non-empty list of equally long lists")
@@ -410,5 +462,5 @@ def load_clips(clips, order="bgr", threads=8, pin=False):
     else:
         flat = [_read(it) for it in flat]
     batch = pack(flat, pin=pin)
-    frames, status = decode(batch, order=order)
+    frames, status = decode(batch, order=order, walk=walk, sub_bytes=sub_bytes)
     return frames.view(N, Ts, batch.height, batch.width, 3), batch.present.reshape(N, Ts), status
