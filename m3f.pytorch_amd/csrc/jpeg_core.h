@@ -1,18 +1,22 @@
 // Baseline-JPEG decoding, the sequential rules as host + device inline functions (include/m3t_hip.h, m3t_jpeg_decode): the bit reader
 // with unstuffing, the Huffman lookup, one block's entropy decode, libjpeg's integer IDCT (jidctint.c, jpeg_idct_islow), its "fancy"
-// chroma upsampling (jdsample.c) and its colour conversion (jdcolor.c).  csrc/jpeg.hip runs this text on the GPU; the stand-alone
-// program csrc/jpeg_host_check.cpp compiles the same text for the host, which is how it is tested without one.
+// chroma upsampling (jdsample.c) and its colour conversion (jdcolor.c); and what every walk of a segment begins and ends with: the
+// segment resolved from the tables (jpeg_segment_resolve), its tables where the walk reads them, its status.  csrc/jpeg.hip runs this
+// text on the GPU; the stand-alone program csrc/jpeg_host_check.cpp compiles the same text for the host, which is how it is tested
+// without one.
 // Rules of this file: every read of the stream is bounded by the segment's end (past it the reader supplies zero bits and the status
 // says so), every coefficient index is checked to be < 64, a Huffman miss raises the status and ends the segment, and nothing here
-// writes anywhere but into the caller's coefficient block.  All arithmetic is 32-bit and wraps (unsigned) where a damaged stream could
+// writes anywhere but into the caller's coefficient block, table copies and plane rows.  All arithmetic is 32-bit and wraps (unsigned) where a damaged stream could
 // overflow, so host and device agree on every input.
 #pragma once
 #include <stdint.h>
 
 #if defined(__HIPCC__)
 #define JPEG_HD __host__ __device__ __forceinline__
+#define JPEG_UNROLL _Pragma("unroll")
 #else
 #define JPEG_HD inline
+#define JPEG_UNROLL
 #endif
 
 // status bits of one image (M3T_JPEG_* of include/m3t_hip.h)
@@ -136,7 +140,7 @@ JPEG_HD int jpeg_symbol(JpegReader& r, const JpegHuff& h) {
 }
 
 // One block: coef[64] (natural order, zero-filled by the caller) receives the DC and the AC values; `pred` is the component's DC
-// predictor.  Returns 0, or a status that ends the segment.  store = false: walk the symbols without writing (not used on the device).
+// predictor.  Returns 0, or a status that ends the segment.  store = false: walk the symbols without writing (jpeg_segment_status).
 JPEG_HD int jpeg_decode_block(JpegReader& r, const JpegHuff& dc, const JpegHuff& ac, const uint8_t* zz, int& pred, int16_t* coef, bool store) {
     int s = jpeg_symbol(r, dc);
     if (s < 0 || s > 15) return JPEG_ST_CODE;
@@ -253,6 +257,105 @@ JPEG_HD void jpeg_block_place(const JpegGeom& g, int m, int b, int& comp, int& y
         comp = b - ny + 1;
         y0 = my * 8; x0 = mx * 8;
     }
+}
+
+// sample (y, x) of component comp in the slot, without an index into g's arrays (a JpegGeom indexed by a variable lives in scratch)
+JPEG_HD long long jpeg_plane_offset(const JpegGeom& g, int comp, int y, int x) {
+    return comp * g.plane[1] + (long long)y * (comp ? g.stride[1] : g.stride[0]) + x;
+}
+
+// ---- one entropy-coded segment: what it is, its tables, its status ------------------------------------------------------------------------
+// aligned 16-byte load and 8-byte store as the device issues them (one instruction) and the host may (no type is punned)
+JPEG_HD void jpeg_load16(const uint8_t* p, uint32_t w[4]) { __builtin_memcpy(w, __builtin_assume_aligned(p, 16), 16); }
+JPEG_HD void jpeg_store8(uint8_t* p, uint32_t lo, uint32_t hi) {
+    const uint32_t w[2] = {lo, hi};
+    __builtin_memcpy(__builtin_assume_aligned(p, 8), w, 8);
+}
+
+JPEG_HD int jpeg_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+struct JpegSegment {
+    bool live;                       // false: nothing to decode (an index outside the tables, an absent image); nothing else is set then
+    int i, k, Ri, m0, m1;            // the image, the segment's number in it, the restart interval, its MCUs [m0, m1)
+    int bytes, mark;                 // the table's byte length (what the routing rule reads) and restart marker in front
+    long long off, end;              // its bytes in the stream, clamped to it
+    int im[JPEG_IMG_COLS];           // the image's row, components and sampling factors normalised
+    JpegGeom g;
+};
+
+// Segment s of the tables.  The host validated them; the clamps change nothing then and keep every later index inside its table.
+JPEG_HD JpegSegment jpeg_segment_resolve(const int* img, const int* seg, int s, int n, int H, int W, long long stream_bytes) {
+    JpegSegment S = {};
+    const int* sg = seg + (long long)JPEG_SEG_COLS * s;
+    S.i = sg[0];
+    if (S.i < 0 || S.i >= n) return S;
+    const int* row = img + (long long)JPEG_IMG_COLS * S.i;
+    if (!(row[0] & 1)) return S;
+    JPEG_UNROLL
+    for (int c = 0; c < JPEG_IMG_COLS; ++c) S.im[c] = row[c];
+    S.im[1] = S.im[1] == 1 ? 1 : 3;
+    S.im[2] = S.im[1] == 1 ? 1 : jpeg_clampi(S.im[2], 1, 2);
+    S.im[3] = S.im[1] == 1 ? 1 : jpeg_clampi(S.im[3], 1, 2);
+    S.g = jpeg_geom(S.im, H, W);
+    const int total = S.g.mcus_x * S.g.mcus_y;
+    S.Ri = jpeg_clampi(S.im[4], 1, total);
+    S.k = s - S.im[5];
+    if (S.k < 0 || (long long)S.k * S.Ri >= total) return S;
+    S.m0 = S.k * S.Ri; S.m1 = S.m0 + S.Ri < total ? S.m0 + S.Ri : total;
+    S.bytes = sg[2]; S.mark = sg[3];
+    const long long o = sg[1] < 0 ? 0 : sg[1], len = sg[2] < 0 ? 0 : sg[2];
+    S.off = o < stream_bytes ? o : stream_bytes;
+    S.end = S.off + len < stream_bytes ? S.off + len : stream_bytes;
+    S.live = true;
+    return S;
+}
+
+// what the tables alone say of a segment: its restart marker is not the one its number asks for, or the packer saw the markers disagree
+JPEG_HD int jpeg_segment_rst(const JpegSegment& S) {
+    return ((S.k > 0 && S.mark != ((S.k - 1) & 7)) || (S.im[0] & 2)) ? JPEG_ST_RST : 0;
+}
+
+// Lane t of T copies the image's tables to where the walk reads them: huff = DC, AC of component 0, 1, .. in lookup form, quant beside
+// it, for nc components (behind the image's last one: copies of component 0's, so that every read finds initialised memory).
+JPEG_HD void jpeg_tables_load(int* huff, int* quant, const JpegSegment& S, int nc, const int* huff_t, int n_huff, const int* quant_t, int n_quant,
+                              int t, int T) {
+    JPEG_UNROLL
+    for (int c = 0; c < 3; ++c) {                            // (unrolled: the row is read at constant indices and stays in registers)
+        if (c >= nc) break;
+        const bool own = c < S.g.ncomp;
+        const int* hd = huff_t + (long long)JPEG_HUFF_INTS * jpeg_clampi(own ? S.im[10 + c] : S.im[10], 0, n_huff - 1);
+        const int* ha = huff_t + (long long)JPEG_HUFF_INTS * jpeg_clampi(own ? S.im[13 + c] : S.im[13], 0, n_huff - 1);
+        const int* q = quant_t + (long long)JPEG_QUANT_INTS * jpeg_clampi(own ? S.im[7 + c] : S.im[7], 0, n_quant - 1);
+        for (int j = t; j < JPEG_HUFF_INTS; j += T) {
+            __builtin_memcpy(huff + (2 * c) * JPEG_HUFF_INTS + j, hd + j, 4);                 // (read as uint16 and uint8 later)
+            __builtin_memcpy(huff + (2 * c + 1) * JPEG_HUFF_INTS + j, ha + j, 4);
+        }
+        for (int j = t; j < JPEG_QUANT_INTS; j += T) __builtin_memcpy(quant + c * JPEG_QUANT_INTS + j, q + j, 4);
+    }
+}
+
+// the blocks of MCU m through the reader; coef: blocks x 64, zero-filled by the caller, unread with store = false.  False: a status ended
+// the segment (it is in r.status).
+JPEG_HD bool jpeg_walk_mcu(JpegReader& r, const JpegGeom& g, int m, const int* huff, const uint8_t* zz, int pred[3], int16_t* coef, bool store) {
+    for (int b = 0; b < g.blocks; ++b) {
+        int comp, y0, x0;
+        jpeg_block_place(g, m, b, comp, y0, x0);
+        const JpegHuff hd = jpeg_huff_at(huff + (2 * comp) * JPEG_HUFF_INTS), ha = jpeg_huff_at(huff + (2 * comp + 1) * JPEG_HUFF_INTS);
+        const int st = jpeg_decode_block(r, hd, ha, zz, pred[comp], store ? coef + 64 * b : nullptr, store);
+        if (st) { r.status |= st; return false; }
+    }
+    return true;
+}
+
+// The sequential reader's walk of a segment straight from the stream, for the status alone (nothing is stored): what that reader says of
+// a marker inside depends on how far its look-ahead got, so a walk that reads another way asks it.  huff: as jpeg_tables_load leaves it.
+JPEG_HD int jpeg_segment_status(const uint8_t* stream, long long stream_bytes, const JpegSegment& S, const int* huff, const uint8_t* zz) {
+    JpegReader r;
+    jpeg_reader_init(r, stream, 0, (int)(stream_bytes < 0x7fffffffll ? stream_bytes : 0x7fffffffll), (int)S.off, (int)S.end);
+    int pred[3] = {0, 0, 0};
+    bool dead = false;
+    for (int m = S.m0; m < S.m1 && !dead; ++m) dead = !jpeg_walk_mcu(r, S.g, m, huff, zz, pred, nullptr, false);
+    return r.status | (dead ? 0 : jpeg_segment_tail(r)) | jpeg_segment_rst(S);
 }
 
 // ---- fancy upsampling (jdsample.c) and colour (jdcolor.c) ---------------------------------------------------------------------------

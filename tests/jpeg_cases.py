@@ -1,6 +1,7 @@
-"""The JPEG fixtures and the damaged streams shared by tests/test_jpeg_host.py and tests/test_gpu_jpeg.py (tests/golden/jpeg_cases.npz, written
-by tests/golden/gen_golden_jpeg.py), the packed-batch file csrc/jpeg_host_check.cpp reads, and the rule both tests hold a damaged stream's
-result to."""
+"""The JPEG fixtures and the damaged streams shared by tests/test_jpeg_host.py, tests/test_jpeg_par_host.py and tests/test_gpu_jpeg*.py
+(tests/golden/jpeg_cases.npz, written by tests/golden/gen_golden_jpeg.py), the packed-batch file csrc/jpeg_host_check.cpp -- the one host
+program, which runs the kernels' text for both walks, the workgroup's schedule included -- reads, and the rule the tests hold a damaged
+stream's result to."""
 import functools
 import struct
 

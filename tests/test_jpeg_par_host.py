@@ -1,5 +1,6 @@
-"""The parallel walk of the JPEG decode without a GPU: csrc/jpeg_par.h compiled for the host by csrc/jpeg_par_host_check.cpp, which emulates the
-workgroup of jpeg_par_kernel lane by lane.  Every golden of both fixture files bit for bit at three sub-sequence sizes and two lane
+"""The parallel walk of the JPEG decode without a GPU: csrc/jpeg_par.h compiled for the host by csrc/jpeg_host_check.cpp (its seven-argument
+form), which calls the phases of jpeg_par_kernel -- the same functions, on the kernel's own data layout -- for one lane after the other.
+Every golden of both fixture files bit for bit at three sub-sequence sizes and two lane
 counts, the fixed-seed damaged streams against the sequential walk of the same program (frames AND status words equal: a segment with a
 marker inside takes its status from the sequential reader, so the walks never differ, not even in the RST bit), guard bytes around
 everything the emulated workgroup writes, the refusals, and the same program under the address and undefined-behaviour sanitizers."""
@@ -40,8 +41,8 @@ def by_size():
 
 
 def _build(tmp_path_factory, flags):
-    exe = str(tmp_path_factory.mktemp("jpeg_par") / "jpeg_par_host_check")
-    subprocess.check_call(["g++"] + flags + [os.path.join(_lib.CSRC_DIR, "jpeg_par_host_check.cpp"), "-o", exe])
+    exe = str(tmp_path_factory.mktemp("jpeg_par") / "jpeg_host_check")
+    subprocess.check_call(["g++"] + flags + [os.path.join(_lib.CSRC_DIR, "jpeg_host_check.cpp"), "-o", exe])
     return exe
 
 
