@@ -501,6 +501,35 @@ int m3t_pool_cl_fwd(const float* x, size_t P, int H, int W, int C, int kh, int k
 int m3t_pool_cl_bwd(const float* dy, const unsigned char* win, size_t P, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                     float* dx, void* stream);
 
+/* GroupNorm on the channels-last chain (csrc/gn_cl.hip; reference models/backbone.py:63-103,165-271 with norm_layer='gn': Conv3d ->
+ * GroupNorm(32, C) -> ReLU (-> MaxPool3d((1, 2, 2)))).  Rows x [N][R][C], R = T H W rows per clip; semantics of F.group_norm(x5d, G, gamma, beta,
+ * eps) on [N, C, T, H, W]: one mean and one biased variance per (clip, group) over (C / G) R values -- no running statistics, train == eval.
+ * C % 4 == 0 and C / 4 divides 256 (as m3t_bn_cl_*), G divides C (C / G may be below 4: a thread's four channels then straddle two groups),
+ * 1 <= N <= 65535, 16-B aligned tensors, ws of m3t_gn_cl_ws_bytes(N, R, C) bytes, 8-B aligned.  A refused call (M3T_EINVAL) launches nothing.
+ * Statistics: fp64 sums per (clip, chunk, channel), a chunk never crosses a clip, chunks then the group's channels folded in a fixed order;
+ * save_mean / save_rstd [N G], rstd = 1 / sqrt(max(var, 0) + eps).  No float atomics: reruns are bit-identical.
+ * m3t_gn_cl_fwd: y = (x - mean) rstd gamma + beta, with `relu` as torch.relu (NaN stays NaN).  gamma / beta NULL: 1 / 0.
+ * m3t_gn_cl_bwd: g = dy (0 where y <= 0 if relu); per (clip, group), M = (C / G) R: s1 = sum gamma_c g, s2 = sum gamma_c g xhat,
+ *   dx = rstd (gamma_c g - s1 / M - xhat s2 / M); dgamma_c = sum_{n,r} g xhat, dbeta_c = sum_{n,r} g (fp64, clips in order; either may be
+ *   NULL).  dx_colsum [C] (optional): the column sums of dx -- under GroupNorm the bias gradient of the convolution in front is NOT zero by
+ *   construction -- from the dx pass itself (fp64 per thread, per block, then over the blocks in order).
+ * m3t_gn_pool_cl_fwd / _bwd: GroupNorm + ReLU + max pooling with a k x k window, stride k, no padding (k = 2, 3; H, W >= k) as ONE operator
+ *   over x [N T][H][W][C]: relu(gn(x)) at full resolution is neither written nor read.  yp [N T][H / k][W / k][C] and one winner byte per element
+ *   (ties: the first maximum in window order, NaN wins); positions no window covers (odd H or W) count in the statistics and get the
+ *   GroupNorm terms of dx only.  The per-element map is the one of m3t_gn_cl_fwd: the same bits.
+ * m3t_amax_out arms the magnitude slot of y / yp (forward) and of dx (backward): the largest finite magnitude. */
+size_t m3t_gn_cl_ws_bytes(int N, size_t R, int C);
+int m3t_gn_cl_fwd(const float* x, int N, size_t R, int C, int G, const float* gamma, const float* beta, float eps, int relu, float* y,
+                  float* save_mean, float* save_rstd, float* ws, size_t ws_bytes, void* stream);
+int m3t_gn_cl_bwd(const float* dy, const float* x, const float* y, const float* gamma, const float* save_mean, const float* save_rstd, int N,
+                  size_t R, int C, int G, int relu, float* dx, float* dgamma, float* dbeta, float* dx_colsum, float* ws, size_t ws_bytes,
+                  void* stream);
+int m3t_gn_pool_cl_fwd(const float* x, int N, int T, int H, int W, int C, int G, int k, const float* gamma, const float* beta, float eps,
+                       float* yp, unsigned char* win, float* save_mean, float* save_rstd, float* ws, size_t ws_bytes, void* stream);
+int m3t_gn_pool_cl_bwd(const float* dyp, const float* x, const float* yp, const unsigned char* win, const float* gamma, const float* save_mean,
+                       const float* save_rstd, int N, int T, int H, int W, int C, int G, int k, float* dx, float* dgamma, float* dbeta,
+                       float* dx_colsum, float* ws, size_t ws_bytes, void* stream);
+
 /* Channels-last operators of the VGGFace front-end (csrc/vggface.hip; reference models/vggface.py:45-50: `x = F.relu(c(x))` after every Conv2d,
  * `F.max_pool2d(x, 2, 2, 0, ceil_mode=True)` at the end of every block).  C % 4 == 0, C <= 1024 (C / 4 need not divide the block), 16-B aligned
  * tensors, any number of rows; a refused call (M3T_EINVAL: C % 4 != 0, H < 1, W < 1, a misaligned pointer, a short workspace) launches nothing.

@@ -110,6 +110,11 @@ SIGNATURES = {
     "m3t_bn_pool_cl_bwd": [_f, _f, _f, C.c_void_p, _f, _f, _f, _z, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _z, _s],
     "m3t_pool_cl_fwd": [_f, _z, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, C.c_void_p, _s],
     "m3t_pool_cl_bwd": [_f, C.c_void_p, _z, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _s],
+    "m3t_gn_cl_ws_bytes": [_i, _z, _i],
+    "m3t_gn_cl_fwd": [_f, _i, _z, _i, _i, _f, _f, C.c_float, _i, _f, _f, _f, _f, _z, _s],
+    "m3t_gn_cl_bwd": [_f, _f, _f, _f, _f, _f, _i, _z, _i, _i, _i, _f, _f, _f, _f, _f, _z, _s],
+    "m3t_gn_pool_cl_fwd": [_f, _i, _i, _i, _i, _i, _i, _i, _f, _f, C.c_float, _f, C.c_void_p, _f, _f, _f, _z, _s],
+    "m3t_gn_pool_cl_bwd": [_f, _f, _f, C.c_void_p, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _z, _s],
     "m3t_relu_cl_ws_bytes": [_z, _i],
     "m3t_relu_cl_fwd": [_f, _z, _i, _f, _s],
     "m3t_relu_cl_bwd": [_f, _f, _z, _i, _f, _f, _f, _z, _s],
@@ -203,7 +208,7 @@ SIGNATURES = {
     "m3t_tpool_cls_loss": [_f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _z, _s],
 }
 
-RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_relu_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t,
+RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_gn_cl_ws_bytes": C.c_size_t, "m3t_relu_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t,
             "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t, "m3t_cls_loss_ws_bytes": C.c_size_t, "m3t_jpeg_workspace_bytes": C.c_size_t}
 
 _lib = None

@@ -3150,9 +3150,10 @@ STEM_CL = [os.environ.get("M3T_STEM_CL", "1") != "0"]
 
 class CLTensor:
     """a channels-last activation of a 3-D stem: `data` [N T H W, C] (a plain autograd tensor) + its grid; `slot`: the 1-element tensor
-    holding data's magnitude slot (raised by the kernel that wrote data) or None.  A BatchNorm3d + ReLU may be PENDING on it (bn_cl(...,
-    lazy=True)): a pooling that follows applies it inside its own window loop (pool_cl: one fused operator, relu(bn(x)) at full resolution is
-    never written); anything else that touches `.data` applies it first."""
+    holding data's magnitude slot (raised by the kernel that wrote data) or None.  A BatchNorm3d + ReLU or a GroupNorm + ReLU may be PENDING on
+    it (bn_cl / gn_cl(..., lazy=True); the record is (kind, arguments) with kind "bn" or "gn"): a pooling that follows applies it inside its own
+    window loop (pool_cl: one fused operator, relu(norm(x)) at full resolution is never written); anything else that touches `.data` applies it
+    first."""
     __slots__ = ("_data", "N", "T", "H", "W", "_slot", "_pending")
 
     def __init__(self, data, N, T, H, W, slot=None, pending=None):
@@ -3160,9 +3161,12 @@ class CLTensor:
 
     def _materialize(self):
         if self._pending is not None:
-            args, self._pending = self._pending, None
+            (kind, args), self._pending = self._pending, None
             self._slot = amax_slots(1, self._data.device)
-            self._data = _BNCL.apply(self._data, *args, self._slot)
+            if kind == "gn":
+                self._data = _GNCL.apply(self._data, *args, True, (self.N, self.T * self.H * self.W), self._slot)
+            else:
+                self._data = _BNCL.apply(self._data, *args, self._slot)
 
     @property
     def data(self):
@@ -3496,7 +3500,7 @@ class _BNCL(torch.autograd.Function):
 def bn_cl(x, gamma, beta, run_mean, run_var, training, momentum, eps, relu=True, lazy=False):
     """lazy (with relu): the operator is left PENDING on the result -- a pooling with tiling windows that follows fuses it (pool_cl)"""
     if lazy and relu and BN_POOL_FUSED[0]:
-        return CLTensor(x.data, x.N, x.T, x.H, x.W, None, (gamma, beta, run_mean, run_var, training, momentum, eps, True))
+        return CLTensor(x.data, x.N, x.T, x.H, x.W, None, ("bn", (gamma, beta, run_mean, run_var, training, momentum, eps, True)))
     slot = amax_slots(1, x.data.device)
     y = _BNCL.apply(x.data, gamma, beta, run_mean, run_var, training, momentum, eps, relu, slot)
     return CLTensor(y, x.N, x.T, x.H, x.W, slot)
@@ -3599,14 +3603,158 @@ def pool_cl(x, k, s, p):
     k, s, p = tuple(k), tuple(s), tuple(p)
     pend = x._pending
     if pend is not None and k == s and p == (0, 0) and k[0] == k[1] and k[0] in (2, 3) and x.H >= k[0] and x.W >= k[0]:
-        gamma, beta, run_mean, run_var, training, momentum, eps, _ = pend
+        kind, args = pend
         slot = amax_slots(1, x._data.device)
-        y = _BNPoolCL.apply(x._data, gamma, beta, run_mean, run_var, training, momentum, eps, (x.N * x.T, x.H, x.W, k[0]), slot)
+        if kind == "gn":
+            G, gamma, beta, eps = args
+            y = _GNPoolCL.apply(x._data, G, gamma, beta, eps, (x.N, x.T, x.H, x.W, k[0]), slot)
+        else:
+            gamma, beta, run_mean, run_var, training, momentum, eps, _ = args
+            y = _BNPoolCL.apply(x._data, gamma, beta, run_mean, run_var, training, momentum, eps, (x.N * x.T, x.H, x.W, k[0]), slot)
         return CLTensor(y, x.N, x.T, x.H // k[0], x.W // k[0], slot)
     slot = amax_slots(1, x.data.device)
     y = _PoolCL.apply(x.data, (x.N * x.T, x.H, x.W, k, s, p), slot)
     Ho, Wo = (x.H + 2 * p[0] - k[0]) // s[0] + 1, (x.W + 2 * p[1] - k[1]) // s[1] + 1
     return CLTensor(y, x.N, x.T, Ho, Wo, slot)
+
+
+# ----------------------------------------------------------------------------- GroupNorm on the chain (norm_layer='gn')
+# Reference models/backbone.py:63-103,165-271 with norm_layer='gn': nn.GroupNorm(32, C) -> ReLU (-> MaxPool3d((1, 2, 2))).  csrc/gn_cl.hip:
+# statistics per (clip, group), no running statistics.  M3T_GN_CL=1 puts the 'gn' stems on the chain; the default, 0, keeps them on planes
+# with the stock GroupNorm (the route of every round before this operator): the chain is the faster and the more accurate of the two
+# (NOTEBOOK section 18), but on the second fixed video of tests/test_gpu_frontends_fp64.py case vggm_gn its rounding takes a pooling decision of
+# the second layer the other way (two window values 2e-6 apart), and that yardstick's videos are not ours to change.  The switch is read
+# when a model is BUILT (models.backbone._vgg_group) and when it runs.
+GN_CL = [os.environ.get("M3T_GN_CL", "0") == "1"]
+
+
+def gn_cl_ok(x, G):
+    """the GroupNorm kernels cover this CLTensor: C % 4 == 0, C / 4 divides 256, G divides C"""
+    Cc = x.C
+    return bool(GN_CL[0] and G > 0 and Cc % 4 == 0 and Cc <= 1024 and 256 % (Cc // 4) == 0 and Cc % G == 0 and 1 <= x.N <= 65535)
+
+
+def _gn_sinks(ctx, gamma, beta):
+    ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
+                     beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
+
+
+class _GNCL(torch.autograd.Function):
+    """GroupNorm (+ReLU) over channels-last rows [N R, C] (csrc/gn_cl.hip m3t_gn_cl_*); y's and dx's magnitude slots are raised by the kernels,
+    dx's column sums (the bias gradient of the convolution in front) come from the dx pass"""
+
+    @staticmethod
+    def forward(ctx, x, G, gamma, beta, eps, relu, geo, y_slot):
+        N_, R = geo
+        x = _req(x, "x")
+        Cc = x.shape[1]
+        y = torch.empty_like(x)
+        stats = torch.empty(2, N_ * G, dtype=torch.float32, device=x.device)
+        ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, R, Cc)))
+        amax_out(y_slot.data_ptr() if y_slot is not None else None)
+        try:
+            rc = lib().m3t_gn_cl_fwd(_p(x), N_, R, Cc, G, _p(gamma), _p(beta), float(eps), int(relu), _p(y), _p(stats[0]), _p(stats[1]), _p(ws),
+                                     ws.numel() * 4, _stream())
+            _lib.check(rc, "m3t_gn_cl_fwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        ctx.save_for_backward(x, y if relu else None, gamma, stats)
+        ctx.geo, ctx.G, ctx.relu = geo, G, bool(relu)
+        _gn_sinks(ctx, gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, gamma, stats = ctx.saved_tensors
+        N_, R = ctx.geo
+        dy = _req(dy.contiguous(), "dy")
+        Cc = x.shape[1]
+        dx = torch.empty_like(x)
+        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, R, Cc)))
+        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[2] and ctx.sink_refs[0] is not None) else None
+        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[3] and ctx.sink_refs[1] is not None) else None
+        slot = amax_slots(1, x.device)
+        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        amax_out(slot.data_ptr())
+        try:
+            rc = lib().m3t_gn_cl_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), N_, R, Cc, ctx.G, int(ctx.relu), _p(dx),
+                                     _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]), _p(csum), _p(ws), ws.numel() * 4,
+                                     _stream())
+            _lib.check(rc, "m3t_gn_cl_bwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        # the convolution in front of this GroupNorm takes dx as its dy: its magnitude slot and its column sums (that layer's bias gradient) ride along
+        _note_grad_slot(dx, slot, csum)
+        return (dx, None, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
+                None, None, None, None)
+
+
+class _GNPoolCL(torch.autograd.Function):
+    """GroupNorm + ReLU + MaxPool3d((1, k, k), stride (1, k, k)) on channels-last frames as one operator (csrc/gn_cl.hip m3t_gn_pool_cl_*):
+    relu(gn(x)) at full resolution is neither written nor read, forward or backward"""
+
+    @staticmethod
+    def forward(ctx, x, G, gamma, beta, eps, geo, y_slot):
+        N_, T_, H, W, k = geo
+        x = _req(x, "x")
+        Cc = x.shape[1]
+        Ho, Wo = H // k, W // k
+        yp = torch.empty(N_ * T_ * Ho * Wo, Cc, dtype=torch.float32, device=x.device)
+        win = torch.empty(N_ * T_ * Ho * Wo, Cc, dtype=torch.uint8, device=x.device)
+        stats = torch.empty(2, N_ * G, dtype=torch.float32, device=x.device)
+        ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, T_ * H * W, Cc)))
+        amax_out(y_slot.data_ptr() if y_slot is not None else None)
+        try:
+            rc = lib().m3t_gn_pool_cl_fwd(_p(x), N_, T_, H, W, Cc, G, k, _p(gamma), _p(beta), float(eps), _p(yp), C.c_void_p(win.data_ptr()),
+                                          _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
+            _lib.check(rc, "m3t_gn_pool_cl_fwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        ctx.save_for_backward(x, yp, win, gamma, stats)
+        ctx.geo, ctx.G = geo, G
+        _gn_sinks(ctx, gamma, beta)
+        return yp
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, yp, win, gamma, stats = ctx.saved_tensors
+        N_, T_, H, W, k = ctx.geo
+        dy = _req(dy.contiguous(), "dy")
+        Cc = x.shape[1]
+        dx = torch.empty_like(x)
+        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, T_ * H * W, Cc)))
+        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[2] and ctx.sink_refs[0] is not None) else None
+        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[3] and ctx.sink_refs[1] is not None) else None
+        slot = amax_slots(1, x.device)
+        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        amax_out(slot.data_ptr())
+        try:
+            rc = lib().m3t_gn_pool_cl_bwd(_p(dy), _p(x), _p(yp), C.c_void_p(win.data_ptr()), _p(gamma), _p(stats[0]), _p(stats[1]), N_, T_, H, W,
+                                          Cc, ctx.G, k, _p(dx), _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]),
+                                          _p(csum), _p(ws), ws.numel() * 4, _stream())
+            _lib.check(rc, "m3t_gn_pool_cl_bwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        _note_grad_slot(dx, slot, csum)
+        return (dx, None, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
+                None, None, None)
+
+
+def gn_cl(x, G, gamma, beta, eps, relu=True, lazy=False):
+    """GroupNorm(G) (+ReLU) of a CLTensor.  lazy (with relu): the operator is left PENDING on the result -- a pooling with tiling windows that
+    follows fuses it (pool_cl), under the conditions it fuses BatchNorm (BN_POOL_FUSED)"""
+    G = int(G)
+    if lazy and relu and BN_POOL_FUSED[0]:
+        return CLTensor(x.data, x.N, x.T, x.H, x.W, None, ("gn", (G, gamma, beta, eps)))
+    slot = amax_slots(1, x.data.device)
+    y = _GNCL.apply(x.data, G, gamma, beta, eps, relu, (x.N, x.T * x.H * x.W), slot)
+    return CLTensor(y, x.N, x.T, x.H, x.W, slot)
 
 
 # ----------------------------------------------------------------------------- the VGGFace front-end on the chain

@@ -4,7 +4,8 @@ API/state-dict compatible with the reference's models/backbone.py for the classe
 north_star path: `VA_3DVGGM` (:62-161), `VA_3DVGGM_Split` (:164-311, the default
 `--backbone v2p_split`) and `VA_3DResNet` (:314-372).  The 3-D stems' convolutions (forward, weight
 and data gradient: tap-walk implicit GEMMs, rounds 5-6; the VGG-M stems as a channels-last chain),
-BatchNorm3d + ReLU and spatial pooling, the temporal back-ends (BiGRU stacks, TCN) and the CBAM
+BatchNorm3d + ReLU and spatial pooling, GroupNorm + ReLU of the `norm_layer='gn'` stems (GroupNorm3dReLU on the same
+channels-last chain, csrc/gn_cl.hip; M3T_GN_CL, see README), the temporal back-ends (BiGRU stacks, TCN) and the CBAM
 gates / BatchNorm2d inside the ResNet run in the HIP library; a configuration the library does not
 cover takes the stock op and says so once on stderr (m3t.ops.stock_fallback).  `VA_3DDenseNet` (:375-423, `--backbone
 densenet`): the ResNet3D stem as a channels-last chain feeding models/densenet.py's DenseNet52_3D, whose dense blocks run as one
@@ -72,6 +73,21 @@ class BatchNorm3dReLU(nn.BatchNorm3d):
         return torch.relu(super().forward(x))
 
 
+class GroupNorm3dReLU(nn.GroupNorm):
+    """nn.GroupNorm followed by ReLU as ONE operator on the channels-last chain (m3t.ops.gn_cl, csrc/gn_cl.hip: statistics per (clip, group),
+    no running statistics -- train and eval are the same computation); same parameters and state_dict keys as nn.GroupNorm.  In the stems'
+    nn.Sequential it takes the GroupNorm slot and an nn.Identity the ReLU's, so every index -- and every checkpoint key -- stays.  Anything
+    the chain does not carry (planes on the GPU, a CPU / float64 input, affine=False, the switch m3t.ops.GN_CL off) is the stock GroupNorm +
+    ReLU, as before this operator existed: not counted as a fallback."""
+
+    def forward(self, x):
+        if isinstance(x, ops.CLTensor):
+            if self.affine and ops.gn_cl_ok(x, self.num_groups):
+                return ops.gn_cl(x, self.num_groups, self.weight, self.bias, self.eps, True, lazy=True)
+            x = x.planes()
+        return torch.relu(super().forward(x))
+
+
 class SpatialMaxPool3d(nn.MaxPool3d):
     """nn.MaxPool3d whose window does not span frames (kernel (1, k, k), stride (1, s, s): every pooling layer of the stems, reference
     backbone.py:80,86,92,182) as a pooling of the N C T planes on the HIP kernels (m3t.ops.pool_planes: one byte per output remembers
@@ -96,12 +112,14 @@ def _norm_relu3d(kind, channels):
     """[normalisation, ReLU] of a stem layer (reference backbone.py:77-79 etc.: BatchNorm3d / GroupNorm(32) then ReLU(True))"""
     if kind == 'bn':
         return [BatchNorm3dReLU(channels), nn.Identity()]
-    return [nn.GroupNorm(32, channels), nn.ReLU(True)]
+    return [GroupNorm3dReLU(32, channels), nn.Identity()]
 
 
 def _vgg_group(idx, norm):
     """Layer group `conv{idx}` of the VGG-M style stem (reference backbone.py:73-103,179-184,243-271)."""
-    chain = norm == 'bn'                  # BatchNorm3d + ReLU have a channels-last kernel; GroupNorm stems stay on planes
+    # BatchNorm3d + ReLU and GroupNorm + ReLU both have channels-last kernels; the GroupNorm stems take the chain under M3T_GN_CL=1
+    # (m3t.ops.GN_CL, read here and again when the model runs) and stay on planes otherwise
+    chain = norm == 'bn' or (norm == 'gn' and ops.GN_CL[0])
     if idx == 1:
         c1 = Conv3d(3, 64, 3, stride=(1, 2, 2), padding=(1, 0, 0))
         c1.cl_chain = chain
@@ -202,7 +220,8 @@ class VA_3DVGGM(nn.Module):
         with ops.batch_counters():
             return self.frame_logits(_squeeze_hw(self.v2p(x)))
 
-    def forward(self, x):
+    def forward(self, x, se=None, au=None):
+        """(se, au: what models.model.AffWild2VA hands every front-end; unused here, as in the reference's one-argument forward.)"""
         with ops.batch_counters():          # (every BatchNorm's num_batches_tracked in one launch)
             return self.temporal(_squeeze_hw(self.v2p(x)))
 

@@ -66,9 +66,9 @@ class AffWild2VA(_Base):
             if hp.backbone == 'resnet':
                 self.visual = VA_3DResNet(resnet_ver='v1', **common)
             elif hp.backbone == 'v2p':
-                self.visual = VA_3DVGGM(**common)
+                self.visual = VA_3DVGGM(norm_layer=getattr(hp, 'norm_layer', 'bn'), **common)
             elif hp.backbone == 'v2p_split':
-                self.visual = VA_3DVGGM_Split(split_layer=hp.split_layer, use_mtl=use_mtl, **common)
+                self.visual = VA_3DVGGM_Split(split_layer=hp.split_layer, use_mtl=use_mtl, norm_layer=getattr(hp, 'norm_layer', 'bn'), **common)
             elif hp.backbone == 'densenet':
                 self.visual = VA_3DDenseNet(**common)
             elif hp.backbone == 'vggface':

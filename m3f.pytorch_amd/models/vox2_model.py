@@ -33,7 +33,7 @@ class VoxCeleb2_1k(_Base):
         if hp.backbone == 'resnet':
             self.visual = VA_3DResNet(frameLen=hp.window, backend=hp.backend, resnet_ver='v1', nClasses=1000)
         elif hp.backbone == 'v2p':
-            self.visual = VA_3DVGGM(frameLen=hp.window, backend=hp.backend, nClasses=1000)
+            self.visual = VA_3DVGGM(frameLen=hp.window, backend=hp.backend, nClasses=1000, norm_layer=getattr(hp, 'norm_layer', 'bn'))
         elif hp.backbone == 'densenet':
             self.visual = VA_3DDenseNet(frameLen=hp.window, backend=hp.backend, nClasses=1000)
         self.history = {'lr': [], 'loss': []}
