@@ -501,6 +501,28 @@ int m3t_pool_cl_fwd(const float* x, size_t P, int H, int W, int C, int kh, int k
 int m3t_pool_cl_bwd(const float* dy, const unsigned char* win, size_t P, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                     float* dx, void* stream);
 
+/* The per-frame ResNet-18/34 (v1) on the chain (csrc/stem_cl.hip; opt-in, M3T_RESNET_CL=1): the two operators that close a residual block and
+ * close the trunk.  Rows are the frames' positions [P H W][C], P = N T.
+ * m3t_bn_add_relu_cl_fwd / _bwd: y = relu(bn(x) + shortcut), the block tail of reference models/resnet.py:37-56 (BasicBlock.forward: out =
+ *   bn2(conv2(.)); out += identity; out = relu(out)) as ONE operator over x, shortcut [M][C].  Statistics (fp64 per-chunk partials in a fixed
+ *   order), the running-statistics update, save_mean / save_invstd, shapes (C % 4 == 0, C / 4 divides 256, C <= 1024, M > 0; training: M >= 2),
+ *   ws (m3t_bn_cl_ws_bytes(M, C) bytes, 8-B aligned) and the slot of y (m3t_amax_out) as m3t_bn_cl_fwd.  Backward works with g = dy (y > 0):
+ *   one partial pass (sum g -> dbeta, sum g xhat -> dgamma), one map pass that writes dx (the BatchNorm data gradient of g; eval: g gamma
+ *   invstd) and ds = g (the shortcut's gradient); dx_colsum [C] (optional) and dx's slot (m3t_amax_out) as m3t_bn_cl_bwd.  No float atomics:
+ *   reruns are bit-identical.  gamma == 0 (zero_init_residual): y = relu(beta + shortcut), dx == 0, dgamma finite.  Bad arguments: M3T_EINVAL
+ *   before any launch.
+ * m3t_mean_cl_fwd / _bwd: nn.AdaptiveAvgPool2d(1) + flatten (reference models/resnet.py:117-119) over channels-last frames x [P][HW][C] ->
+ *   y [P][C]: a frame's rows are added in index order in fp64 (deterministic); backward writes dx [P][HW][C] = dy / HW.  C % 4 == 0, P, HW > 0,
+ *   16-B aligned tensors. */
+int m3t_bn_add_relu_cl_fwd(const float* x, const float* shortcut, size_t M, int C, const float* gamma, const float* beta, float* run_mean,
+                           float* run_var, float momentum, float eps, int training, float* y, float* save_mean, float* save_invstd, float* ws,
+                           size_t ws_bytes, void* stream);
+int m3t_bn_add_relu_cl_bwd(const float* dy, const float* x, const float* y, const float* gamma, const float* save_mean, const float* save_invstd,
+                           size_t M, int C, int training, float* dx, float* ds, float* dgamma, float* dbeta, float* dx_colsum, float* ws,
+                           size_t ws_bytes, void* stream);
+int m3t_mean_cl_fwd(const float* x, size_t P, int HW, int C, float* y, void* stream);
+int m3t_mean_cl_bwd(const float* dy, size_t P, int HW, int C, float* dx, void* stream);
+
 /* GroupNorm on the channels-last chain (csrc/gn_cl.hip; reference models/backbone.py:63-103,165-271 with norm_layer='gn': Conv3d ->
  * GroupNorm(32, C) -> ReLU (-> MaxPool3d((1, 2, 2)))).  Rows x [N][R][C], R = T H W rows per clip; semantics of F.group_norm(x5d, G, gamma, beta,
  * eps) on [N, C, T, H, W]: one mean and one biased variance per (clip, group) over (C / G) R values -- no running statistics, train == eval.

@@ -676,3 +676,209 @@ extern "C" int m3t_bn_pool_cl_bwd(const float* dyp, const float* x, const float*
     }
     return 0;
 }
+
+// ---- the per-frame ResNet (v1) on the chain: the two operators that close a residual block and close the trunk.  Reference models/resnet.py
+// :37-56 (BasicBlock.forward: out = bn2(conv2(.)); out += identity; out = relu(out)) and :117-119 (AdaptiveAvgPool2d(1) + flatten).
+namespace {
+
+// y = relu(bn(x) + shortcut): one sweep, a thread's four channels fixed (the grid's stride is a multiple of C / 4)
+__global__ __launch_bounds__(CL_TH) void bnar_fwd_kernel(const float* __restrict__ x, const float* __restrict__ sc, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, const float* __restrict__ mean,
+                                                         const float* __restrict__ invstd, float* __restrict__ y, size_t total4, int C,
+                                                         unsigned long long* __restrict__ slot) {
+    __shared__ float red4[4];
+    const int c4n = C >> 2;
+    const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
+    const int q = (int)(i0 % (size_t)c4n);
+    float w[4], b[4], mu[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int c = 4 * q + e;
+        mu[e] = mean[c];
+        w[e] = (gamma ? gamma[c] : 1.f) * invstd[c];
+        b[e] = beta ? beta[c] : 0.f;
+    }
+    float mx = 0.f;
+    for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
+        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        const float4 s = reinterpret_cast<const float4*>(sc)[i];
+        const float ve[4] = {v.x, v.y, v.z, v.w}, se[4] = {s.x, s.y, s.z, s.w};
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = m3t_relu(((ve[e] - mu[e]) * w[e] + b[e]) + se[e]);      // (gamma = 0, beta = 0: relu(shortcut), bit for bit)
+        reinterpret_cast<float4*>(y)[i] = make_float4(o[0], o[1], o[2], o[3]);
+        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+    }
+    if (slot) m3t_block_raise_slot(slot, mx, red4);
+}
+
+// g = dy (y > 0);  ds = g;  dx = the BatchNorm data gradient of g.  Column sums of dx and its magnitude slot as bncl_map_kernel<1>.
+__global__ __launch_bounds__(CL_TH) void bnar_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y,
+                                                         const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                         const float* __restrict__ invstd, const float* __restrict__ sums, float* __restrict__ dx,
+                                                         float* __restrict__ ds, size_t total4, int C, float inv_count, int training,
+                                                         unsigned long long* __restrict__ slot, float* __restrict__ colpart) {
+    __shared__ float red4[4];
+    __shared__ float csum[CL_TH * 4];
+    const int c4n = C >> 2;
+    const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
+    const int q = (int)(i0 % (size_t)c4n);
+    float w[4], mu[4], is[4], k1[4], k2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int c = 4 * q + e;
+        mu[e] = mean[c]; is[e] = invstd[c];
+        w[e] = (gamma ? gamma[c] : 1.f) * is[e];
+        k1[e] = training ? sums[c] * inv_count : 0.f;
+        k2[e] = training ? sums[C + c] * inv_count : 0.f;
+    }
+    float mx = 0.f;
+    float cs[4] = {0.f, 0.f, 0.f, 0.f};
+    for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
+        const float4 dv = reinterpret_cast<const float4*>(dy)[i];
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        const float4 yv = reinterpret_cast<const float4*>(y)[i];
+        const float de[4] = {dv.x, dv.y, dv.z, dv.w}, xe[4] = {xv.x, xv.y, xv.z, xv.w}, ye[4] = {yv.x, yv.y, yv.z, yv.w};
+        float o[4], g[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            g[e] = (ye[e] > 0.f) ? de[e] : 0.f;
+            o[e] = training ? w[e] * (g[e] - k1[e] - ((xe[e] - mu[e]) * is[e]) * k2[e]) : g[e] * w[e];
+        }
+        reinterpret_cast<float4*>(dx)[i] = make_float4(o[0], o[1], o[2], o[3]);
+        reinterpret_cast<float4*>(ds)[i] = make_float4(g[0], g[1], g[2], g[3]);
+        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (colpart) { cs[0] += o[0]; cs[1] += o[1]; cs[2] += o[2]; cs[3] += o[3]; }
+    }
+    if (colpart) {
+        // block partial [C]: the 256 / (C / 4) threads that share a channel quad, in thread order (deterministic); colpart [blocks][C]
+#pragma unroll
+        for (int e = 0; e < 4; ++e) csum[threadIdx.x * 4 + e] = cs[e];
+        __syncthreads();
+        for (int c = threadIdx.x; c < C; c += CL_TH) {
+            float t = 0.f;
+            const int base = (int)((size_t)blockIdx.x * CL_TH % (size_t)c4n);
+            const int first = ((c >> 2) - base + c4n) % c4n;
+            for (int th = first; th < CL_TH; th += c4n) t += csum[th * 4 + (c & 3)];
+            colpart[(size_t)blockIdx.x * C + c] = t;
+        }
+        __syncthreads();
+    }
+    if (slot) m3t_block_raise_slot(slot, mx, red4);
+}
+
+// y[p][c] = mean over the HW rows of frame p: a thread = (frame, channel quad), the rows in index order, the sum in fp64 (deterministic)
+__global__ __launch_bounds__(CL_TH) void meancl_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total4, int HW, int C) {
+    const int c4n = C >> 2;
+    for (size_t i = (size_t)blockIdx.x * CL_TH + threadIdx.x; i < total4; i += (size_t)gridDim.x * CL_TH) {
+        const size_t p = i / (size_t)c4n;
+        const int q = (int)(i % (size_t)c4n);
+        const float* src = x + p * (size_t)HW * C + 4 * q;
+        double a[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+        for (int r = 0; r < HW; ++r) {
+            const float4 v = *reinterpret_cast<const float4*>(src + (size_t)r * C);
+            a[0] += (double)v.x; a[1] += (double)v.y; a[2] += (double)v.z; a[3] += (double)v.w;
+        }
+        const double n = (double)HW;
+        reinterpret_cast<float4*>(y)[i] = make_float4((float)(a[0] / n), (float)(a[1] / n), (float)(a[2] / n), (float)(a[3] / n));
+    }
+}
+
+// dx[p][r][c] = dy[p][c] / HW
+__global__ __launch_bounds__(CL_TH) void meancl_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, size_t total4, int HW, int C) {
+    const int c4n = C >> 2;
+    const float n = (float)HW;
+    for (size_t i = (size_t)blockIdx.x * CL_TH + threadIdx.x; i < total4; i += (size_t)gridDim.x * CL_TH) {
+        const size_t row = i / (size_t)c4n;
+        const int q = (int)(i % (size_t)c4n);
+        const float4 d = reinterpret_cast<const float4*>(dy)[(row / (size_t)HW) * (size_t)c4n + q];
+        reinterpret_cast<float4*>(dx)[i] = make_float4(d.x / n, d.y / n, d.z / n, d.w / n);
+    }
+}
+
+}  // namespace
+
+// The tail of a v1 residual block, y = relu(bn(x) + shortcut), as ONE operator over channels-last rows x, shortcut [M][C].  Statistics,
+// running-statistics update, saved mean / inv-std, ws and y's magnitude slot (m3t_amax_out) as m3t_bn_cl_fwd.
+extern "C" int m3t_bn_add_relu_cl_fwd(const float* x, const float* shortcut, size_t M, int C, const float* gamma, const float* beta, float* run_mean,
+                                      float* run_var, float momentum, float eps, int training, float* y, float* save_mean, float* save_invstd,
+                                      float* ws, size_t ws_bytes, void* stream) {
+    unsigned long long* slot = m3t_take_amax_out();
+    if (!bncl_shape_ok(M, C) || !x || !shortcut || !y || !save_mean || !save_invstd || ((uintptr_t)x % 16) != 0 || ((uintptr_t)shortcut % 16) != 0 ||
+        ((uintptr_t)y % 16) != 0)
+        return M3T_EINVAL;
+    if (!training && (!run_mean || !run_var)) return M3T_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (training) {
+        if (M < 2) return M3T_EINVAL;
+        if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+        const int nch = cl_chunks(M);
+        const size_t rpc = (M + nch - 1) / nch;
+        double* partial = reinterpret_cast<double*>(ws);
+        const int groups = CL_TH / (C / 4);
+        bncl_partial_kernel<0><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(x, nullptr, nullptr, nullptr, nullptr, M, C, rpc, 0, partial);
+        M3T_LAUNCH_CHECK();
+        bncl_stats_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, (double)M, C, eps, momentum, run_mean, run_var, save_mean, save_invstd);
+        M3T_LAUNCH_CHECK();
+    } else {
+        bncl_eval_stats_kernel<<<cdiv(C, 256), 256, 0, s>>>(run_mean, run_var, C, eps, save_mean, save_invstd);
+        M3T_LAUNCH_CHECK();
+    }
+    const size_t total4 = M * (size_t)(C / 4);
+    bnar_fwd_kernel<<<grid_for(total4, C / 4), CL_TH, 0, s>>>(x, shortcut, gamma, beta, save_mean, save_invstd, y, total4, C, slot);
+    M3T_LAUNCH_CHECK();
+    return 0;
+}
+
+// Backward of m3t_bn_add_relu_cl_fwd with g = dy (y > 0): one partial pass (sum g, sum g xhat: dbeta, dgamma), one map pass that writes dx (the
+// BatchNorm data gradient of g) and ds = g (the shortcut's gradient).  dx_colsum (optional), dx's magnitude slot and ws as m3t_bn_cl_bwd.
+extern "C" int m3t_bn_add_relu_cl_bwd(const float* dy, const float* x, const float* y, const float* gamma, const float* save_mean,
+                                      const float* save_invstd, size_t M, int C, int training, float* dx, float* ds, float* dgamma, float* dbeta,
+                                      float* dx_colsum, float* ws, size_t ws_bytes, void* stream) {
+    unsigned long long* slot = m3t_take_amax_out();
+    if (!bncl_shape_ok(M, C) || !dy || !x || !y || !dx || !ds || !save_mean || !save_invstd || ((uintptr_t)dy % 16) != 0 || ((uintptr_t)x % 16) != 0 ||
+        ((uintptr_t)y % 16) != 0 || ((uintptr_t)dx % 16) != 0 || ((uintptr_t)ds % 16) != 0)
+        return M3T_EINVAL;
+    if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int nch = cl_chunks(M);
+    const size_t rpc = (M + nch - 1) / nch;
+    double* partial = reinterpret_cast<double*>(ws);
+    float* sums = reinterpret_cast<float*>(partial + (size_t)nch * 2 * C);
+    const int groups = CL_TH / (C / 4);
+    bncl_partial_kernel<1><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(dy, x, y, save_mean, save_invstd, M, C, rpc, 1, partial);
+    M3T_LAUNCH_CHECK();
+    bncl_bwd_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, C, sums, dgamma, dbeta);
+    M3T_LAUNCH_CHECK();
+    const size_t total4 = M * (size_t)(C / 4);
+    const int nblk = grid_for(total4, C / 4);
+    float* colpart = dx_colsum ? sums + 2 * (size_t)C + 64 : nullptr;
+    bnar_bwd_kernel<<<nblk, CL_TH, 0, s>>>(dy, x, y, gamma, save_mean, save_invstd, sums, dx, ds, total4, C, (float)(1.0 / (double)M), training, slot,
+                                           colpart);
+    M3T_LAUNCH_CHECK();
+    if (dx_colsum) {
+        bncl_colsum_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(colpart, nblk, C, dx_colsum);
+        M3T_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// AdaptiveAvgPool2d(1) + flatten over P channels-last frames x [P][HW][C] -> y [P][C]; C % 4 == 0, 16-B aligned tensors.
+extern "C" int m3t_mean_cl_fwd(const float* x, size_t P, int HW, int C, float* y, void* stream) {
+    if (!x || !y || P == 0 || HW <= 0 || C <= 0 || C % 4 != 0 || ((uintptr_t)x % 16) != 0 || ((uintptr_t)y % 16) != 0) return M3T_EINVAL;
+    const size_t total4 = P * (size_t)(C / 4);
+    size_t b = (total4 + CL_TH - 1) / CL_TH;
+    if (b > 2048) b = 2048;
+    meancl_fwd_kernel<<<(int)b, CL_TH, 0, (hipStream_t)stream>>>(x, y, total4, HW, C);
+    M3T_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int m3t_mean_cl_bwd(const float* dy, size_t P, int HW, int C, float* dx, void* stream) {
+    if (!dy || !dx || P == 0 || HW <= 0 || C <= 0 || C % 4 != 0 || ((uintptr_t)dy % 16) != 0 || ((uintptr_t)dx % 16) != 0) return M3T_EINVAL;
+    const size_t total4 = P * (size_t)HW * (size_t)(C / 4);
+    meancl_bwd_kernel<<<grid_for(total4, C / 4), CL_TH, 0, (hipStream_t)stream>>>(dy, dx, total4, HW, C);
+    M3T_LAUNCH_CHECK();
+    return 0;
+}

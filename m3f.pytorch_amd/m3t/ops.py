@@ -3618,6 +3618,134 @@ def pool_cl(x, k, s, p):
     return CLTensor(y, x.N, x.T, Ho, Wo, slot)
 
 
+# ----------------------------------------------------------------------------- the per-frame ResNet-18/34 (v1) on the chain
+# Reference models/resnet.py:18-124 behind the c3d stem of models/backbone.py:314-372.  A CLTensor's rows [N T H W, C] ARE the per-frame fold
+# x.transpose(1, 2).reshape(-1, 64, h, w): the convolutions are conv3d_cl with a Conv2d weight (a unit time tap), BatchNorm (+ReLU) is bn_cl, and
+# csrc/stem_cl.hip adds the two operators the chain lacked -- the block tail relu(bn2(x) + shortcut) and the spatial mean that closes the trunk.
+# M3T_RESNET_CL=1 puts `VA_3DResNet(resnet_ver='v1', use_cbam=False, frontend_agg_mode='ap')` on the chain; the default, 0, keeps it on planes.
+# The switch is read when a model is BUILT (models.backbone.VA_3DResNet marks its first Conv3d) and when it runs.
+RESNET_CL = [os.environ.get("M3T_RESNET_CL", "0") == "1"]
+
+
+def _same_grid(a, b):
+    return (a.N, a.T, a.H, a.W, a.C) == (b.N, b.T, b.H, b.W, b.C)
+
+
+class _BNAddReluCL(torch.autograd.Function):
+    """relu(bn(x) + shortcut) over channels-last rows (csrc/stem_cl.hip m3t_bn_add_relu_cl_*; reference models/resnet.py:37-56); y's and dx's
+    magnitude slots are raised by the kernels, dx's column sums come from the dx pass, the shortcut's gradient ds = dy (y > 0) is an ordinary
+    tensor"""
+
+    @staticmethod
+    def forward(ctx, x, sc, gamma, beta, run_mean, run_var, training, momentum, eps, y_slot):
+        x, sc = _req(x, "x"), _req(sc, "shortcut")
+        M, Cc = x.shape
+        y = torch.empty_like(x)
+        stats = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
+        amax_out(y_slot.data_ptr() if y_slot is not None else None)
+        try:
+            with _Timed("bn_add_relu_cl_fwd", 1, 0, nbytes=(16 if training else 12) * M * Cc):
+                rc = lib().m3t_bn_add_relu_cl_fwd(_p(x), _p(sc), M, Cc, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum), float(eps),
+                                                  int(training), _p(y), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
+                _lib.check(rc, "m3t_bn_add_relu_cl_fwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        ctx.save_for_backward(x, y, gamma, stats)
+        ctx.training = bool(training)
+        ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
+                         beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, gamma, stats = ctx.saved_tensors
+        dy = _req(dy.contiguous(), "dy")
+        M, Cc = x.shape
+        dx, ds = torch.empty_like(x), torch.empty_like(x)
+        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
+        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[2] and ctx.sink_refs[0] is not None) else None
+        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[3] and ctx.sink_refs[1] is not None) else None
+        slot = amax_slots(1, x.device)
+        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        amax_out(slot.data_ptr())
+        try:
+            with _Timed("bn_add_relu_cl_bwd", 2, 0, nbytes=32 * M * Cc):
+                rc = lib().m3t_bn_add_relu_cl_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), M, Cc, int(ctx.training), _p(dx), _p(ds),
+                                                  _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]), _p(csum), _p(ws),
+                                                  ws.numel() * 4, _stream())
+                _lib.check(rc, "m3t_bn_add_relu_cl_bwd")
+        except BaseException:
+            _amax_clear()
+            raise
+        # the convolution in front (conv2) takes dx as its dy: its magnitude slot and column sums ride along
+        _note_grad_slot(dx, slot, csum)
+        return (dx, ds, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
+                None, None, None, None, None, None)
+
+
+def bn_add_relu_cl(x, shortcut, gamma, beta, run_mean, run_var, training, momentum, eps):
+    """relu(batch_norm(x) + shortcut): x, shortcut CLTensors of one grid (device, fp32) -> CLTensor.  Refused, before anything is launched:
+    anything else, and channel counts the BatchNorm kernels do not cover (C % 4, 256 % (C / 4), C <= 1024)"""
+    if not (isinstance(x, CLTensor) and isinstance(shortcut, CLTensor)):
+        raise M3THipError("bn_add_relu_cl: x and shortcut must be CLTensors")
+    if not _same_grid(x, shortcut):
+        raise M3THipError("bn_add_relu_cl: x [%d, %d, %d, %d, C=%d] and shortcut [%d, %d, %d, %d, C=%d] are not one grid"
+                          % (x.N, x.T, x.H, x.W, x.C, shortcut.N, shortcut.T, shortcut.H, shortcut.W, shortcut.C))
+    for t_, name in ((x._data, "x"), (shortcut._data, "shortcut")):
+        if not (t_.is_cuda and t_.dtype == torch.float32):
+            raise M3THipError("bn_add_relu_cl: %s must be a float32 device (HIP) tensor: the M3T hot path has no CPU fallback" % name)
+    Cc = x.C
+    if Cc % 4 != 0 or Cc > 1024 or 256 % (Cc // 4) != 0:
+        raise M3THipError("bn_add_relu_cl: C = %d (need C %% 4 == 0, C / 4 a divisor of 256, C <= 1024)" % Cc)
+    slot = amax_slots(1, x._data.device)
+    y = _BNAddReluCL.apply(x.data, shortcut.data, gamma, beta, run_mean, run_var, training, momentum, eps, slot)
+    return CLTensor(y, x.N, x.T, x.H, x.W, slot)
+
+
+class _MeanCL(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d(1) + flatten over channels-last frames (csrc/stem_cl.hip m3t_mean_cl_*; reference models/resnet.py:117-119)"""
+
+    @staticmethod
+    def forward(ctx, x, geo):
+        P, HW = geo
+        x = _req(x, "x")
+        Cc = x.shape[1]
+        y = torch.empty(P, Cc, dtype=torch.float32, device=x.device)
+        with _Timed("mean_cl_fwd", 1, 0, nbytes=4 * (P * HW + P) * Cc):
+            _lib.check(lib().m3t_mean_cl_fwd(_p(x), P, HW, Cc, _p(y), _stream()), "m3t_mean_cl_fwd")
+        ctx.geo = geo
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        P, HW = ctx.geo
+        dy = _req(dy.contiguous(), "dy")
+        Cc = dy.shape[1]
+        dx = torch.empty(P * HW, Cc, dtype=torch.float32, device=dy.device)
+        with _Timed("mean_cl_bwd", 1, 0, nbytes=4 * (P * HW + P) * Cc):
+            _lib.check(lib().m3t_mean_cl_bwd(_p(dy), P, HW, Cc, _p(dx), _stream()), "m3t_mean_cl_bwd")
+        return dx, None
+
+
+def mean_cl(x):
+    """CLTensor [N, T, H, W] x C -> Tensor [N T, C]: the mean over every frame's H W positions (the rows of the GRU's [N, T, C] input)"""
+    if not isinstance(x, CLTensor):
+        raise M3THipError("mean_cl: x must be a CLTensor")
+    if not (x._data.is_cuda and x._data.dtype == torch.float32):
+        raise M3THipError("mean_cl: x must be a float32 device (HIP) tensor: the M3T hot path has no CPU fallback")
+    if x.C % 4 != 0:
+        raise M3THipError("mean_cl: C = %d (need C %% 4 == 0)" % x.C)
+    return _MeanCL.apply(x.data, (x.N * x.T, x.H * x.W))
+
+
+def resnet_cl_ok(x):
+    """the per-frame ResNet's chain applies: the switch, the chain's switches and fp16x3 mode, the BatchNorm kernels, an fp32 device CLTensor"""
+    return bool(RESNET_CL[0] and BN_PLANES[0] and _cl_chain_on() and isinstance(x, CLTensor) and x._data.is_cuda and x._data.dtype == torch.float32)
+
+
 # ----------------------------------------------------------------------------- GroupNorm on the chain (norm_layer='gn')
 # Reference models/backbone.py:63-103,165-271 with norm_layer='gn': nn.GroupNorm(32, C) -> ReLU (-> MaxPool3d((1, 2, 2))).  csrc/gn_cl.hip:
 # statistics per (clip, group), no running statistics.  M3T_GN_CL=1 puts the 'gn' stems on the chain; the default, 0, keeps them on planes

@@ -315,9 +315,12 @@ class VA_3DResNet(nn.Module):
         super().__init__()
         self.inputDim, self.hiddenDim, self.nClasses = inputDim, hiddenDim, nClasses
         self.frameLen, self.nLayers, self.backend, self.nFCs = frameLen, nLayers, backend, nFCs
+        c1 = Conv3d(3, 64, kernel_size=(5, 7, 7), stride=(1, 2, 2), padding=(2, 3, 3), bias=False)
+        # M3T_RESNET_CL=1 (m3t.ops.RESNET_CL, read here and again when the model runs): v1 blocks without CBAM and average-pooled features run
+        # as ONE channels-last chain from the video to the GRU input; m3t.video.ingest_for then ingests straight into that layout
+        c1.cl_chain = bool(ops.RESNET_CL[0] and resnet_ver == 'v1' and not use_cbam and frontend_agg_mode == 'ap')
         self.c3d = nn.Sequential(
-            Conv3d(3, 64, kernel_size=(5, 7, 7), stride=(1, 2, 2), padding=(2, 3, 3), bias=False),
-            BatchNorm3dReLU(64), nn.Identity(),
+            c1, BatchNorm3dReLU(64), nn.Identity(),
             SpatialMaxPool3d(kernel_size=(1, 3, 3), stride=(1, 2, 2), padding=(0, 1, 1)))
         assert resnet_depth in [18, 34] and resnet_ver in ['v1', 'v2'], \
             'unsupported ResNet configuration: {}, {}'.format(resnet_depth, resnet_ver)
@@ -332,13 +335,16 @@ class VA_3DResNet(nn.Module):
             self.gru = GRU(inputDim, hiddenDim, nLayers, nClasses, nFCs)
         _init_like_reference(self)
 
-    def forward(self, x):
+    def forward(self, x, se=None, au=None):
+        """x: [B, 3, T, H, W] or a VideoCL.  (se, au: what models.model.AffWild2VA hands every front-end; unused here, as in the reference's
+        one-argument forward.)"""
         with ops.batch_counters():          # (every BatchNorm's num_batches_tracked -- 20 in the ResNet, 8 in its CBAM gates, the stem's -- in one launch)
             return self._forward(x)
 
     def _forward(self, x):
         x = self.c3d(x)                                            # [B,64,T,h,w]
-        x = x.transpose(1, 2).reshape(-1, 64, x.size(3), x.size(4))  # fold T into the batch: per-frame ResNet
+        if not isinstance(x, ops.CLTensor):                        # (a CLTensor's rows [N T h w, 64] are that fold already: the trunk takes it as it is)
+            x = x.transpose(1, 2).reshape(-1, 64, x.size(3), x.size(4))  # fold T into the batch: per-frame ResNet
         x = self.resnet(x).view(-1, self.frameLen, self.inputDim)
         if self.backend == 'gru':
             x = self.gru(x)

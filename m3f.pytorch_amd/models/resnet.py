@@ -5,12 +5,21 @@ API/state-dict compatible with the reference's models/resnet.py:18-124 (`BasicBl
 BatchNorm2d with the ReLU behind it (PlaneBatchNorm2d) and since round 5 the dense 2-D convolutions (GemmConv2d: forward with any
 stride, weight gradient and the data gradient as tap-walk implicit GEMMs over channels-last rows on the fp16x3 kernels, no patch
 matrix) run in the HIP library, in every grad mode (round 6: validation / test steps and frozen encoders take the same walks).
+Under M3T_RESNET_CL=1 (m3t.ops.RESNET_CL, opt-in) the v1 trunk without CBAM takes a channels-last m3t.ops.CLTensor from the c3d stem and
+stays on it: GemmConv2d -> ops.conv3d_cl, PlaneBatchNorm2d -> ops.bn_cl, the block tail relu(bn2(.) + shortcut) -> ops.bn_add_relu_cl (one
+operator), AdaptiveAvgPool2d(1) + flatten -> ops.mean_cl -- no transpose between the first convolution and the GRU input.
 """
 import torch
 import torch.nn as nn
 
 from m3t import ops
 from .cbam import CBAM
+
+
+def _frames(x):
+    """a CLTensor leaves the chain as the per-frame planes [N T, C, H, W] (one tiled transpose + the fold of reference backbone.py:349-350)"""
+    p = x.planes()
+    return p.transpose(1, 2).reshape(-1, p.size(1), p.size(3), p.size(4))
 
 
 class PlaneBatchNorm2d(nn.BatchNorm2d):
@@ -22,7 +31,18 @@ class PlaneBatchNorm2d(nn.BatchNorm2d):
         super().__init__(num_features, **kw)
         self.fuse_relu = fuse_relu
 
+    def _cl_ok(self, x):
+        return bool(ops.BN_PLANES[0] and self.affine and self.track_running_stats and self.momentum is not None and x.C % 4 == 0
+                    and x.C <= 1024 and 256 % (x.C // 4) == 0)
+
     def forward(self, x):
+        if isinstance(x, ops.CLTensor):          # the per-frame trunk on the channels-last chain (M3T_RESNET_CL=1): rows = (frame, position)
+            if self._cl_ok(x):
+                if self.training:
+                    ops.count_batch(self.num_batches_tracked)
+                return ops.bn_cl(x, self.weight, self.bias, self.running_mean, self.running_var, self.training, self.momentum, self.eps,
+                                 self.fuse_relu)
+            x = _frames(x)
         if (ops.BN_PLANES[0] and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and self.affine and self.track_running_stats
                 and self.momentum is not None):
             if self.training:
@@ -43,6 +63,10 @@ class GemmConv2d(nn.Conv2d):
 
     def forward(self, x):
         # one path whatever the grad mode (validation / test steps, frozen encoders: see models.backbone.Conv3d)
+        if isinstance(x, ops.CLTensor):          # the channels-last chain: the walks with a unit time tap, no transpose on either side
+            if ops.conv3d_cl_ok(x, self.weight, self.stride, self.padding, self.groups, self.dilation, self.padding_mode):
+                return ops.conv3d_cl(x, self.weight, self.bias, self.stride, self.padding)
+            x = _frames(x)
         if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and self.groups == 1 and tuple(self.dilation) == (1, 1)
                 and self.padding_mode == "zeros" and isinstance(self.padding, tuple)):
             return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding)
@@ -73,7 +97,18 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         shortcut = x if self.downsample is None else self.downsample(x)
-        y = self.bn2(self.conv2(self.bn1(self.conv1(x))))            # (bn1 applies the ReLU)
+        y = self.conv2(self.bn1(self.conv1(x)))                      # (bn1 applies the ReLU)
+        if isinstance(y, ops.CLTensor):
+            # on the chain the block ends in ONE operator, relu(bn2(y) + shortcut) (m3t_bn_add_relu_cl): bn2 does not run on its own
+            bn = self.bn2
+            if self.cbam is None and isinstance(shortcut, ops.CLTensor) and bn._cl_ok(y):
+                if bn.training:
+                    ops.count_batch(bn.num_batches_tracked)
+                return ops.bn_add_relu_cl(y, shortcut, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps)
+            y = _frames(y)
+        if isinstance(shortcut, ops.CLTensor):
+            shortcut = _frames(shortcut)
+        y = self.bn2(y)
         if self.cbam is not None:
             y = self.cbam(y)
         return ops.add_relu(y, shortcut)                             # (one pass: m3t_add_relu)
@@ -156,8 +191,17 @@ class ResNet(_Trunk):
         seq += [block(self.inplanes, planes, use_cbam=use_cbam) for _ in range(1, blocks)]
         return nn.Sequential(*seq)
 
+    def cl_eligible(self):
+        """the trunk can run as a channels-last chain: v1 blocks without CBAM, average-pooled features"""
+        return self.agg_mode == "ap" and all(type(m) is BasicBlock and m.cbam is None for layer in (self.layer1, self.layer2, self.layer3, self.layer4)
+                                             for m in layer)
+
     def forward(self, x):
+        if isinstance(x, ops.CLTensor) and not (ops.resnet_cl_ok(x) and self.cl_eligible()):
+            x = _frames(x)                   # the trunk's door: everything the chain does not carry runs on planes, as ever
         x = self._run_stages(x)
+        if isinstance(x, ops.CLTensor):
+            return ops.mean_cl(x)            # (agg_mode 'ap': AdaptiveAvgPool2d(1) + flatten; the rows are the GRU's [N, T, 512] input)
         if self.agg_mode == "ap":
             x = self.avgpool(x).flatten(1)
         if self.agg_mode == "fc":
@@ -191,6 +235,8 @@ class ResNetV2(_Trunk):
         return nn.Sequential(*seq)
 
     def forward(self, x):
+        if isinstance(x, ops.CLTensor):
+            x = _frames(x)                   # (v2 blocks are not on the chain)
         x = self.relu5(self.bn5(self._run_stages(x)))
         x = self.avgpool(x).flatten(1)       # the reference pools (twice in 'ap' mode: idempotent) then flattens
         if self.agg_mode == "fc":
