@@ -2153,7 +2153,9 @@ class _TemporalBlock(torch.autograd.Function):
         if slots is not None:
             ok.update((1, 2))
             x_ext = _X_EXT[0]                             # (slots tensor, index) left on x by its producer (the previous block's epilogue)
-            todo = ([] if x_ext is not None else [(x, sp)]) + ([(wd, sp + 24)] if wd is not None else [])
+            # (wd is the Conv1d weight [Co, Ci, 1]: measured as the [Co, Ci] matrix -- with its last dimension of 1 measure_amax declined
+            # the whole list, and every contraction with x or wd measured its operand again)
+            todo = ([] if x_ext is not None else [(x, sp)]) + ([(wd.detach().view(Co, Ci), sp + 24)] if wd is not None else [])
             if todo and measure_amax(todo):
                 ok.update(([] if x_ext is not None else [0]) + ([3] if wd is not None else []))
         sl = lambda i: ((x_ext[0].data_ptr() + 8 * x_ext[1]) if (i == 0 and x_ext is not None) else
