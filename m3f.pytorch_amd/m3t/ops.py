@@ -542,10 +542,12 @@ def transpose2d(src):
 
 
 def amax_out(slot):
-    """the NEXT conv1d / mask_pos / weight_norm_fwd call raises the magnitude slot at address `slot` to max |its output| in the same kernel
-    (include/m3t_hip.h, m3t_amax_out): the producer measures what the consuming fp16x3 contraction scales by.  Call it IMMEDIATELY in front
-    of the consuming call -- after every allocation (an allocation failure between the two would leave the pointer parked for an
-    unrelated later call; the wrappers below also clear it on any failure)"""
+    """the NEXT producing call of the calling thread raises the magnitude slot at address `slot` to max |its output| in the same kernel
+    (include/m3t_hip.h, m3t_amax_out): the producer measures what the consuming fp16x3 contraction scales by.  The producers are every entry
+    point this file reaches through _armed_call (the conv1d epilogue, the mask and weight-norm kernels, add_relu, the planes BatchNorm, the
+    transposes, the video ingest and the channels-last chain's operators: more than twenty).  The library takes the pointer in the next such
+    call whatever that call is, so an armed pointer must never outlive its call: inside this file arming is _armed_call's business alone
+    (tests/test_amax_arm_rule.py), after every allocation and cleared on any failure.  Public for callers that drive the library by hand."""
     if slot is not None:
         _lib.check(lib().m3t_amax_out(C.c_void_p(slot)), "m3t_amax_out")
 
@@ -554,22 +556,28 @@ def _amax_clear():
     _lib.check(lib().m3t_amax_out(None), "m3t_amax_out")
 
 
+def _armed_call(slot_ptr, entry, *args):
+    """the library call `entry`(*args) with the magnitude slot at address `slot_ptr` armed for it (None: nothing armed).  The arguments are
+    evaluated, and so every allocation is made, before this frame arms; whatever the call raises -- ctypes refusing an argument before the C
+    side runs included -- leaves no pointer parked for a later kernel."""
+    amax_out(slot_ptr)
+    try:
+        _lib.check(getattr(lib(), entry)(*args), entry)
+    except BaseException:
+        _amax_clear()
+        raise
+
+
 def mask_pos(s, dy, mul=None, drop=None, amax=None):
     """dy where s > 0 (x mul); drop = (p, seed): x the in-kernel dropout mask of the forward conv epilogue, regenerated;
     amax: address of a magnitude slot the kernel raises to max |out|"""
     out = torch.empty_like(dy)
-    amax_out(amax)
-    try:
-        if drop is not None and drop[0] > 0:
-            Cc = dy.shape[-1]
-            _lib.check(lib().m3t_mask_pos_drop(_p(s), _p(dy), _p(out), dy.numel() // Cc, Cc, float(drop[0]), int(drop[1]), _stream()),
-                       "m3t_mask_pos_drop")
-            return out
-        _lib.check(lib().m3t_mask_pos(_p(s), _p(dy), _p(mul), _p(out), dy.numel(), _stream()), "m3t_mask_pos")
-        return out
-    except BaseException:
-        _amax_clear()
-        raise
+    if drop is not None and drop[0] > 0:
+        Cc = dy.shape[-1]
+        _armed_call(amax, "m3t_mask_pos_drop", _p(s), _p(dy), _p(out), dy.numel() // Cc, Cc, float(drop[0]), int(drop[1]), _stream())
+    else:
+        _armed_call(amax, "m3t_mask_pos", _p(s), _p(dy), _p(mul), _p(out), dy.numel(), _stream())
+    return out
 
 
 # ----------------------------------------------------------------------------- Linear
@@ -717,9 +725,7 @@ class _AddRelu(torch.autograd.Function):
     def forward(ctx, a, b):
         out = torch.empty_like(a)
         slot = amax_slots(1, a.device) if TRANSPOSE_IMAGES[0] else None
-        if slot is not None:
-            amax_out(slot.data_ptr())
-        _lib.check(lib().m3t_add_relu(_p(a), _p(b), _p(out), a.numel(), _stream()), "m3t_add_relu")
+        _armed_call(_p(slot), "m3t_add_relu", _p(a), _p(b), _p(out), a.numel(), _stream())
         _OUT_SLOT[0] = slot
         ctx.save_for_backward(out)
         return out
@@ -2105,10 +2111,8 @@ def btc_to_bct(x):
 def _conv(x, w_t, bias, res, mask, pre, B, T, Ci, Co, K, dil, act, anti, prec=0, drop=(0.0, 0), amax=(None, None), amax_y=None):
     """amax_y: address of a magnitude slot the epilogue raises to max |y| (armed AFTER the output allocation)"""
     y = torch.empty(B, T, Co, dtype=torch.float32, device=x.device)
-    amax_out(amax_y)
-    rc = lib().m3t_conv1d_fwd_scaled(_p(x), _p(w_t), _p(bias), _p(res), _p(mask), _p(y), _p(pre), B, T, Ci, Co, K, dil, 0,
-                                     act, anti, float(drop[0]), int(drop[1]), prec, amax[0], amax[1], _stream())
-    _lib.check(rc, "m3t_conv1d_fwd")
+    _armed_call(amax_y, "m3t_conv1d_fwd_scaled", _p(x), _p(w_t), _p(bias), _p(res), _p(mask), _p(y), _p(pre), B, T, Ci, Co, K, dil, 0,
+                act, anti, float(drop[0]), int(drop[1]), prec, amax[0], amax[1], _stream())
     return y
 
 
@@ -2146,10 +2150,8 @@ class _TemporalBlock(torch.autograd.Function):
         if (prec & _lib.M3T_GEMM_F16X3) and (B * T) % 128 == 0 and Co % 128 == 0 and Ci % 32 == 0:
             slots = amax_slots(9, dev)
         sp = slots.data_ptr() if slots is not None else None
-        amax_out(sp + 8 if slots is not None else None)
-        _lib.check(lib().m3t_weight_norm_fwd(_p(v1), _p(g1), _p(w1t), _p(n1), Co, Ci, K, _stream()), "m3t_weight_norm_fwd")
-        amax_out(sp + 16 if slots is not None else None)
-        _lib.check(lib().m3t_weight_norm_fwd(_p(v2), _p(g2), _p(w2t), _p(n2), Co, Co, K, _stream()), "m3t_weight_norm_fwd")
+        _armed_call(sp + 8 if slots is not None else None, "m3t_weight_norm_fwd", _p(v1), _p(g1), _p(w1t), _p(n1), Co, Ci, K, _stream())
+        _armed_call(sp + 16 if slots is not None else None, "m3t_weight_norm_fwd", _p(v2), _p(g2), _p(w2t), _p(n2), Co, Co, K, _stream())
         if slots is not None:
             ok.update((1, 2))
             x_ext = _X_EXT[0]                             # (slots tensor, index) left on x by its producer (the previous block's epilogue)
@@ -2588,6 +2590,24 @@ def grad_norm_scale_(flat, world_size, max_norm):
 
 
 # ----------------------------------------------------------------------------- BatchNorm3d (+ReLU) of the 3-D stems
+def _affine_sinks(ctx, gamma, beta):
+    """forward of a normalisation: remember which of gamma / beta have a gradient sink (top of this file) -- the backward kernel then writes
+    dgamma / dbeta straight into the flat gradient buffer"""
+    ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
+                     beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
+
+
+def _affine_grads(ctx, ig, ib, gamma, Cc, device):
+    """backward of a normalisation with gamma / beta at positions ig / ib of needs_input_grad -> (the two [Cc] rows the kernel writes dgamma
+    and dbeta to: the sink's view if it can be taken, else a row of a fresh [2, Cc]; the two values autograd gets: that row, or None where
+    the sink took the gradient or there is no affine pair)"""
+    g = torch.empty(2, Cc, dtype=torch.float32, device=device)
+    gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[ig] and ctx.sink_refs[0] is not None) else None
+    bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[ib] and ctx.sink_refs[1] is not None) else None
+    return (gs if gs is not None else g[0], bs if bs is not None else g[1],
+            g[0] if (gamma is not None and gs is None) else None, g[1] if (gamma is not None and bs is None) else None)
+
+
 class _BNPlanes(torch.autograd.Function):
     """nn.BatchNorm3d (+ nn.ReLU) on channels-first activations [N, C, T, H, W] (reference models/backbone.py:73-103,179-191), csrc/bn.hip
     m3t_bn_planes_*: statistics sweep | apply + ReLU; backward sums sweep | dx -- the ReLU costs no pass of its own"""
@@ -2601,17 +2621,12 @@ class _BNPlanes(torch.autograd.Function):
         stats = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
         ws = workspace(x.device, int(lib().m3t_bn_planes_ws_bytes(N, Cc, S)))
         slot = amax_slots(1, x.device) if TRANSPOSE_IMAGES[0] else None      # (raised to max |y| by the apply kernel: the next convolution's scale)
-        if slot is not None:
-            amax_out(slot.data_ptr())
-        rc = lib().m3t_bn_planes_fwd(_p(x), N, Cc, S, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum), float(eps),
-                                     int(training), int(relu), _p(y), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
-        _lib.check(rc, "m3t_bn_planes_fwd")
+        _armed_call(_p(slot), "m3t_bn_planes_fwd", _p(x), N, Cc, S, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum), float(eps),
+                    int(training), int(relu), _p(y), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
         _OUT_SLOT[0] = slot
         ctx.save_for_backward(x, y if relu else None, gamma, stats)
         ctx.training, ctx.relu = bool(training), bool(relu)
-        # gradient sinks (top of this file): dgamma / dbeta are written by the backward kernel straight into the flat gradient buffer
-        ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
-                         beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
+        _affine_sinks(ctx, gamma, beta)
         return y
 
     @staticmethod
@@ -2621,21 +2636,14 @@ class _BNPlanes(torch.autograd.Function):
         N, Cc = x.shape[0], x.shape[1]
         S = x.numel() // (N * Cc)
         dx = torch.empty_like(x)
-        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        dg, db, dgamma, dbeta = _affine_grads(ctx, 1, 2, gamma, Cc, x.device)
         ws = workspace(x.device, int(lib().m3t_bn_planes_ws_bytes(N, Cc, S)))
-        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[1] and ctx.sink_refs[0] is not None) else None
-        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[2] and ctx.sink_refs[1] is not None) else None
         slot = amax_slots(1, x.device) if TRANSPOSE_IMAGES[0] else None      # (raised to max |dx|: handed to the convolution in front, _note_grad_slot)
-        if slot is not None:
-            amax_out(slot.data_ptr())
-        rc = lib().m3t_bn_planes_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), N, Cc, S, int(ctx.training), int(ctx.relu),
-                                     _p(dx), _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]), _p(ws), ws.numel() * 4,
-                                     _stream())
-        _lib.check(rc, "m3t_bn_planes_bwd")
+        _armed_call(_p(slot), "m3t_bn_planes_bwd", _p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), N, Cc, S, int(ctx.training),
+                    int(ctx.relu), _p(dx), _p(dg), _p(db), _p(ws), ws.numel() * 4, _stream())
         if slot is not None:
             _note_grad_slot(dx, slot)
-        return (dx, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
-                None, None, None, None, None, None)
+        return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
 # M3T_BN_PLANES=0: BatchNorm3d / BatchNorm2d (+ReLU) of the stems and the per-frame ResNet on the stock (MIOpen) ops instead of csrc/bn.hip's
@@ -2648,6 +2656,13 @@ def bn_planes(x, gamma, beta, run_mean, run_var, training, momentum, eps, relu=T
     return _tag_out(_BNPlanes.apply(x, gamma, beta, run_mean, run_var, training, momentum, eps, relu))
 
 
+def _pool_grid(H, W, k, s, p, ceil_mode=False):
+    """(Ho, Wo) of a pooling of H x W frames with windows k, strides s, paddings p (pairs); ceil_mode: a last window that starts inside the
+    frame counts (unpadded poolings only: the one form the chain has, models/vggface.py)"""
+    up = (s[0] - 1, s[1] - 1) if ceil_mode else (0, 0)
+    return (H + 2 * p[0] - k[0] + up[0]) // s[0] + 1, (W + 2 * p[1] - k[1] + up[1]) // s[1] + 1
+
+
 class _PoolPlanes(torch.autograd.Function):
     """max pooling of [..., H, W] planes with a (kh, kw) window (csrc/bn.hip m3t_pool_planes_*: one byte per output for the winner,
     gather backward) -- nn.MaxPool3d((1, k, k)) of the 3-D stems (reference models/backbone.py:80,86,92,182)"""
@@ -2657,7 +2672,7 @@ class _PoolPlanes(torch.autograd.Function):
         x = _req(x.contiguous(), "x")
         H, W = x.shape[-2], x.shape[-1]
         P = x.numel() // (H * W)
-        Ho, Wo = (H + 2 * p[0] - k[0]) // s[0] + 1, (W + 2 * p[1] - k[1]) // s[1] + 1
+        Ho, Wo = _pool_grid(H, W, k, s, p)
         y = torch.empty(x.shape[:-2] + (Ho, Wo), dtype=torch.float32, device=x.device)
         win = torch.empty(x.shape[:-2] + (Ho, Wo), dtype=torch.uint8, device=x.device)
         rc = lib().m3t_pool_planes_fwd(_p(x), P, H, W, k[0], k[1], s[0], s[1], p[0], p[1], _p(y), C.c_void_p(win.data_ptr()), _stream())
@@ -2887,11 +2902,7 @@ class _Conv3dGemmWgrad(torch.autograd.Function):
                     _lib.check(lib().m3t_bct_to_btc_img(_p(xc), _p(x_img), N_, Ci, T_ * H_ * W_, a_x, None, _stream()), "m3t_bct_to_btc_img")
                 else:
                     x_cl = torch.empty(srows, cw, dtype=torch.float32, device=x.device)
-                    amax_out(slots.data_ptr())
-                    if cw == Ci:
-                        _lib.check(lib().m3t_bct_to_btc(_p(xc), _p(x_cl), N_, Ci, T_ * H_ * W_, _stream()), "m3t_bct_to_btc")
-                    else:
-                        _lib.check(lib().m3t_planes_to_cl4(_p(xc), _p(x_cl), N_, Ci, T_ * H_ * W_, _stream()), "m3t_planes_to_cl4")
+                    _armed_call(slots.data_ptr(), "m3t_bct_to_btc" if cw == Ci else "m3t_planes_to_cl4", _p(xc), _p(x_cl), N_, Ci, T_ * H_ * W_, _stream())
                     _lib.check(lib().m3t_f16x3_split(_p(x_cl), srows, cw, cw, _p(x_img), cw, slots.data_ptr(), _stream()), "m3t_f16x3_split")
                 if w_native is not None:
                     _lib.check(lib().m3t_f16x3_split_perm(_p(w_native), Co, taps, Ci, Ci * taps, 1, taps, _p(w_img), a_w, _stream()), "m3t_f16x3_split_perm")
@@ -3007,11 +3018,9 @@ class _Conv3dGemmWgrad(torch.autograd.Function):
             else:
                 dy_cl = torch.empty(rows, Co, dtype=torch.float32, device=dy.device)
                 slot_dy = amax_slots(1, dy.device)
-                amax_out(slot_dy.data_ptr())                      # (armed after every allocation, consumed by the very next call)
-                if with_sums:      # the bias gradient's per-tile channel sums ride along
-                    _lib.check(lib().m3t_bct_to_btc_sums(_p(dyc), _p(dy_cl), Nn, Co, Sp, _p(dpart), _stream()), "m3t_bct_to_btc_sums")
-                else:
-                    _lib.check(lib().m3t_bct_to_btc(_p(dyc), _p(dy_cl), Nn, Co, Sp, _stream()), "m3t_bct_to_btc")
+                # (with_sums: the bias gradient's per-tile channel sums ride along)
+                entry, sums = ("m3t_bct_to_btc_sums", (_p(dpart),)) if with_sums else ("m3t_bct_to_btc", ())
+                _armed_call(slot_dy.data_ptr(), entry, _p(dyc), _p(dy_cl), Nn, Co, Sp, *sums, _stream())
         dy_img_ = [pre_img]
 
         def dy_image():      # dy channels-last split ONCE under the slot its transpose raised: read by the data gradient's walk(s) and the weight gradient's
@@ -3184,6 +3193,10 @@ class CLTensor:
     def C(self):
         return self._data.shape[1]
 
+    def like(self, data, slot, H=None, W=None, pending=None):
+        """an operator's result on this tensor's clips and frames: `data` with its slot, on the same grid or (a pooling) on H x W"""
+        return CLTensor(data, self.N, self.T, self.H if H is None else H, self.W if W is None else W, slot, pending)
+
     def planes(self):
         """[N, C, T, H, W] (one tiled transpose: leaving the chain)"""
         return btc_to_bct(self.data.view(self.N, self.T * self.H * self.W, self.C)).view(self.N, self.C, self.T, self.H, self.W)
@@ -3221,16 +3234,11 @@ def video_ingest(frames, frame_idx, T, geom, lut, H, W, layout, _entry="m3t_vide
     if layout == "cl":
         out = torch.empty(N_ * T * H * W, 4, dtype=torch.float32, device=dev)
         slot = amax_slots(1, dev)
-        amax_out(slot.data_ptr())
     else:
         out = torch.empty(N_, 3, T, H, W, dtype=torch.float32, device=dev)
         slot = None
-    try:
-        _lib.check(getattr(lib(), _entry)(_p(frames), N_, Ts, Hs, Ws, _p(frame_idx), T, _p(geom), _p(lut), stride, H, W,
-                                          0 if layout == "cl" else 1, _p(out), _stream()), _entry)
-    except BaseException:
-        _amax_clear()
-        raise
+    _armed_call(_p(slot), _entry, _p(frames), N_, Ts, Hs, Ws, _p(frame_idx), T, _p(geom), _p(lut), stride, H, W, 0 if layout == "cl" else 1,
+                _p(out), _stream())
     return VideoCL(out, N_, T, H, W, slot) if layout == "cl" else out
 
 
@@ -3248,6 +3256,16 @@ def _note_grad_slot(t, slot, colsum=None):
     if len(_GRAD_SLOT) > 64:
         _GRAD_SLOT.clear()
     _GRAD_SLOT[id(t)] = (weakref.ref(t), slot, t._version, t.data_ptr(), colsum)
+
+
+def _dx_handover(dx):
+    """a channels-last backward hands its dx [rows, C] to the convolution in front, which takes it as its dy: -> (slot, csum), the magnitude
+    slot the dx kernel is armed with and the [C] row it writes dx's column sums (that layer's bias gradient) to, noted for _grad_slot here.
+    The note is keyed on the dx object and holds only a weak reference: if the kernel call raises, dx dies with its frame and the note with it."""
+    slot = amax_slots(1, dx.device)
+    csum = torch.empty(dx.shape[1], dtype=torch.float32, device=dx.device)
+    _note_grad_slot(dx, slot, csum)
+    return slot, csum
 
 
 def _grad_slot(t):
@@ -3316,8 +3334,7 @@ class _Conv3dCL(torch.autograd.Function):
             else:
                 x_cl = torch.empty(srows, 4, dtype=torch.float32, device=x.device)
                 a_x = slots.data_ptr()
-                amax_out(a_x)
-                _lib.check(lib().m3t_planes_to_cl4(_p(_req(x.contiguous(), "x")), _p(x_cl), N_, Ci, T_ * H_ * W_, _stream()), "m3t_planes_to_cl4")
+                _armed_call(a_x, "m3t_planes_to_cl4", _p(_req(x.contiguous(), "x")), _p(x_cl), N_, Ci, T_ * H_ * W_, _stream())
         else:
             cw = Ci
             w_t = None                               # (the [co][(tap, ci)] image is written straight from w: m3t_f16x3_split_perm)
@@ -3458,18 +3475,11 @@ class _BNCL(torch.autograd.Function):
         y = torch.empty_like(x)
         stats = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
         ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            rc = lib().m3t_bn_cl_fwd(_p(x), M, Cc, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum), float(eps), int(training),
-                                     int(relu), _p(y), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
-            _lib.check(rc, "m3t_bn_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        _armed_call(_p(y_slot), "m3t_bn_cl_fwd", _p(x), M, Cc, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum), float(eps),
+                    int(training), int(relu), _p(y), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
         ctx.save_for_backward(x, y if relu else None, gamma, stats)
         ctx.training, ctx.relu = bool(training), bool(relu)
-        ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
-                         beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
+        _affine_sinks(ctx, gamma, beta)
         return y
 
     @staticmethod
@@ -3478,34 +3488,20 @@ class _BNCL(torch.autograd.Function):
         dy = _req(dy.contiguous(), "dy")
         M, Cc = x.shape
         dx = torch.empty_like(x)
-        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        dg, db, dgamma, dbeta = _affine_grads(ctx, 1, 2, gamma, Cc, x.device)
         ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
-        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[1] and ctx.sink_refs[0] is not None) else None
-        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[2] and ctx.sink_refs[1] is not None) else None
-        slot = amax_slots(1, x.device)
-        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        amax_out(slot.data_ptr())
-        try:
-            rc = lib().m3t_bn_cl_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), M, Cc, int(ctx.training), int(ctx.relu), _p(dx),
-                                     _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]), _p(csum), _p(ws), ws.numel() * 4,
-                                     _stream())
-            _lib.check(rc, "m3t_bn_cl_bwd")
-        except BaseException:
-            _amax_clear()
-            raise
-        # the convolution in front of this BatchNorm takes dx as its dy: its magnitude slot and its column sums (that layer's bias gradient) ride along
-        _note_grad_slot(dx, slot, csum)
-        return (dx, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
-                None, None, None, None, None, None, None)
+        slot, csum = _dx_handover(dx)
+        _armed_call(_p(slot), "m3t_bn_cl_bwd", _p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), M, Cc, int(ctx.training),
+                    int(ctx.relu), _p(dx), _p(dg), _p(db), _p(csum), _p(ws), ws.numel() * 4, _stream())
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None
 
 
 def bn_cl(x, gamma, beta, run_mean, run_var, training, momentum, eps, relu=True, lazy=False):
     """lazy (with relu): the operator is left PENDING on the result -- a pooling with tiling windows that follows fuses it (pool_cl)"""
     if lazy and relu and BN_POOL_FUSED[0]:
-        return CLTensor(x.data, x.N, x.T, x.H, x.W, None, ("bn", (gamma, beta, run_mean, run_var, training, momentum, eps, True)))
+        return x.like(x.data, None, pending=("bn", (gamma, beta, run_mean, run_var, training, momentum, eps, True)))
     slot = amax_slots(1, x.data.device)
-    y = _BNCL.apply(x.data, gamma, beta, run_mean, run_var, training, momentum, eps, relu, slot)
-    return CLTensor(y, x.N, x.T, x.H, x.W, slot)
+    return x.like(_BNCL.apply(x.data, gamma, beta, run_mean, run_var, training, momentum, eps, relu, slot), slot)
 
 
 BN_POOL_FUSED = [os.environ.get("M3T_BN_POOL_FUSED", "1") != "0"]      # 0: BatchNorm + ReLU and the pooling as two operators (A/B)
@@ -3517,54 +3513,33 @@ class _BNPoolCL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, run_mean, run_var, training, momentum, eps, geo, y_slot):
-        P, H, W, k = geo
+        P, H, W, k, (Ho, Wo) = geo
         x = _req(x, "x")
         Cc = x.shape[1]
-        Ho, Wo = H // k, W // k
         yp = torch.empty(P * Ho * Wo, Cc, dtype=torch.float32, device=x.device)
         win = torch.empty(P * Ho * Wo, Cc, dtype=torch.uint8, device=x.device)
         stats = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
         ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(P * H * W, Cc)))
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            rc = lib().m3t_bn_pool_cl_fwd(_p(x), P, H, W, Cc, k, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum), float(eps),
-                                          int(training), _p(yp), C.c_void_p(win.data_ptr()), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4,
-                                          _stream())
-            _lib.check(rc, "m3t_bn_pool_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        _armed_call(_p(y_slot), "m3t_bn_pool_cl_fwd", _p(x), P, H, W, Cc, k, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum),
+                    float(eps), int(training), _p(yp), C.c_void_p(win.data_ptr()), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
         ctx.save_for_backward(x, yp, win, gamma, stats)
         ctx.geo, ctx.training = geo, bool(training)
-        ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
-                         beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
+        _affine_sinks(ctx, gamma, beta)
         return yp
 
     @staticmethod
     def backward(ctx, dy):
         x, yp, win, gamma, stats = ctx.saved_tensors
-        P, H, W, k = ctx.geo
+        P, H, W, k, _ = ctx.geo
         dy = _req(dy.contiguous(), "dy")
         Cc = x.shape[1]
         dx = torch.empty_like(x)
-        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        dg, db, dgamma, dbeta = _affine_grads(ctx, 1, 2, gamma, Cc, x.device)
         ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(P * H * W, Cc)))
-        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[1] and ctx.sink_refs[0] is not None) else None
-        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[2] and ctx.sink_refs[1] is not None) else None
-        slot = amax_slots(1, x.device)
-        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        amax_out(slot.data_ptr())
-        try:
-            rc = lib().m3t_bn_pool_cl_bwd(_p(dy), _p(x), _p(yp), C.c_void_p(win.data_ptr()), _p(gamma), _p(stats[0]), _p(stats[1]), P, H, W, Cc, k,
-                                          int(ctx.training), _p(dx), _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]),
-                                          _p(csum), _p(ws), ws.numel() * 4, _stream())
-            _lib.check(rc, "m3t_bn_pool_cl_bwd")
-        except BaseException:
-            _amax_clear()
-            raise
-        _note_grad_slot(dx, slot, csum)
-        return (dx, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
-                None, None, None, None, None, None, None)
+        slot, csum = _dx_handover(dx)
+        _armed_call(_p(slot), "m3t_bn_pool_cl_bwd", _p(dy), _p(x), _p(yp), C.c_void_p(win.data_ptr()), _p(gamma), _p(stats[0]), _p(stats[1]),
+                    P, H, W, Cc, k, int(ctx.training), _p(dx), _p(dg), _p(db), _p(csum), _p(ws), ws.numel() * 4, _stream())
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None
 
 
 class _PoolCL(torch.autograd.Function):
@@ -3572,19 +3547,13 @@ class _PoolCL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, geo, y_slot):
-        P, H, W, k, s, p = geo
+        P, H, W, k, s, p, (Ho, Wo) = geo
         x = _req(x, "x")
         Cc = x.shape[1]
-        Ho, Wo = (H + 2 * p[0] - k[0]) // s[0] + 1, (W + 2 * p[1] - k[1]) // s[1] + 1
         y = torch.empty(P * Ho * Wo, Cc, dtype=torch.float32, device=x.device)
         win = torch.empty(P * Ho * Wo, Cc, dtype=torch.uint8, device=x.device)
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            _lib.check(lib().m3t_pool_cl_fwd(_p(x), P, H, W, Cc, k[0], k[1], s[0], s[1], p[0], p[1], _p(y), C.c_void_p(win.data_ptr()), _stream()),
-                       "m3t_pool_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        _armed_call(_p(y_slot), "m3t_pool_cl_fwd", _p(x), P, H, W, Cc, k[0], k[1], s[0], s[1], p[0], p[1], _p(y), C.c_void_p(win.data_ptr()),
+                    _stream())
         ctx.save_for_backward(win)
         ctx.geo = geo
         return y
@@ -3592,7 +3561,7 @@ class _PoolCL(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (win,) = ctx.saved_tensors
-        P, H, W, k, s, p = ctx.geo
+        P, H, W, k, s, p, _ = ctx.geo
         dy = _req(dy.contiguous(), "dy")
         Cc = dy.shape[1]
         dx = torch.empty(P * H * W, Cc, dtype=torch.float32, device=dy.device)
@@ -3603,21 +3572,20 @@ class _PoolCL(torch.autograd.Function):
 
 def pool_cl(x, k, s, p):
     k, s, p = tuple(k), tuple(s), tuple(p)
+    grid = _pool_grid(x.H, x.W, k, s, p)
     pend = x._pending
     if pend is not None and k == s and p == (0, 0) and k[0] == k[1] and k[0] in (2, 3) and x.H >= k[0] and x.W >= k[0]:
         kind, args = pend
         slot = amax_slots(1, x._data.device)
         if kind == "gn":
             G, gamma, beta, eps = args
-            y = _GNPoolCL.apply(x._data, G, gamma, beta, eps, (x.N, x.T, x.H, x.W, k[0]), slot)
+            y = _GNPoolCL.apply(x._data, G, gamma, beta, eps, (x.N, x.T, x.H, x.W, k[0], grid), slot)
         else:
             gamma, beta, run_mean, run_var, training, momentum, eps, _ = args
-            y = _BNPoolCL.apply(x._data, gamma, beta, run_mean, run_var, training, momentum, eps, (x.N * x.T, x.H, x.W, k[0]), slot)
-        return CLTensor(y, x.N, x.T, x.H // k[0], x.W // k[0], slot)
+            y = _BNPoolCL.apply(x._data, gamma, beta, run_mean, run_var, training, momentum, eps, (x.N * x.T, x.H, x.W, k[0], grid), slot)
+        return x.like(y, slot, *grid)
     slot = amax_slots(1, x.data.device)
-    y = _PoolCL.apply(x.data, (x.N * x.T, x.H, x.W, k, s, p), slot)
-    Ho, Wo = (x.H + 2 * p[0] - k[0]) // s[0] + 1, (x.W + 2 * p[1] - k[1]) // s[1] + 1
-    return CLTensor(y, x.N, x.T, Ho, Wo, slot)
+    return x.like(_PoolCL.apply(x.data, (x.N * x.T, x.H, x.W, k, s, p, grid), slot), slot, *grid)
 
 
 # ----------------------------------------------------------------------------- the per-frame ResNet-18/34 (v1) on the chain
@@ -3645,19 +3613,12 @@ class _BNAddReluCL(torch.autograd.Function):
         y = torch.empty_like(x)
         stats = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
         ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            with _Timed("bn_add_relu_cl_fwd", 1, 0, nbytes=(16 if training else 12) * M * Cc):
-                rc = lib().m3t_bn_add_relu_cl_fwd(_p(x), _p(sc), M, Cc, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum), float(eps),
-                                                  int(training), _p(y), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
-                _lib.check(rc, "m3t_bn_add_relu_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        with _Timed("bn_add_relu_cl_fwd", 1, 0, nbytes=(16 if training else 12) * M * Cc):
+            _armed_call(_p(y_slot), "m3t_bn_add_relu_cl_fwd", _p(x), _p(sc), M, Cc, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum),
+                        float(eps), int(training), _p(y), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
         ctx.save_for_backward(x, y, gamma, stats)
         ctx.training = bool(training)
-        ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
-                         beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
+        _affine_sinks(ctx, gamma, beta)
         return y
 
     @staticmethod
@@ -3666,26 +3627,13 @@ class _BNAddReluCL(torch.autograd.Function):
         dy = _req(dy.contiguous(), "dy")
         M, Cc = x.shape
         dx, ds = torch.empty_like(x), torch.empty_like(x)
-        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        dg, db, dgamma, dbeta = _affine_grads(ctx, 2, 3, gamma, Cc, x.device)
         ws = workspace(x.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
-        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[2] and ctx.sink_refs[0] is not None) else None
-        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[3] and ctx.sink_refs[1] is not None) else None
-        slot = amax_slots(1, x.device)
-        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        amax_out(slot.data_ptr())
-        try:
-            with _Timed("bn_add_relu_cl_bwd", 2, 0, nbytes=32 * M * Cc):
-                rc = lib().m3t_bn_add_relu_cl_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), M, Cc, int(ctx.training), _p(dx), _p(ds),
-                                                  _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]), _p(csum), _p(ws),
-                                                  ws.numel() * 4, _stream())
-                _lib.check(rc, "m3t_bn_add_relu_cl_bwd")
-        except BaseException:
-            _amax_clear()
-            raise
-        # the convolution in front (conv2) takes dx as its dy: its magnitude slot and column sums ride along
-        _note_grad_slot(dx, slot, csum)
-        return (dx, ds, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
-                None, None, None, None, None, None)
+        slot, csum = _dx_handover(dx)      # (the convolution in front is the block's conv2)
+        with _Timed("bn_add_relu_cl_bwd", 2, 0, nbytes=32 * M * Cc):
+            _armed_call(_p(slot), "m3t_bn_add_relu_cl_bwd", _p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), M, Cc, int(ctx.training),
+                        _p(dx), _p(ds), _p(dg), _p(db), _p(csum), _p(ws), ws.numel() * 4, _stream())
+        return dx, ds, dgamma, dbeta, None, None, None, None, None, None
 
 
 def bn_add_relu_cl(x, shortcut, gamma, beta, run_mean, run_var, training, momentum, eps):
@@ -3703,8 +3651,7 @@ def bn_add_relu_cl(x, shortcut, gamma, beta, run_mean, run_var, training, moment
     if Cc % 4 != 0 or Cc > 1024 or 256 % (Cc // 4) != 0:
         raise M3THipError("bn_add_relu_cl: C = %d (need C %% 4 == 0, C / 4 a divisor of 256, C <= 1024)" % Cc)
     slot = amax_slots(1, x._data.device)
-    y = _BNAddReluCL.apply(x.data, shortcut.data, gamma, beta, run_mean, run_var, training, momentum, eps, slot)
-    return CLTensor(y, x.N, x.T, x.H, x.W, slot)
+    return x.like(_BNAddReluCL.apply(x.data, shortcut.data, gamma, beta, run_mean, run_var, training, momentum, eps, slot), slot)
 
 
 class _MeanCL(torch.autograd.Function):
@@ -3764,11 +3711,6 @@ def gn_cl_ok(x, G):
     return bool(GN_CL[0] and G > 0 and Cc % 4 == 0 and Cc <= 1024 and 256 % (Cc // 4) == 0 and Cc % G == 0 and 1 <= x.N <= 65535)
 
 
-def _gn_sinks(ctx, gamma, beta):
-    ctx.sink_refs = (gamma if (gamma is not None and id(gamma) in _GRAD_SINKS) else None,
-                     beta if (beta is not None and id(beta) in _GRAD_SINKS) else None)
-
-
 class _GNCL(torch.autograd.Function):
     """GroupNorm (+ReLU) over channels-last rows [N R, C] (csrc/gn_cl.hip m3t_gn_cl_*); y's and dx's magnitude slots are raised by the kernels,
     dx's column sums (the bias gradient of the convolution in front) come from the dx pass"""
@@ -3781,17 +3723,11 @@ class _GNCL(torch.autograd.Function):
         y = torch.empty_like(x)
         stats = torch.empty(2, N_ * G, dtype=torch.float32, device=x.device)
         ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, R, Cc)))
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            rc = lib().m3t_gn_cl_fwd(_p(x), N_, R, Cc, G, _p(gamma), _p(beta), float(eps), int(relu), _p(y), _p(stats[0]), _p(stats[1]), _p(ws),
-                                     ws.numel() * 4, _stream())
-            _lib.check(rc, "m3t_gn_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        _armed_call(_p(y_slot), "m3t_gn_cl_fwd", _p(x), N_, R, Cc, G, _p(gamma), _p(beta), float(eps), int(relu), _p(y), _p(stats[0]), _p(stats[1]),
+                    _p(ws), ws.numel() * 4, _stream())
         ctx.save_for_backward(x, y if relu else None, gamma, stats)
         ctx.geo, ctx.G, ctx.relu = geo, G, bool(relu)
-        _gn_sinks(ctx, gamma, beta)
+        _affine_sinks(ctx, gamma, beta)
         return y
 
     @staticmethod
@@ -3801,25 +3737,12 @@ class _GNCL(torch.autograd.Function):
         dy = _req(dy.contiguous(), "dy")
         Cc = x.shape[1]
         dx = torch.empty_like(x)
-        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        dg, db, dgamma, dbeta = _affine_grads(ctx, 2, 3, gamma, Cc, x.device)
         ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, R, Cc)))
-        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[2] and ctx.sink_refs[0] is not None) else None
-        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[3] and ctx.sink_refs[1] is not None) else None
-        slot = amax_slots(1, x.device)
-        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        amax_out(slot.data_ptr())
-        try:
-            rc = lib().m3t_gn_cl_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), N_, R, Cc, ctx.G, int(ctx.relu), _p(dx),
-                                     _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]), _p(csum), _p(ws), ws.numel() * 4,
-                                     _stream())
-            _lib.check(rc, "m3t_gn_cl_bwd")
-        except BaseException:
-            _amax_clear()
-            raise
-        # the convolution in front of this GroupNorm takes dx as its dy: its magnitude slot and its column sums (that layer's bias gradient) ride along
-        _note_grad_slot(dx, slot, csum)
-        return (dx, None, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
-                None, None, None, None)
+        slot, csum = _dx_handover(dx)
+        _armed_call(_p(slot), "m3t_gn_cl_bwd", _p(dy), _p(x), _p(y), _p(gamma), _p(stats[0]), _p(stats[1]), N_, R, Cc, ctx.G, int(ctx.relu), _p(dx),
+                    _p(dg), _p(db), _p(csum), _p(ws), ws.numel() * 4, _stream())
+        return dx, None, dgamma, dbeta, None, None, None, None
 
 
 class _GNPoolCL(torch.autograd.Function):
@@ -3828,52 +3751,33 @@ class _GNPoolCL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, G, gamma, beta, eps, geo, y_slot):
-        N_, T_, H, W, k = geo
+        N_, T_, H, W, k, (Ho, Wo) = geo
         x = _req(x, "x")
         Cc = x.shape[1]
-        Ho, Wo = H // k, W // k
         yp = torch.empty(N_ * T_ * Ho * Wo, Cc, dtype=torch.float32, device=x.device)
         win = torch.empty(N_ * T_ * Ho * Wo, Cc, dtype=torch.uint8, device=x.device)
         stats = torch.empty(2, N_ * G, dtype=torch.float32, device=x.device)
         ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, T_ * H * W, Cc)))
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            rc = lib().m3t_gn_pool_cl_fwd(_p(x), N_, T_, H, W, Cc, G, k, _p(gamma), _p(beta), float(eps), _p(yp), C.c_void_p(win.data_ptr()),
-                                          _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
-            _lib.check(rc, "m3t_gn_pool_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        _armed_call(_p(y_slot), "m3t_gn_pool_cl_fwd", _p(x), N_, T_, H, W, Cc, G, k, _p(gamma), _p(beta), float(eps), _p(yp),
+                    C.c_void_p(win.data_ptr()), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
         ctx.save_for_backward(x, yp, win, gamma, stats)
         ctx.geo, ctx.G = geo, G
-        _gn_sinks(ctx, gamma, beta)
+        _affine_sinks(ctx, gamma, beta)
         return yp
 
     @staticmethod
     def backward(ctx, dy):
         x, yp, win, gamma, stats = ctx.saved_tensors
-        N_, T_, H, W, k = ctx.geo
+        N_, T_, H, W, k, _ = ctx.geo
         dy = _req(dy.contiguous(), "dy")
         Cc = x.shape[1]
         dx = torch.empty_like(x)
-        g = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        dg, db, dgamma, dbeta = _affine_grads(ctx, 2, 3, gamma, Cc, x.device)
         ws = workspace(x.device, int(lib().m3t_gn_cl_ws_bytes(N_, T_ * H * W, Cc)))
-        gs = _take_sink(ctx.sink_refs[0]) if (ctx.needs_input_grad[2] and ctx.sink_refs[0] is not None) else None
-        bs = _take_sink(ctx.sink_refs[1]) if (ctx.needs_input_grad[3] and ctx.sink_refs[1] is not None) else None
-        slot = amax_slots(1, x.device)
-        csum = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        amax_out(slot.data_ptr())
-        try:
-            rc = lib().m3t_gn_pool_cl_bwd(_p(dy), _p(x), _p(yp), C.c_void_p(win.data_ptr()), _p(gamma), _p(stats[0]), _p(stats[1]), N_, T_, H, W,
-                                          Cc, ctx.G, k, _p(dx), _p(gs if gs is not None else g[0]), _p(bs if bs is not None else g[1]),
-                                          _p(csum), _p(ws), ws.numel() * 4, _stream())
-            _lib.check(rc, "m3t_gn_pool_cl_bwd")
-        except BaseException:
-            _amax_clear()
-            raise
-        _note_grad_slot(dx, slot, csum)
-        return (dx, None, (g[0] if (gamma is not None and gs is None) else None), (g[1] if (gamma is not None and bs is None) else None),
-                None, None, None)
+        slot, csum = _dx_handover(dx)
+        _armed_call(_p(slot), "m3t_gn_pool_cl_bwd", _p(dy), _p(x), _p(yp), C.c_void_p(win.data_ptr()), _p(gamma), _p(stats[0]), _p(stats[1]),
+                    N_, T_, H, W, Cc, ctx.G, k, _p(dx), _p(dg), _p(db), _p(csum), _p(ws), ws.numel() * 4, _stream())
+        return dx, None, dgamma, dbeta, None, None, None
 
 
 def gn_cl(x, G, gamma, beta, eps, relu=True, lazy=False):
@@ -3881,10 +3785,9 @@ def gn_cl(x, G, gamma, beta, eps, relu=True, lazy=False):
     follows fuses it (pool_cl), under the conditions it fuses BatchNorm (BN_POOL_FUSED)"""
     G = int(G)
     if lazy and relu and BN_POOL_FUSED[0]:
-        return CLTensor(x.data, x.N, x.T, x.H, x.W, None, ("gn", (G, gamma, beta, eps)))
+        return x.like(x.data, None, pending=("gn", (G, gamma, beta, eps)))
     slot = amax_slots(1, x.data.device)
-    y = _GNCL.apply(x.data, G, gamma, beta, eps, relu, (x.N, x.T * x.H * x.W), slot)
-    return CLTensor(y, x.N, x.T, x.H, x.W, slot)
+    return x.like(_GNCL.apply(x.data, G, gamma, beta, eps, relu, (x.N, x.T * x.H * x.W), slot), slot)
 
 
 # ----------------------------------------------------------------------------- the VGGFace front-end on the chain
@@ -3914,13 +3817,8 @@ class _ReluCL(torch.autograd.Function):
         x = _req(x, "x")
         M, Cc = x.shape
         y = x if inplace else torch.empty_like(x)
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            with _Timed("relu_cl_fwd", 1, 0, nbytes=8 * M * Cc):
-                _lib.check(lib().m3t_relu_cl_fwd(_p(x), M, Cc, _p(y), _stream()), "m3t_relu_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        with _Timed("relu_cl_fwd", 1, 0, nbytes=8 * M * Cc):
+            _armed_call(_p(y_slot), "m3t_relu_cl_fwd", _p(x), M, Cc, _p(y), _stream())
         if inplace:
             ctx.mark_dirty(x)
         ctx.save_for_backward(y)
@@ -3933,25 +3831,16 @@ class _ReluCL(torch.autograd.Function):
         M, Cc = y.shape
         dx = torch.empty_like(y)
         ws = _relu_ws(y.device, M, Cc)
-        slot = amax_slots(1, y.device)
-        csum = torch.empty(Cc, dtype=torch.float32, device=y.device)
-        amax_out(slot.data_ptr())
-        try:
-            with _Timed("relu_cl_bwd", 2, 0, nbytes=12 * M * Cc):
-                _lib.check(lib().m3t_relu_cl_bwd(_p(dy), _p(y), M, Cc, _p(dx), _p(csum), _p(ws), ws.numel() * 4, _stream()), "m3t_relu_cl_bwd")
-        except BaseException:
-            _amax_clear()
-            raise
-        # the convolution in front takes dx as its dy: its magnitude slot and its column sums (that layer's bias gradient) ride along
-        _note_grad_slot(dx, slot, csum)
+        slot, csum = _dx_handover(dx)
+        with _Timed("relu_cl_bwd", 2, 0, nbytes=12 * M * Cc):
+            _armed_call(_p(slot), "m3t_relu_cl_bwd", _p(dy), _p(y), M, Cc, _p(dx), _p(csum), _p(ws), ws.numel() * 4, _stream())
         return dx, None, None
 
 
 def relu_cl(x, inplace=False):
     """CLTensor -> CLTensor; inplace: x's rows are overwritten (a convolution's output, which its backward does not read)"""
     slot = amax_slots(1, x.data.device)
-    y = _ReluCL.apply(x.data, bool(inplace), slot)
-    return CLTensor(y, x.N, x.T, x.H, x.W, slot)
+    return x.like(_ReluCL.apply(x.data, bool(inplace), slot), slot)
 
 
 class _ReluPoolCL(torch.autograd.Function):
@@ -3960,20 +3849,13 @@ class _ReluPoolCL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, geo, y_slot):
-        P, H, W, ceil_mode = geo
+        P, H, W, ceil_mode, (Ho, Wo) = geo
         x = _req(x, "x")
         Cc = x.shape[1]
-        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if ceil_mode else (H // 2, W // 2)
         yp = torch.empty(P * Ho * Wo, Cc, dtype=torch.float32, device=x.device)
         win = torch.empty(P * Ho * Wo, Cc, dtype=torch.uint8, device=x.device)
-        amax_out(y_slot.data_ptr() if y_slot is not None else None)
-        try:
-            with _Timed("relu_pool_cl_fwd", 1, 0, nbytes=(4 * P * H * W + 5 * P * Ho * Wo) * Cc):
-                _lib.check(lib().m3t_relu_pool_cl_fwd(_p(x), P, H, W, Cc, int(ceil_mode), _p(yp), C.c_void_p(win.data_ptr()), _stream()),
-                           "m3t_relu_pool_cl_fwd")
-        except BaseException:
-            _amax_clear()
-            raise
+        with _Timed("relu_pool_cl_fwd", 1, 0, nbytes=(4 * P * H * W + 5 * P * Ho * Wo) * Cc):
+            _armed_call(_p(y_slot), "m3t_relu_pool_cl_fwd", _p(x), P, H, W, Cc, int(ceil_mode), _p(yp), C.c_void_p(win.data_ptr()), _stream())
         ctx.save_for_backward(yp, win)
         ctx.geo = geo
         return yp
@@ -3981,31 +3863,23 @@ class _ReluPoolCL(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         yp, win = ctx.saved_tensors
-        P, H, W, ceil_mode = ctx.geo
+        P, H, W, ceil_mode, _ = ctx.geo
         dy = _req(dy.contiguous(), "dy")
         Cc = yp.shape[1]
         dx = torch.empty(P * H * W, Cc, dtype=torch.float32, device=yp.device)
         ws = _relu_ws(yp.device, P * H * W, Cc)
-        slot = amax_slots(1, yp.device)
-        csum = torch.empty(Cc, dtype=torch.float32, device=yp.device)
-        amax_out(slot.data_ptr())
-        try:
-            with _Timed("relu_pool_cl_bwd", 2, 0, nbytes=(4 * P * H * W + 9 * yp.shape[0]) * Cc):
-                _lib.check(lib().m3t_relu_pool_cl_bwd(_p(dy), _p(yp), C.c_void_p(win.data_ptr()), P, H, W, Cc, int(ceil_mode), _p(dx), _p(csum),
-                                                      _p(ws), ws.numel() * 4, _stream()), "m3t_relu_pool_cl_bwd")
-        except BaseException:
-            _amax_clear()
-            raise
-        _note_grad_slot(dx, slot, csum)
+        slot, csum = _dx_handover(dx)
+        with _Timed("relu_pool_cl_bwd", 2, 0, nbytes=(4 * P * H * W + 9 * yp.shape[0]) * Cc):
+            _armed_call(_p(slot), "m3t_relu_pool_cl_bwd", _p(dy), _p(yp), C.c_void_p(win.data_ptr()), P, H, W, Cc, int(ceil_mode), _p(dx), _p(csum),
+                        _p(ws), ws.numel() * 4, _stream())
         return dx, None, None
 
 
 def relu_pool_cl(x, ceil_mode=True):
     """CLTensor -> CLTensor: relu then a 2 x 2 / stride 2 / no padding max pooling of every frame"""
+    grid = _pool_grid(x.H, x.W, (2, 2), (2, 2), (0, 0), ceil_mode)
     slot = amax_slots(1, x.data.device)
-    y = _ReluPoolCL.apply(x.data, (x.N * x.T, x.H, x.W, bool(ceil_mode)), slot)
-    Ho, Wo = ((x.H + 1) // 2, (x.W + 1) // 2) if ceil_mode else (x.H // 2, x.W // 2)
-    return CLTensor(y, x.N, x.T, Ho, Wo, slot)
+    return x.like(_ReluPoolCL.apply(x.data, (x.N * x.T, x.H, x.W, bool(ceil_mode), grid), slot), slot, *grid)
 
 
 def conv2d(x, w, b, stride, padding):
