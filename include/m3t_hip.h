@@ -523,6 +523,27 @@ int m3t_bn_add_relu_cl_bwd(const float* dy, const float* x, const float* y, cons
 int m3t_mean_cl_fwd(const float* x, size_t P, int HW, int C, float* y, void* stream);
 int m3t_mean_cl_bwd(const float* dy, size_t P, int HW, int C, float* dx, void* stream);
 
+/* The per-frame ResNet-18/34 v2 (pre-activation) on the chain (csrc/stem_cl.hip; opt-in, M3T_RESNET_V2_CL=1): the operator that closes a
+ * residual sum.  Reference models/resnet.py:157-173, 241-242: a block ends in out + identity, and the very next thing is relu(bn1(.)) of the
+ * following block -- or bn5 + relu5 at the trunk's end -- while the sum itself lives on as the next identity.
+ * m3t_add_bn_relu_cl_fwd: a, b [M][C] -> TWO outputs, s = a + b and z = relu(bn(s)).  Training (3 launches): the statistics pass reads a and b,
+ *   WRITES s and sums the fp32-rounded s (chunks, order and fp64 partials of m3t_bn_cl_fwd), then the running-statistics update and the saved
+ *   mean / inv-std, then one map pass s -> z: 20 B per element against 24 for a + b followed by m3t_bn_cl_fwd, and s, z, the saved and the
+ *   running statistics are the bits of that pair.  Eval (2 launches): one sweep reads a, b and writes s, z; s may be null there (a caller
+ *   under no_grad whose sum is dead skips the write), in training a null s is M3T_EINVAL.  Shapes, ws and z's slot (m3t_amax_out) as
+ *   m3t_bn_cl_fwd; s carries no slot (it is only ever an addend).
+ * m3t_add_bn_relu_cl_bwd: g = dz (z > 0); one partial pass over (dz, s, z) (sum g -> dbeta, sum g xhat -> dgamma), one map pass that writes a
+ *   SINGLE tensor ds = (the BatchNorm data gradient of g; eval: g gamma invstd) + ds_out, the gradient of a and of b alike.  ds_out (optional):
+ *   the gradient that reaches s through the next identity, added last; null at the trunk's end and in front of a block with a downsample.
+ *   ds_colsum [C] (optional) and ds's slot (m3t_amax_out) as m3t_bn_cl_bwd's of dx: 32 B per element.  No float atomics: reruns are
+ *   bit-identical.  gamma == 0: ds == ds_out.  Bad arguments: M3T_EINVAL before any launch. */
+int m3t_add_bn_relu_cl_fwd(const float* a, const float* b, size_t M, int C, const float* gamma, const float* beta, float* run_mean, float* run_var,
+                           float momentum, float eps, int training, float* s, float* z, float* save_mean, float* save_invstd, float* ws,
+                           size_t ws_bytes, void* stream);
+int m3t_add_bn_relu_cl_bwd(const float* dz, const float* ds_out, const float* s, const float* z, const float* gamma, const float* save_mean,
+                           const float* save_invstd, size_t M, int C, int training, float* ds, float* dgamma, float* dbeta, float* ds_colsum,
+                           float* ws, size_t ws_bytes, void* stream);
+
 /* GroupNorm on the channels-last chain (csrc/gn_cl.hip; reference models/backbone.py:63-103,165-271 with norm_layer='gn': Conv3d ->
  * GroupNorm(32, C) -> ReLU (-> MaxPool3d((1, 2, 2)))).  Rows x [N][R][C], R = T H W rows per clip; semantics of F.group_norm(x5d, G, gamma, beta,
  * eps) on [N, C, T, H, W]: one mean and one biased variance per (clip, group) over (C / G) R values -- no running statistics, train == eval.

@@ -882,3 +882,218 @@ extern "C" int m3t_mean_cl_bwd(const float* dy, size_t P, int HW, int C, float* 
     M3T_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- the per-frame ResNet v2 (pre-activation) on the chain: the operator that closes a residual sum.  Reference models/resnet.py:157-173 (a block
+// ends in out + identity; the next block opens with relu(bn1(.)) of that sum, and the sum itself is the next identity) and :241-242 (bn5 + relu5 at
+// the trunk's end).  s = a + b and z = relu(bn(s)) from one operator; backward folds the identity's gradient into the one tensor it writes.
+namespace {
+
+// bncl_partial_kernel<0> of s = a + b, which it also writes: the same chunking, the same four rows in flight, the same order of every sum -- the
+// statistics are those of bn_cl on torch's a + b, bit for bit
+__global__ __launch_bounds__(CL_TH) void abr_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ sum, size_t M,
+                                                            int C, size_t rows_per_chunk, double* __restrict__ partial) {
+    extern __shared__ double red[];                         // [2][groups][C]
+    const int c4n = C >> 2, groups = CL_TH / c4n;
+    const int q = threadIdx.x % c4n, g = threadIdx.x / c4n;
+    const size_t r0 = (size_t)blockIdx.x * rows_per_chunk;
+    const size_t r1 = r0 + rows_per_chunk < M ? r0 + rows_per_chunk : M;
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {0.0, 0.0, 0.0, 0.0};
+    if (g < groups) {
+        for (size_t rb = r0 + g; rb < r1; rb += (size_t)4 * groups) {
+            float4 av[4], bv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const size_t r = rb + (size_t)u * groups;
+                const bool in = r < r1;
+                const size_t o = (in ? r : rb) * C + 4 * q;
+                av[u] = *reinterpret_cast<const float4*>(a + o);
+                bv[u] = *reinterpret_cast<const float4*>(b + o);
+                if (!in) av[u] = bv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            float fs[4] = {0.f, 0.f, 0.f, 0.f}, ft[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float ve[4] = {av[u].x + bv[u].x, av[u].y + bv[u].y, av[u].z + bv[u].z, av[u].w + bv[u].w};      // (fp32-rounded: what the map pass reads back)
+                const size_t r = rb + (size_t)u * groups;
+                if (r < r1) *reinterpret_cast<float4*>(sum + r * C + 4 * q) = make_float4(ve[0], ve[1], ve[2], ve[3]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { fs[e] += ve[e]; ft[e] = fmaf(ve[e], ve[e], ft[e]); }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { s[e] += (double)fs[e]; t[e] += (double)ft[e]; }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { red[(size_t)g * C + 4 * q + e] = s[e]; red[(size_t)(groups + g) * C + 4 * q + e] = t[e]; }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += CL_TH) {
+        double a0 = 0.0, b0 = 0.0;
+        for (int k = 0; k < groups; ++k) { a0 += red[(size_t)k * C + c]; b0 += red[(size_t)(groups + k) * C + c]; }      // fixed order
+        partial[((size_t)blockIdx.x * 2 + 0) * C + c] = a0;
+        partial[((size_t)blockIdx.x * 2 + 1) * C + c] = b0;
+    }
+}
+
+// eval mode: s = a + b (written unless sum is null), z = relu(bn(s)) with bncl_map_kernel<0>'s formula: one sweep
+__global__ __launch_bounds__(CL_TH) void abr_eval_kernel(const float* __restrict__ a, const float* __restrict__ bsrc, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, const float* __restrict__ mean,
+                                                         const float* __restrict__ invstd, float* __restrict__ sum, float* __restrict__ z,
+                                                         size_t total4, int C, unsigned long long* __restrict__ slot) {
+    __shared__ float red4[4];
+    const int c4n = C >> 2;
+    const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
+    const int q = (int)(i0 % (size_t)c4n);
+    float w[4], b[4], mu[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int c = 4 * q + e;
+        mu[e] = mean[c];
+        w[e] = (gamma ? gamma[c] : 1.f) * invstd[c];
+        b[e] = beta ? beta[c] : 0.f;
+    }
+    float mx = 0.f;
+    for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
+        const float4 v = reinterpret_cast<const float4*>(a)[i];
+        const float4 u = reinterpret_cast<const float4*>(bsrc)[i];
+        const float ve[4] = {v.x + u.x, v.y + u.y, v.z + u.z, v.w + u.w};
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = m3t_relu((ve[e] - mu[e]) * w[e] + b[e]);
+        if (sum) reinterpret_cast<float4*>(sum)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
+        reinterpret_cast<float4*>(z)[i] = make_float4(o[0], o[1], o[2], o[3]);
+        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+    }
+    if (slot) m3t_block_raise_slot(slot, mx, red4);
+}
+
+// g = dz (z > 0);  ds = the BatchNorm data gradient of g (+ ds_out, added last: the gradient that reaches s as the next identity).  Column sums of
+// ds and its magnitude slot as bnar_bwd_kernel's of dx.
+__global__ __launch_bounds__(CL_TH) void abr_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ ds_out, const float* __restrict__ sm,
+                                                        const float* __restrict__ z, const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                        const float* __restrict__ invstd, const float* __restrict__ sums, float* __restrict__ ds,
+                                                        size_t total4, int C, float inv_count, int training,
+                                                        unsigned long long* __restrict__ slot, float* __restrict__ colpart) {
+    __shared__ float red4[4];
+    __shared__ float csum[CL_TH * 4];
+    const int c4n = C >> 2;
+    const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
+    const int q = (int)(i0 % (size_t)c4n);
+    float w[4], mu[4], is[4], k1[4], k2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int c = 4 * q + e;
+        mu[e] = mean[c]; is[e] = invstd[c];
+        w[e] = (gamma ? gamma[c] : 1.f) * is[e];
+        k1[e] = training ? sums[c] * inv_count : 0.f;
+        k2[e] = training ? sums[C + c] * inv_count : 0.f;
+    }
+    float mx = 0.f;
+    float cs[4] = {0.f, 0.f, 0.f, 0.f};
+    for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
+        const float4 dv = reinterpret_cast<const float4*>(dz)[i];
+        const float4 xv = reinterpret_cast<const float4*>(sm)[i];
+        const float4 zv = reinterpret_cast<const float4*>(z)[i];
+        const float de[4] = {dv.x, dv.y, dv.z, dv.w}, xe[4] = {xv.x, xv.y, xv.z, xv.w}, ze[4] = {zv.x, zv.y, zv.z, zv.w};
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float g = (ze[e] > 0.f) ? de[e] : 0.f;
+            o[e] = training ? w[e] * (g - k1[e] - ((xe[e] - mu[e]) * is[e]) * k2[e]) : g * w[e];
+        }
+        if (ds_out) {
+            const float4 pv = reinterpret_cast<const float4*>(ds_out)[i];
+            o[0] += pv.x; o[1] += pv.y; o[2] += pv.z; o[3] += pv.w;
+        }
+        reinterpret_cast<float4*>(ds)[i] = make_float4(o[0], o[1], o[2], o[3]);
+        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (colpart) { cs[0] += o[0]; cs[1] += o[1]; cs[2] += o[2]; cs[3] += o[3]; }
+    }
+    if (colpart) {
+        // block partial [C]: the 256 / (C / 4) threads that share a channel quad, in thread order (deterministic); colpart [blocks][C]
+#pragma unroll
+        for (int e = 0; e < 4; ++e) csum[threadIdx.x * 4 + e] = cs[e];
+        __syncthreads();
+        for (int c = threadIdx.x; c < C; c += CL_TH) {
+            float t = 0.f;
+            const int base = (int)((size_t)blockIdx.x * CL_TH % (size_t)c4n);
+            const int first = ((c >> 2) - base + c4n) % c4n;
+            for (int th = first; th < CL_TH; th += c4n) t += csum[th * 4 + (c & 3)];
+            colpart[(size_t)blockIdx.x * C + c] = t;
+        }
+        __syncthreads();
+    }
+    if (slot) m3t_block_raise_slot(slot, mx, red4);
+}
+
+}  // namespace
+
+// The sum that closes a v2 residual block and the BatchNorm + ReLU that opens the next one, s = a + b and z = relu(bn(s)), as ONE operator over
+// channels-last rows a, b [M][C].  Training: the statistics pass writes s while it sums it (s is then required); eval: one sweep, s optional.
+// Statistics, running-statistics update, saved mean / inv-std, ws and z's magnitude slot (m3t_amax_out) as m3t_bn_cl_fwd on s.
+extern "C" int m3t_add_bn_relu_cl_fwd(const float* a, const float* b, size_t M, int C, const float* gamma, const float* beta, float* run_mean,
+                                      float* run_var, float momentum, float eps, int training, float* s_out, float* z, float* save_mean,
+                                      float* save_invstd, float* ws, size_t ws_bytes, void* stream) {
+    unsigned long long* slot = m3t_take_amax_out();
+    if (!bncl_shape_ok(M, C) || !a || !b || !z || !save_mean || !save_invstd || ((uintptr_t)a % 16) != 0 || ((uintptr_t)b % 16) != 0 ||
+        ((uintptr_t)z % 16) != 0 || ((uintptr_t)s_out % 16) != 0)
+        return M3T_EINVAL;
+    if (training && !s_out) return M3T_EINVAL;
+    if (!training && (!run_mean || !run_var)) return M3T_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t total4 = M * (size_t)(C / 4);
+    if (training) {
+        if (M < 2) return M3T_EINVAL;
+        if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+        const int nch = cl_chunks(M);
+        const size_t rpc = (M + nch - 1) / nch;
+        double* partial = reinterpret_cast<double*>(ws);
+        const int groups = CL_TH / (C / 4);
+        abr_partial_kernel<<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), st>>>(a, b, s_out, M, C, rpc, partial);
+        M3T_LAUNCH_CHECK();
+        bncl_stats_final_kernel<<<cdiv(C, 64), 256, 0, st>>>(partial, nch, (double)M, C, eps, momentum, run_mean, run_var, save_mean, save_invstd);
+        M3T_LAUNCH_CHECK();
+        bncl_map_kernel<0><<<grid_for(total4, C / 4), CL_TH, 0, st>>>(s_out, nullptr, nullptr, gamma, beta, save_mean, save_invstd, nullptr, z, total4, C,
+                                                                     0.f, 1, 1, slot, nullptr);
+        M3T_LAUNCH_CHECK();
+    } else {
+        bncl_eval_stats_kernel<<<cdiv(C, 256), 256, 0, st>>>(run_mean, run_var, C, eps, save_mean, save_invstd);
+        M3T_LAUNCH_CHECK();
+        abr_eval_kernel<<<grid_for(total4, C / 4), CL_TH, 0, st>>>(a, b, gamma, beta, save_mean, save_invstd, s_out, z, total4, C, slot);
+        M3T_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// Backward of m3t_add_bn_relu_cl_fwd with g = dz (z > 0): one partial pass (sum g, sum g xhat: dbeta, dgamma), one map pass that writes the ONE
+// tensor ds = (the BatchNorm data gradient of g) + ds_out -- the gradient of a and of b alike.  ds_out (optional): what reaches s through its
+// other use, the next identity.  ds_colsum (optional), ds's magnitude slot and ws as m3t_bn_cl_bwd's of dx.
+extern "C" int m3t_add_bn_relu_cl_bwd(const float* dz, const float* ds_out, const float* s, const float* z, const float* gamma,
+                                      const float* save_mean, const float* save_invstd, size_t M, int C, int training, float* ds, float* dgamma,
+                                      float* dbeta, float* ds_colsum, float* ws, size_t ws_bytes, void* stream) {
+    unsigned long long* slot = m3t_take_amax_out();
+    if (!bncl_shape_ok(M, C) || !dz || !s || !z || !ds || !save_mean || !save_invstd || ((uintptr_t)dz % 16) != 0 || ((uintptr_t)s % 16) != 0 ||
+        ((uintptr_t)z % 16) != 0 || ((uintptr_t)ds % 16) != 0 || ((uintptr_t)ds_out % 16) != 0)
+        return M3T_EINVAL;
+    if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int nch = cl_chunks(M);
+    const size_t rpc = (M + nch - 1) / nch;
+    double* partial = reinterpret_cast<double*>(ws);
+    float* sums = reinterpret_cast<float*>(partial + (size_t)nch * 2 * C);
+    const int groups = CL_TH / (C / 4);
+    bncl_partial_kernel<1><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), st>>>(dz, s, z, save_mean, save_invstd, M, C, rpc, 1, partial);
+    M3T_LAUNCH_CHECK();
+    bncl_bwd_final_kernel<<<cdiv(C, 64), 256, 0, st>>>(partial, nch, C, sums, dgamma, dbeta);
+    M3T_LAUNCH_CHECK();
+    const size_t total4 = M * (size_t)(C / 4);
+    const int nblk = grid_for(total4, C / 4);
+    float* colpart = ds_colsum ? sums + 2 * (size_t)C + 64 : nullptr;
+    abr_bwd_kernel<<<nblk, CL_TH, 0, st>>>(dz, ds_out, s, z, gamma, save_mean, save_invstd, sums, ds, total4, C, (float)(1.0 / (double)M), training,
+                                           slot, colpart);
+    M3T_LAUNCH_CHECK();
+    if (ds_colsum) {
+        bncl_colsum_final_kernel<<<cdiv(C, 64), 256, 0, st>>>(colpart, nblk, C, ds_colsum);
+        M3T_LAUNCH_CHECK();
+    }
+    return 0;
+}

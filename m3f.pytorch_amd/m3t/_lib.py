@@ -114,6 +114,8 @@ SIGNATURES = {
     "m3t_bn_add_relu_cl_bwd": [_f, _f, _f, _f, _f, _f, _z, _i, _i, _f, _f, _f, _f, _f, _f, _z, _s],
     "m3t_mean_cl_fwd": [_f, _z, _i, _i, _f, _s],
     "m3t_mean_cl_bwd": [_f, _z, _i, _i, _f, _s],
+    "m3t_add_bn_relu_cl_fwd": [_f, _f, _z, _i, _f, _f, _f, _f, C.c_float, C.c_float, _i, _f, _f, _f, _f, _f, _z, _s],
+    "m3t_add_bn_relu_cl_bwd": [_f, _f, _f, _f, _f, _f, _f, _z, _i, _i, _f, _f, _f, _f, _f, _z, _s],
     "m3t_gn_cl_ws_bytes": [_i, _z, _i],
     "m3t_gn_cl_fwd": [_f, _i, _z, _i, _i, _f, _f, C.c_float, _i, _f, _f, _f, _f, _z, _s],
     "m3t_gn_cl_bwd": [_f, _f, _f, _f, _f, _f, _i, _z, _i, _i, _i, _f, _f, _f, _f, _f, _z, _s],

@@ -3695,6 +3695,86 @@ def resnet_cl_ok(x):
     return bool(RESNET_CL[0] and BN_PLANES[0] and _cl_chain_on() and isinstance(x, CLTensor) and x._data.is_cuda and x._data.dtype == torch.float32)
 
 
+# ----------------------------------------------------------------------------- the per-frame ResNet-18/34 v2 (pre-activation) on the chain
+# Reference models/resnet.py:127-251.  A v2 block ends in s = out + identity (:173); the very next thing is relu(bn1(s)) of the following block, or
+# bn5 + relu5 at the trunk's end (:160-161, :241-242), and s itself lives on as the next identity.  csrc/stem_cl.hip m3t_add_bn_relu_cl_* is that
+# seam as one operator with two outputs; everything else a v2 block needs is on the chain already (conv3d_cl, bn_cl, pool_cl, mean_cl).
+# M3T_RESNET_V2_CL=1 puts `VA_3DResNet(resnet_ver='v2', use_cbam=False, frontend_agg_mode='ap')` on the chain; the default, 0, keeps it on planes.
+# A switch of its own (M3T_RESNET_CL is v1's alone), read when a model is BUILT and when it runs.
+RESNET_V2_CL = [os.environ.get("M3T_RESNET_V2_CL", "0") == "1"]
+
+
+class _AddBNReluCL(torch.autograd.Function):
+    """(s, z) = (a + b, relu(bn(a + b))) over channels-last rows (csrc/stem_cl.hip m3t_add_bn_relu_cl_*; reference models/resnet.py:157-173,
+    241-242).  z's and ds's magnitude slots are raised by the kernels, ds's column sums come from the map pass.  Backward writes ONE tensor ds =
+    bn_dx(dz (z > 0)) + ds_out and returns it for a and for b alike: no backward of the chain writes into the dy it is handed (_Conv3dCL,
+    _PoolCL, _BNCL and this one only read it), and the note _dx_handover leaves on it is void once anything bumps its version."""
+
+    @staticmethod
+    def forward(ctx, a, b, gamma, beta, run_mean, run_var, training, momentum, eps, z_slot, keep_s):
+        a, b = _req(a, "a"), _req(b, "b")
+        M, Cc = a.shape
+        s = torch.empty_like(a) if keep_s else None      # (eval under no_grad with a dead sum: the kernel skips the write)
+        z = torch.empty_like(a)
+        stats = torch.empty(2, Cc, dtype=torch.float32, device=a.device)
+        ws = workspace(a.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
+        with _Timed("add_bn_relu_cl_fwd", 3 if training else 2, 0, nbytes=(20 if training else (16 if keep_s else 12)) * M * Cc):
+            _armed_call(_p(z_slot), "m3t_add_bn_relu_cl_fwd", _p(a), _p(b), M, Cc, _p(gamma), _p(beta), _p(run_mean), _p(run_var), float(momentum),
+                        float(eps), int(training), _p(s), _p(z), _p(stats[0]), _p(stats[1]), _p(ws), ws.numel() * 4, _stream())
+        ctx.save_for_backward(s, z, gamma, stats)
+        ctx.training = bool(training)
+        ctx.set_materialize_grads(False)      # (backward sees None, not a tensor of zeros, for an output nobody used: ds_out at the trunk's end)
+        _affine_sinks(ctx, gamma, beta)
+        return s, z
+
+    @staticmethod
+    def backward(ctx, ds_out, dz):
+        s, z, gamma, stats = ctx.saved_tensors
+        M, Cc = z.shape
+        if dz is None:
+            # nothing came back through the BatchNorm: the sum's gradient is its identity's alone, the affine pair's is zero -- no launch
+            zero = lambda i: torch.zeros(Cc, dtype=torch.float32, device=z.device) if (gamma is not None and ctx.needs_input_grad[i]) else None
+            return ds_out, ds_out, zero(2), zero(3), None, None, None, None, None, None, None
+        dz = _req(dz.contiguous(), "dz")
+        if ds_out is not None:
+            ds_out = _req(ds_out.contiguous(), "ds_out")
+        ds = torch.empty_like(z)
+        dg, db, dgamma, dbeta = _affine_grads(ctx, 2, 3, gamma, Cc, z.device)
+        ws = workspace(z.device, int(lib().m3t_bn_cl_ws_bytes(M, Cc)))
+        slot, csum = _dx_handover(ds)      # (the convolution in front is the closed block's conv2)
+        with _Timed("add_bn_relu_cl_bwd", 4, 0, nbytes=(32 if ds_out is not None else 28) * M * Cc):
+            _armed_call(_p(slot), "m3t_add_bn_relu_cl_bwd", _p(dz), _p(ds_out), _p(s), _p(z), _p(gamma), _p(stats[0]), _p(stats[1]), M, Cc,
+                        int(ctx.training), _p(ds), _p(dg), _p(db), _p(csum), _p(ws), ws.numel() * 4, _stream())
+        return ds, ds, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def add_bn_relu_cl(a, b, gamma, beta, run_mean, run_var, training, momentum, eps, need_s=True):
+    """(s, z) = (a + b, relu(batch_norm(a + b))): a, b CLTensors of one grid (device, fp32) -> two CLTensors; s carries no magnitude slot (it is
+    only ever an addend).  need_s=False: the caller has no use for the sum -- in eval mode under no_grad it is then not written and s is None.
+    Refused, before anything is launched: anything else, and channel counts the BatchNorm kernels do not cover (C % 4, 256 % (C / 4),
+    C <= 1024)"""
+    if not (isinstance(a, CLTensor) and isinstance(b, CLTensor)):
+        raise M3THipError("add_bn_relu_cl: a and b must be CLTensors")
+    if not _same_grid(a, b):
+        raise M3THipError("add_bn_relu_cl: a [%d, %d, %d, %d, C=%d] and b [%d, %d, %d, %d, C=%d] are not one grid"
+                          % (a.N, a.T, a.H, a.W, a.C, b.N, b.T, b.H, b.W, b.C))
+    for t_, name in ((a._data, "a"), (b._data, "b")):
+        if not (t_.is_cuda and t_.dtype == torch.float32):
+            raise M3THipError("add_bn_relu_cl: %s must be a float32 device (HIP) tensor: the M3T hot path has no CPU fallback" % name)
+    Cc = a.C
+    if Cc % 4 != 0 or Cc > 1024 or 256 % (Cc // 4) != 0:
+        raise M3THipError("add_bn_relu_cl: C = %d (need C %% 4 == 0, C / 4 a divisor of 256, C <= 1024)" % Cc)
+    slot = amax_slots(1, a._data.device)
+    keep_s = bool(need_s or training or torch.is_grad_enabled())
+    s, z = _AddBNReluCL.apply(a.data, b.data, gamma, beta, run_mean, run_var, training, momentum, eps, slot, keep_s)
+    return (a.like(s, None) if keep_s else None), a.like(z, slot)
+
+
+def resnet_v2_cl_ok(x):
+    """resnet_cl_ok for the v2 trunk: its own switch, the chain's switches and fp16x3 mode, the BatchNorm kernels, an fp32 device CLTensor"""
+    return bool(RESNET_V2_CL[0] and BN_PLANES[0] and _cl_chain_on() and isinstance(x, CLTensor) and x._data.is_cuda and x._data.dtype == torch.float32)
+
+
 # ----------------------------------------------------------------------------- GroupNorm on the chain (norm_layer='gn')
 # Reference models/backbone.py:63-103,165-271 with norm_layer='gn': nn.GroupNorm(32, C) -> ReLU (-> MaxPool3d((1, 2, 2))).  csrc/gn_cl.hip:
 # statistics per (clip, group), no running statistics.  M3T_GN_CL=1 puts the 'gn' stems on the chain; the default, 0, keeps them on planes

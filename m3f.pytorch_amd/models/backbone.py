@@ -318,7 +318,9 @@ class VA_3DResNet(nn.Module):
         c1 = Conv3d(3, 64, kernel_size=(5, 7, 7), stride=(1, 2, 2), padding=(2, 3, 3), bias=False)
         # M3T_RESNET_CL=1 (m3t.ops.RESNET_CL, read here and again when the model runs): v1 blocks without CBAM and average-pooled features run
         # as ONE channels-last chain from the video to the GRU input; m3t.video.ingest_for then ingests straight into that layout
-        c1.cl_chain = bool(ops.RESNET_CL[0] and resnet_ver == 'v1' and not use_cbam and frontend_agg_mode == 'ap')
+        # M3T_RESNET_V2_CL=1 (m3t.ops.RESNET_V2_CL) does the same for the v2 trunk; each version answers to its own switch alone
+        c1.cl_chain = bool(not use_cbam and frontend_agg_mode == 'ap' and
+                           ((ops.RESNET_CL[0] and resnet_ver == 'v1') or (ops.RESNET_V2_CL[0] and resnet_ver == 'v2')))
         self.c3d = nn.Sequential(
             c1, BatchNorm3dReLU(64), nn.Identity(),
             SpatialMaxPool3d(kernel_size=(1, 3, 3), stride=(1, 2, 2), padding=(0, 1, 1)))

@@ -8,6 +8,9 @@ matrix) run in the HIP library, in every grad mode (round 6: validation / test s
 Under M3T_RESNET_CL=1 (m3t.ops.RESNET_CL, opt-in) the v1 trunk without CBAM takes a channels-last m3t.ops.CLTensor from the c3d stem and
 stays on it: GemmConv2d -> ops.conv3d_cl, PlaneBatchNorm2d -> ops.bn_cl, the block tail relu(bn2(.) + shortcut) -> ops.bn_add_relu_cl (one
 operator), AdaptiveAvgPool2d(1) + flatten -> ops.mean_cl -- no transpose between the first convolution and the GRU input.
+Under M3T_RESNET_V2_CL=1 (m3t.ops.RESNET_V2_CL, opt-in, a switch of its own) the v2 trunk without CBAM does the same: every residual sum and the
+BatchNorm + ReLU behind it -- the next block's bn1, or bn5 -- are ONE operator with two outputs (ops.add_bn_relu_cl: the sum, which lives on as
+the next identity, and its activation).
 """
 import torch
 import torch.nn as nn
@@ -139,6 +142,13 @@ class BasicBlockV2(nn.Module):
             y = self.cbam(y)
         return y + shortcut
 
+    def forward_cl(self, pre, s):
+        """the chain form (ResNetV2._run_chain): `pre` is what conv1 reads -- relu(bn1(s)), which the operator that closed the sum in front
+        already made, or the stem's map for the first block -- and `s` the open sum (None when nobody kept it: this block then has a
+        downsample).  -> (y, shortcut): the sum y + shortcut is closed by whoever applies the next BatchNorm (ops.add_bn_relu_cl)"""
+        shortcut = s if self.downsample is None else self.downsample(pre)
+        return self.conv2(self.bn2(self.conv1(pre))), shortcut
+
 
 def _init_trunk(net):
     for m in net.modules():
@@ -234,9 +244,36 @@ class ResNetV2(_Trunk):
         seq += [block(self.inplanes, planes, use_cbam=use_cbam) for _ in range(1, blocks)]
         return nn.Sequential(*seq)
 
+    def cl_eligible(self):
+        """the trunk can run as a channels-last chain: v2 blocks without CBAM, average-pooled features"""
+        return self.agg_mode == "ap" and all(type(m) is BasicBlockV2 and m.cbam is None
+                                             for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for m in layer)
+
+    @staticmethod
+    def _close(bn, y, shortcut, need_s):
+        """s = y + shortcut and z = relu(bn(s)) as ONE operator (m3t_add_bn_relu_cl): `bn` -- the next block's bn1, or bn5 -- does not run on
+        its own, so its batch is counted here"""
+        if bn.training:
+            ops.count_batch(bn.num_batches_tracked)
+        return ops.add_bn_relu_cl(y, shortcut, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps, need_s)
+
+    def _run_chain(self, x):
+        """the four stages, bn5 + ReLU and the spatial mean on the channels-last chain (M3T_RESNET_V2_CL=1): the blocks are walked here because a
+        residual sum is closed by the BatchNorm BEHIND it -- the module tree, and with it every state_dict key, stays as it is"""
+        blocks = [m for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for m in layer]
+        first = blocks[0]
+        y, shortcut = first.forward_cl(x if first.is_first_block_of_first_layer else first.bn1(x), x)
+        for nxt in blocks[1:]:
+            s, z = self._close(nxt.bn1, y, shortcut, nxt.downsample is None)      # (a block with a downsample takes its identity from z: s is dead)
+            y, shortcut = nxt.forward_cl(z, s)
+        _, z = self._close(self.bn5, y, shortcut, False)
+        return ops.mean_cl(z)                # (the reference pools twice in 'ap' mode: idempotent; the rows are the GRU's [N, T, 512] input)
+
     def forward(self, x):
         if isinstance(x, ops.CLTensor):
-            x = _frames(x)                   # (v2 blocks are not on the chain)
+            if ops.resnet_v2_cl_ok(x) and self.cl_eligible():
+                return self._run_chain(x)
+            x = _frames(x)                   # the trunk's door: everything the chain does not carry runs on planes, as ever
         x = self.relu5(self.bn5(self._run_stages(x)))
         x = self.avgpool(x).flatten(1)       # the reference pools (twice in 'ap' mode: idempotent) then flattens
         if self.agg_mode == "fc":
