@@ -1019,6 +1019,25 @@ int m3t_jpeg_decode_walk(const uint8_t* stream_d, long long stream_bytes, const 
 int m3t_jpeg_par_max_bytes(void);
 int m3t_jpeg_par_lanes(int lanes);
 
+/* The resident frame store's batch step (csrc/frame_store.hip; m3t.jpeg.FrameStore): the scan bytes of every frame of a corpus stay on the
+ * device in n_chunks buffers, uploaded once, and ONE launch assembles the byte stream of a batch -- m3t_jpeg_decode_walk's stream_d -- from
+ * them.  m3t.jpeg.plan_frames builds the table.
+ *   chunks_h, chunk_bytes_h  host long long [n_chunks]: the device address of each chunk (16-byte aligned) and its size in bytes
+ *   chunks_d                 the same addresses on the device (read by the kernel)
+ *   rows      int [m][4] = chunk, source offset, destination offset, bytes; given twice like the decode's tables: rows_h on the host
+ *             (validated here, before the launch) and rows_d, the same ints on the device, 16-byte aligned (read by the kernel)
+ *   dst       device, 16-byte aligned, dst_bytes a multiple of 16 in [16, 2^31)
+ * For every row dst[dst_off .. dst_off + bytes) = chunk[src_off .. src_off + bytes); every other byte of dst[0 .. dst_bytes) is written as
+ * zero by the same kernel: one pass over dst, every 16-byte granule stored exactly once, so the result does not depend on any order.  A flat
+ * grid-stride over the destination granules; a lane finds its granule's row by a binary search of the destination offsets (at most
+ * ceil(log2(m + 1)) steps) and moves 16 bytes.  No atomics, no communication between workgroups, no spinning.  No byte outside a validated
+ * source range is read and none outside dst[0 .. dst_bytes) is written.
+ * M3T_EINVAL, before any launch: m < 0 or n_chunks < 0; a null or misaligned pointer (dst always; the tables when m > 0); a chunk index
+ * out of range; a source range outside its chunk; a negative offset or length, or one that is no multiple of 16; destinations that are not
+ * ascending, overlap, or end past dst_bytes - 16 (the stream's closing 16 zero bytes).  m == 0 zero-fills and returns 0. */
+int m3t_jpeg_gather(const long long* chunks_h, const long long* chunk_bytes_h, int n_chunks, const long long* chunks_d, const int* rows_h,
+                    const int* rows_d, int m, uint8_t* dst, long long dst_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * Window collate (csrc/collate.hip): the rest of the AffWild2 loader's __getitem__ (models/dataset.py:241-343 minus load_video) for a whole
  * batch in ONE launch, from side tracks that live on the device (m3t.dataset.TrackStore uploads them once).

@@ -181,6 +181,7 @@ SIGNATURES = {
                              _f, _s],
     "m3t_jpeg_par_max_bytes": [],
     "m3t_jpeg_par_lanes": [_i],
+    "m3t_jpeg_gather": [C.c_void_p, C.c_void_p, _i, _f, C.c_void_p, _f, _i, _f, C.c_longlong, _s],
     "m3t_window_collate": [_f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _f, C.c_longlong, _i, _i, _i, _f, C.c_longlong, _f, C.c_longlong,
                            _f, _i, _f, _i, _i, _f, _f, _f, _f, _f, _f, _f, _s],
     "m3t_grad_norm_scale": [_f, _z, C.c_float, C.c_float, _f, _f, _z, _s],

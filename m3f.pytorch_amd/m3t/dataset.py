@@ -13,8 +13,9 @@ windows is cut from it by one kernel, from one small int table.
 
 An item is (video, start, track_len) -- or (video, start), track_len = window, the training split; `video` is an index or a name.
 `batch['video']` stays the caller's (decode, then `m3t.video.ingest`): for a store given `has_image`, collate adds the `video_frame_idx`
-rows that go with the frames start .. start + track_len - 1 of each item.  Out of scope: JPEG decoding, the file-system scan, prefetch
-threads and DDP sharding.
+rows that go with the frames start .. start + track_len - 1 of each item.  The frames themselves have a resident store of their own,
+`m3t.jpeg.FrameStore` (the files' scan bytes on the device, a batch of windows decoded from them; its `has_image(video)` is the array this
+store takes).  Out of scope: the file-system scan, prefetch threads and DDP sharding.
 """
 import numpy as np
 import torch

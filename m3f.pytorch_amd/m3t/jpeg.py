@@ -15,6 +15,16 @@ later stage takes:
   load_clips   clips[n][t] of bytes / paths / None -> (frames [N, Ts, H, W, 3], present [N, Ts], status); `present` is what
                video.frame_index takes, an absent frame is zeros (the reference's `img is None`)
 
+pack is per-batch host work (header walks, marker scans, table builds, one concatenation) and nothing it computes depends on the batch.
+The resident store does it once for a whole set of videos and cuts a batch from the device:
+
+  frame_records   every file of a set read and parsed ONCE -> FrameRecords: per-frame rows, the set's tables, the scan bytes in chunks
+  plan_frames     a batch of windows (video, start[, track_len]) -> FramePlan: the decode's int table, the gather table, frame_idx;
+                  host validation and vectorised indexing only
+  gather_host     the gather in numpy (the kernel's oracle); gather: m3t_jpeg_gather (csrc/frame_store.hip) as it is
+  FrameStore      the chunks on the device; decode(items) -> (frames [N, window, H, W, 3], frame_idx, status): plan_frames, one small
+                  upload, one device-to-device gather, the decode above; batches(items, batch_size)
+
 In scope: baseline sequential DCT (SOF0), 8 bits, Huffman, one interleaved scan, 1 component (gray) or 3 (YCbCr, luma 1x1 / 2x1 / 2x2,
 chroma 1x1), up to four tables of each kind, restart intervals; APPn / COM are skipped and EXIF orientation is ignored.  Everything else
 -- progressive, extended, lossless, arithmetic, 12 bits, 16-bit quantisation tables, four components, other sampling factors, several
@@ -417,7 +427,6 @@ def decode(batch, out=None, slots=None, order="bgr", walk="auto", sub_bytes=None
         dst_slots = n
     if not torch.cuda.is_available():
         raise M3THipError("m3t.jpeg needs the GPU: the M3T path has no CPU fallback")
-    lib = _lib.load()
     dev = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
     with torch.cuda.device(dev):
         if out is None:
@@ -425,15 +434,24 @@ def decode(batch, out=None, slots=None, order="bgr", walk="auto", sub_bytes=None
         tables = np.ascontiguousarray(tables, np.int32)
         t_d = torch.from_numpy(tables).to(dev, non_blocking=True)
         s_d = batch.stream.to(dev, non_blocking=True)
-        ws_bytes = int(lib.m3t_jpeg_workspace_bytes(n, H, W))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        walk_stats = torch.empty(batch.n_segs, 2, dtype=torch.int32, device=dev) if stats else None
-        _lib.check(lib.m3t_jpeg_decode_walk(s_d.data_ptr(), s_d.numel(), tables.ctypes.data, t_d.data_ptr(), n, batch.n_segs, batch.n_quant,
-                                            batch.n_huff, H, W, out.data_ptr(), dst_slots, 0 if order == "bgr" else 1, ws.data_ptr(), ws_bytes,
-                                            status.data_ptr(), walk_i, sub_i, min_i, max_i,
-                                            walk_stats.data_ptr() if stats and batch.n_segs else None, _stream()), "m3t_jpeg_decode_walk")
+        status, walk_stats = _decode_on_device(s_d, tables, t_d, (n, batch.n_segs, batch.n_quant, batch.n_huff, H, W), out, dst_slots, order,
+                                               (walk_i, sub_i, min_i, max_i), stats, dev)
     return (out, status, walk_stats) if stats else (out, status)
+
+
+def _decode_on_device(s_d, tables_h, tables_d, counts, out, dst_slots, order, walk_ints, stats, dev):
+    """The one call of m3t_jpeg_decode_walk (decode and FrameStore.decode share it): the stream s_d and the int table (host array and device
+    tensor, the same ints) are on `dev`, the current device; -> (status int32 [n], walk_stats int32 [n_segs, 2] or None), on the current stream."""
+    n, n_segs, n_quant, n_huff, H, W = counts
+    lib = _lib.load()
+    ws_bytes = int(lib.m3t_jpeg_workspace_bytes(n, H, W))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    walk_stats = torch.empty(n_segs, 2, dtype=torch.int32, device=dev) if stats else None
+    _lib.check(lib.m3t_jpeg_decode_walk(s_d.data_ptr(), s_d.numel(), tables_h.ctypes.data, tables_d.data_ptr(), n, n_segs, n_quant, n_huff, H, W,
+                                        out.data_ptr(), dst_slots, 0 if order == "bgr" else 1, ws.data_ptr(), ws_bytes, status.data_ptr(),
+                                        *walk_ints, walk_stats.data_ptr() if stats and n_segs else None, _stream()), "m3t_jpeg_decode_walk")
+    return status, walk_stats
 
 
 def _read(item):
@@ -464,3 +482,388 @@ def load_clips(clips, order="bgr", threads=8, pin=False, walk="auto", sub_bytes=
     batch = pack(flat, pin=pin)
     frames, status = decode(batch, order=order, walk=walk, sub_bytes=sub_bytes)
     return frames.view(N, Ts, batch.height, batch.width, 3), batch.present.reshape(N, Ts), status
+
+
+# ---- the resident frame store -----------------------------------------------------------------------------------------------------------
+# Nothing pack computes depends on the batch: a file's header, tables, segment list and scan bytes are the same in every epoch.  So they are
+# found ONCE (frame_records), the scan bytes stay on the device (FrameStore), and a batch of windows is a few vectorised index operations
+# on the host (plan_frames), one device-to-device gather (m3t_jpeg_gather, csrc/frame_store.hip) and the decode as it is.
+GATHER_COLS = 4                     # chunk, source offset, destination offset, bytes (include/m3t_hip.h)
+STREAM_MAX = 2 ** 31 - 1 - 2048     # the largest stream m3t_jpeg_decode_walk takes: its segment offsets are `int` (csrc/jpeg_core.h)
+_READ_AHEAD = 256                   # files in flight between the reader threads and the parser
+
+
+def _excl_cumsum(a):
+    out = np.zeros(a.shape[0], np.int64)
+    np.cumsum(a[:-1], out=out[1:])
+    return out
+
+
+class FrameRecords:
+    """What frame_records found, per frame f of the whole set (the videos' frames one after the other, video v at video_off[v] ..
+    video_off[v + 1]):
+      present bool [F]; chunk int32 [F], offset int64 [F] (a multiple of 16), nbytes int32 [F]: where the frame's scan lies;
+      images  int32 [F, 16]: pack's row -- flags, components, luma h, luma v, MCUs per segment, 0, segments, then the quantisation, DC and
+              AC table of each component as indices into `quant` / `huff` (the set's tables, deduplicated by content);
+      seg_row int64 [F]: the frame's first row of segs int32 [S, 3] = offset relative to the frame's scan, length, restart marker;
+      quant   int32 [Q, 32], huff int32 [Hf, 384]: pack's lookup forms;
+      chunk_sizes int64 [C]; chunks: the host chunks (uint8 arrays), or None where every chunk was handed on as it filled;
+      names, height, width, chunk_bytes."""
+    __slots__ = ("names", "index", "video_off", "present", "chunk", "offset", "nbytes", "images", "seg_row", "segs", "quant", "huff",
+                 "chunk_sizes", "chunks", "height", "width", "chunk_bytes")
+
+    def _video(self, video):
+        if isinstance(video, str):
+            if video not in self.index:
+                raise ValueError("frame store: unknown video %r" % (video,))
+            return self.index[video]
+        v = int(video)
+        if not 0 <= v < len(self.names):
+            raise ValueError("frame store: unknown video %d (the store holds %d)" % (v, len(self.names)))
+        return v
+
+    def has_image(self, video):
+        """bool [frames of the video]: what TrackStore's videos[name]['has_image'] takes"""
+        v = self._video(video)
+        return self.present[self.video_off[v]:self.video_off[v + 1]].copy()
+
+    @property
+    def n_frames(self):
+        return int(self.video_off[-1])
+
+
+def frame_records(videos, chunk_bytes=1 << 30, on_unsupported="raise", threads=8, _sink=None):
+    """videos: an ordered mapping name -> a sequence of `bytes`, a path or None, one entry per frame (frame i is the reference's
+    '{:05d}.jpg'.format(i + 1)) -> FrameRecords.  Host only.  Every file is read (by a pool of `threads` threads, at most 16) and parsed
+    exactly once.  The scan bytes go into chunks: a frame's scan starts on a 16-byte boundary and is zero padded to one, never straddles a
+    chunk, a chunk holds at most chunk_bytes (a multiple of 16 below 2^31), a single frame larger than that gets a chunk of its own.  A
+    missing file or None is an absent frame; a file parse refuses raises Unsupported with the video and the frame in front of the reason
+    (on_unsupported="raise") or is an absent frame ("absent").  ValueError (naming the video and frame) where two frames differ in size,
+    and for a set without a single frame to decode.
+    _sink(index, chunk): called with every chunk as it fills (a view of the staging buffer, valid during the call); the records then keep
+    no chunk, and the host memory held at any time is one chunk and the tables (FrameStore uploads through it)."""
+    chunk_bytes = int(chunk_bytes)
+    if chunk_bytes <= 0 or chunk_bytes % 16 or chunk_bytes >= 2 ** 31:
+        raise ValueError("frame_records: chunk_bytes must be a positive multiple of 16 below 2^31")
+    if on_unsupported not in ("raise", "absent"):
+        raise ValueError("frame_records: on_unsupported must be 'raise' or 'absent'")
+    names = list(videos)
+    if not names:
+        raise ValueError("frame_records: no videos")
+    counts = [len(videos[nm]) for nm in names]
+    F = int(sum(counts))
+    r = FrameRecords()
+    r.names, r.index, r.chunk_bytes = names, {nm: i for i, nm in enumerate(names)}, chunk_bytes
+    r.video_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    r.present = np.zeros(F, bool)
+    r.chunk, r.offset, r.nbytes = np.zeros(F, np.int32), np.zeros(F, np.int64), np.zeros(F, np.int32)
+    r.images, r.seg_row = np.zeros((F, IMG_COLS), np.int32), np.zeros(F, np.int64)
+    quants, huffs, qrows, hrows = {}, {}, [], []
+
+    def q_index(q):
+        key = q.tobytes()
+        if key not in quants:
+            quants[key] = len(qrows)
+            nat = np.zeros(64, np.uint16)
+            nat[ZIGZAG] = q
+            qrows.append(nat.view(np.int32))
+        return quants[key]
+
+    def h_index(t):
+        key = t[0].tobytes() + t[1].tobytes()
+        if key not in huffs:
+            huffs[key] = len(hrows)
+            hrows.append(huff_lookup(t[0], t[1]))
+        return huffs[key]
+
+    stage = np.zeros(min(chunk_bytes, 1 << 20), np.uint8)      # grows to one chunk; zero wherever no scan byte has been written
+    pos, sizes, kept, segs, n_segs, size, first = 0, [], None if _sink else [], [], 0, None, None
+
+    def flush():
+        nonlocal pos
+        if pos == 0:
+            return
+        if _sink:
+            _sink(len(sizes), stage[:pos])
+        else:
+            kept.append(stage[:pos].copy())
+        sizes.append(pos)
+        stage[:pos] = 0
+        pos = 0
+
+    def entries():
+        for v, nm in enumerate(names):
+            for i, it in enumerate(videos[nm]):
+                yield v, i, it
+
+    with ThreadPoolExecutor(max(1, min(int(threads), 16))) as pool:
+        todo, f = entries(), 0
+        while True:
+            group = [e for _, e in zip(range(_READ_AHEAD), todo)]
+            if not group:
+                break
+            for (v, i, _), data in zip(group, pool.map(_read, [e[2] for e in group])):
+                f += 1
+                if data is None:
+                    continue
+                try:
+                    h = parse(data)
+                except Unsupported as e:
+                    if on_unsupported == "absent":
+                        continue
+                    raise Unsupported("video %r, frame %d: %s" % (names[v], i, e)) from None
+                if size is None:
+                    size, first = (h.height, h.width), (names[v], i)
+                if (h.height, h.width) != size:
+                    raise ValueError("frame_records: video %r, frame %d is %d x %d; the frames of a store share one size, and video %r, "
+                                     "frame %d is %d x %d" % ((names[v], i, h.height, h.width) + first + size))
+                scan = np.frombuffer(data, np.uint8, count=h.scan_end - h.scan_offset, offset=h.scan_offset)
+                padded = (scan.size + 15) // 16 * 16
+                if pos and pos + padded > chunk_bytes:
+                    flush()
+                if pos + padded > stage.size:                   # grow towards one chunk; past it only for a single oversize frame
+                    if padded >= 2 ** 31:
+                        raise ValueError("frame_records: video %r, frame %d: a scan of %d bytes" % (names[v], i, scan.size))
+                    grown = np.zeros(max(pos + padded, min(2 * stage.size, chunk_bytes)), np.uint8)
+                    grown[:pos] = stage[:pos]
+                    stage = grown
+                stage[pos:pos + scan.size] = scan
+                # the segments, exactly as pack finds them
+                mcus = h.mcus
+                ri = h.restart_interval if 0 < h.restart_interval < mcus else mcus
+                want = -(-mcus // ri)
+                at = np.flatnonzero((scan[:-1] == 0xFF) & ((scan[1:] & 0xF8) == 0xD0)) if scan.size > 1 else np.zeros(0, np.int64)
+                rows = np.empty((want, 3), np.int32)
+                rows[:] = (scan.size, 0, -2)
+                found = at.size + 1
+                k = min(found, want)
+                rows[:k, 0] = np.concatenate([[0], at + 2])[:k]
+                rows[:k, 1] = (np.concatenate([at, [scan.size]]) - np.concatenate([[0], at + 2]))[:k]
+                rows[:k, 2] = np.concatenate([[-1], scan[at + 1] & 7])[:k]
+                g = f - 1
+                r.present[g], r.chunk[g], r.offset[g], r.nbytes[g], r.seg_row[g] = True, len(sizes), pos, scan.size, n_segs
+                r.images[g, :7] = (1 | (2 if found != want else 0), h.components, h.hs, h.vs, ri, 0, want)
+                for c in range(h.components):
+                    r.images[g, 7 + c], r.images[g, 10 + c], r.images[g, 13 + c] = q_index(h.quant[c]), h_index(h.dc[c]), h_index(h.ac[c])
+                segs.append(rows)
+                n_segs += want
+                pos += padded
+                if padded > chunk_bytes:
+                    flush()
+    flush()
+    if size is None:
+        raise ValueError("frame_records: no frame of the set can be decoded, the store has no size")
+    r.segs = np.concatenate(segs).astype(np.int32, copy=False) if segs else np.zeros((0, 3), np.int32)
+    r.quant = np.stack(qrows).astype(np.int32, copy=False)
+    r.huff = np.stack(hrows).astype(np.int32, copy=False)
+    r.chunk_sizes, r.chunks = np.asarray(sizes, np.int64), kept
+    r.height, r.width = size
+    return r
+
+
+class FramePlan:
+    """What plan_frames made of a batch.  N, window, n = N window; tables: the ONE int table of m3t_jpeg_decode_walk (JpegBatch's layout,
+    slots the identity) with n_segs, n_quant, n_huff; rows: the gather table int32 [m, 4]; stream_bytes; frame_idx int32 [N, window];
+    present bool [n]; height, width."""
+    __slots__ = ("N", "window", "n", "tables", "n_segs", "n_quant", "n_huff", "rows", "stream_bytes", "frame_idx", "present", "height", "width")
+
+    def batch(self, stream):
+        """-> the JpegBatch this plan describes over `stream`, the gathered bytes (a uint8 host tensor or array of stream_bytes)"""
+        stream = stream if isinstance(stream, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(stream, np.uint8))
+        if stream.dtype != torch.uint8 or stream.numel() != self.stream_bytes:
+            raise ValueError("FramePlan.batch: the stream must be %d uint8" % self.stream_bytes)
+        b = JpegBatch()
+        b.stream, b.tables = stream, self.tables
+        b.n, b.n_segs, b.n_quant, b.n_huff, b.height, b.width = self.n, self.n_segs, self.n_quant, self.n_huff, self.height, self.width
+        b.present, b.headers = self.present, [None] * self.n
+        return b
+
+
+def plan_frames(records, items, window):
+    """Host validation of a batch of windows over a FrameRecords, before anything touches a device -> FramePlan.  items: [(video, start[,
+    track_len])], video an index or a name, track_len = window when left out (dataset.plan's items).  Image n window + t is frame start + t
+    of item n; a slot past track_len or an absent frame is an absent image (the decode zero-fills it).  ValueError: an unknown video, a
+    negative start, track_len outside [1, window], start + track_len past the video's frames, a batch whose gathered bytes would not fit
+    the decode's `int` offsets.  Everything per frame and per segment is vectorised indexing; only the items are walked."""
+    window = int(window)
+    if window <= 0:
+        raise ValueError("plan_frames: window must be positive, got %r" % (window,))
+    N = len(items)
+    tab = np.zeros((N, 3), np.int64)
+    for n, it in enumerate(items):
+        if len(it) not in (2, 3):
+            raise ValueError("plan_frames: item %d: expected (video, start[, track_len]), got %r" % (n, it))
+        try:
+            v = records._video(it[0])
+        except ValueError as e:
+            raise ValueError("plan_frames: item %d: %s" % (n, e)) from None
+        start, tl = int(it[1]), window if len(it) == 2 else int(it[2])
+        frames = int(records.video_off[v + 1] - records.video_off[v])
+        if start < 0:
+            raise ValueError("plan_frames: item %d: start %d is negative" % (n, start))
+        if not 1 <= tl <= window:
+            raise ValueError("plan_frames: item %d: track_len %d outside [1, %d]" % (n, tl, window))
+        if start + tl > frames:
+            raise ValueError("plan_frames: item %d: frames %d .. %d run past the %d frames of %s"
+                             % (n, start, start + tl - 1, frames, records.names[v]))
+        tab[n] = (v, start, tl)
+    p = FramePlan()
+    p.N, p.window, p.n, p.height, p.width = N, window, N * window, records.height, records.width
+    t = np.arange(window, dtype=np.int64)
+    inside = t[None, :] < tab[:, 2:3]
+    frame = np.where(inside, records.video_off[tab[:, 0]][:, None] + tab[:, 1:2] + t[None, :], 0)
+    p.present = (inside & records.present[frame]).reshape(-1)
+    idx = np.flatnonzero(p.present)                              # the images to decode, and the frames behind them
+    fr = frame.reshape(-1)[idx]
+    nbytes = (records.nbytes[fr].astype(np.int64) + 15) // 16 * 16
+    to = _excl_cumsum(nbytes)
+    p.stream_bytes = int(nbytes.sum()) + 16
+    if p.stream_bytes > STREAM_MAX:
+        raise ValueError("plan_frames: the batch gathers %d bytes; the decode's segment offsets are int, at most %d" % (p.stream_bytes, STREAM_MAX))
+    p.rows = np.stack([records.chunk[fr].astype(np.int64), records.offset[fr], to, nbytes], axis=1).astype(np.int32).reshape(-1, GATHER_COLS)
+    images = np.zeros((p.n, IMG_COLS), np.int32)
+    img = records.images[fr]                                     # (a copy: fancy indexing)
+    n_seg = img[:, 6].astype(np.int64)
+    seg0 = _excl_cumsum(n_seg)
+    p.n_segs = int(n_seg.sum())
+    img[:, 5] = seg0
+    src = np.repeat(records.seg_row[fr] - seg0, n_seg) + np.arange(p.n_segs, dtype=np.int64)
+    segs = np.empty((p.n_segs, SEG_COLS), np.int32)
+    segs[:, 0] = np.repeat(idx, n_seg)
+    segs[:, 1] = records.segs[src, 0] + np.repeat(to, n_seg)      # rebased to the batch stream
+    segs[:, 2:] = records.segs[src, 1:]
+    comp = np.arange(3)[None, :] < img[:, 1:2]                   # the table columns an image names: one per component
+    for cols, name, store in ((slice(7, 10), "n_quant", records.quant), (slice(10, 16), "n_huff", records.huff)):
+        named = comp if name == "n_quant" else np.concatenate([comp, comp], axis=1)
+        used = np.unique(img[:, cols][named])
+        img[:, cols] = np.where(named, np.searchsorted(used, img[:, cols]), 0)
+        setattr(p, name, int(used.size))
+        if name == "n_quant":
+            quant = store[used]
+        else:
+            huff = store[used]
+    images[idx] = img
+    p.tables = np.concatenate([images.reshape(-1), segs.reshape(-1), np.arange(p.n, dtype=np.int32), quant.reshape(-1),
+                               huff.reshape(-1)]).astype(np.int32, copy=False)
+    from . import video                                          # (here: m3t.video loads the operator layer, which parse and pack do without)
+    rows = []
+    for v, start, tl in tab:
+        present = records.present[records.video_off[v]:records.video_off[v + 1]]
+        rows.append(video.frame_index(present[start:start + tl], 0, int(tl), window))
+    p.frame_idx = np.stack(rows).astype(np.int32) if rows else np.zeros((0, window), np.int32)
+    return p
+
+
+def gather_host(chunks, rows, stream_bytes):
+    """m3t_jpeg_gather in numpy: the host chunks (FrameRecords.chunks) and a gather table -> the batch stream, uint8 [stream_bytes].
+    The kernel's oracle, and what hands a store-built batch to csrc/jpeg_host_check.cpp."""
+    out = np.zeros(int(stream_bytes), np.uint8)
+    for chunk, src, to, nbytes in np.asarray(rows, np.int64).reshape(-1, GATHER_COLS):
+        part = np.asarray(chunks[chunk][src:src + nbytes])
+        if part.size != nbytes or to < 0 or to + nbytes > out.size - 16:
+            raise ValueError("gather_host: row (%d, %d, %d, %d) does not fit" % (chunk, src, to, nbytes))
+        out[to:to + nbytes] = part
+    return out
+
+
+def gather(chunks, rows, dst, dst_bytes=None):
+    """m3t_jpeg_gather as it is: chunks, a list of uint8 device tensors; rows, int32 [m, 4]; dst, a uint8 device tensor of which the first
+    dst_bytes (default: all) are written, on the current stream.  M3THipError for whatever the entry point refuses."""
+    if not torch.cuda.is_available():
+        raise M3THipError("m3t.jpeg needs the GPU: the M3T path has no CPU fallback")
+    rows = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1, GATHER_COLS))
+    addr = np.array([c.data_ptr() for c in chunks], np.int64)
+    size = np.array([c.numel() for c in chunks], np.int64)
+    addr_d = torch.from_numpy(addr).to(dst.device) if len(chunks) else None
+    rows_d = torch.from_numpy(rows.reshape(-1)).to(dst.device) if rows.size else None
+    _lib.check(_lib.load().m3t_jpeg_gather(addr.ctypes.data, size.ctypes.data, len(chunks), addr_d.data_ptr() if len(chunks) else None,
+                                           rows.ctypes.data, rows_d.data_ptr() if rows.size else None, rows.shape[0], dst.data_ptr(),
+                                           dst.numel() if dst_bytes is None else int(dst_bytes), _stream()), "m3t_jpeg_gather")
+    return dst
+
+
+class FrameStore:
+    """The scan bytes of a set of videos' JPEG frames on the current device, and the decode of a batch of windows from them.
+
+    videos: frame_records' mapping; window: frames per item.  The files are read and parsed once, here; each chunk is uploaded as it fills
+    through one pinned staging buffer and stays on the device.  decode(items) costs the host plan_frames and two small copies.
+    There is no CPU path.  Out of scope: a disk cache of the parsed store, a host-resident arena for a corpus that does not fit the device,
+    prefetch threads and DDP sharding, the file-system scan that produces `videos`, frames of different sizes in one store."""
+
+    def __init__(self, videos, window, chunk_bytes=1 << 30, on_unsupported="raise", threads=8):
+        self.window = int(window)
+        if self.window <= 0:
+            raise ValueError("FrameStore: window must be positive")
+        if not torch.cuda.is_available():
+            raise M3THipError("m3t.jpeg.FrameStore needs the GPU: the M3T path has no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.chunks, staging = [], [None]
+
+        def upload(index, chunk):
+            if staging[0] is None or staging[0].numel() < chunk.size:
+                staging[0] = torch.empty(chunk.size, dtype=torch.uint8).pin_memory()
+            staging[0].numpy()[:chunk.size] = chunk
+            self.chunks.append(staging[0][:chunk.size].to(self.device, non_blocking=True))
+            torch.cuda.current_stream().synchronize()           # the staging buffer is written again for the next chunk
+
+        self.records = frame_records(videos, chunk_bytes, on_unsupported, threads, _sink=upload)
+        self.names, self.height, self.width = self.records.names, self.records.height, self.records.width
+        self._addr = np.array([c.data_ptr() for c in self.chunks], np.int64)
+        self._size = np.array([c.numel() for c in self.chunks], np.int64)
+        self._addr_d = torch.from_numpy(self._addr).to(self.device)
+
+    @property
+    def nbytes(self):
+        """bytes of device memory the store holds"""
+        return int(self._size.sum()) + 8 * len(self.chunks)
+
+    def has_image(self, video):
+        """bool [frames of the video]: what TrackStore's videos[name]['has_image'] takes"""
+        return self.records.has_image(video)
+
+    def decode(self, items, out=None, order="bgr", walk="auto", sub_bytes=None, par_min_bytes=None, par_max_bytes=None, stats=False):
+        """items: [(video, start[, track_len])] -> (frames, frame_idx, status[, walk_stats]).  frames: uint8 [N, window, H, W, 3] on the
+        store's device (`out`, filled, where one of that shape is given): frame start + t of item n at [n, t], zeros where that frame is
+        absent or t >= track_len.  frame_idx: int32 [N, window] host tensor, video.frame_index per item: batch['video_frame_idx'] and what
+        video.ingest takes.  status: int32 [N window] on the device, jpeg.decode's.  order, walk, sub_bytes, par_min_bytes, par_max_bytes,
+        stats: jpeg.decode's.  plan_frames first (ValueError), then on the current stream and without a host synchronisation: one upload
+        of the two small tables, m3t_jpeg_gather into a fresh stream buffer, m3t_jpeg_decode_walk."""
+        if order not in ("bgr", "rgb"):
+            raise ValueError("FrameStore.decode: order must be 'bgr' or 'rgb'")
+        walk_ints = _walk_args(walk, sub_bytes, par_min_bytes, par_max_bytes)
+        p = plan_frames(self.records, items, self.window)
+        H, W, dev = self.height, self.width, self.device
+        if torch.cuda.current_device() != dev.index:
+            raise M3THipError("FrameStore.decode: the store lives on %s, the current device is cuda:%d" % (dev, torch.cuda.current_device()))
+        shape = (p.N, p.window, H, W, 3)
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == shape):
+                raise ValueError("FrameStore.decode: out must be uint8 %s" % (list(shape),))
+            if not (out.is_cuda and out.device == dev and out.is_contiguous()):
+                raise M3THipError("FrameStore.decode: out must be a contiguous tensor on %s" % (dev,))
+        frame_idx = torch.from_numpy(p.frame_idx)
+        m = int(p.rows.shape[0])
+        if m == 0:                                              # nothing to decode: zeros, without a launch of the decode
+            out = torch.zeros(shape, dtype=torch.uint8, device=dev) if out is None else out.zero_()
+            status = torch.zeros(p.n, dtype=torch.int32, device=dev)
+            return (out, frame_idx, status, torch.zeros(0, 2, dtype=torch.int32, device=dev)) if stats else (out, frame_idx, status)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        both = np.concatenate([p.rows.reshape(-1), p.tables])   # the gather's rows in front: 16 bytes each, the table behind them aligned
+        both_d = torch.from_numpy(both).to(dev, non_blocking=True)
+        rows_h, tables_h = both[:m * GATHER_COLS], both[m * GATHER_COLS:]
+        s_d = torch.empty(p.stream_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().m3t_jpeg_gather(self._addr.ctypes.data, self._size.ctypes.data, len(self.chunks), self._addr_d.data_ptr(),
+                                               rows_h.ctypes.data, both_d.data_ptr(), m, s_d.data_ptr(), p.stream_bytes, _stream()),
+                   "m3t_jpeg_gather")
+        status, walk_stats = _decode_on_device(s_d, tables_h, both_d[m * GATHER_COLS:], (p.n, p.n_segs, p.n_quant, p.n_huff, H, W), out, p.n,
+                                               order, walk_ints, stats, dev)
+        return (out, frame_idx, status, walk_stats) if stats else (out, frame_idx, status)
+
+    def batches(self, items, batch_size):
+        """decode() over consecutive slices of `items`; the last one may be short"""
+        batch_size = int(batch_size)
+        if batch_size <= 0:
+            raise ValueError("batches: batch_size must be positive")
+        for i in range(0, len(items), batch_size):
+            yield self.decode(items[i:i + batch_size])
