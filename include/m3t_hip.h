@@ -43,6 +43,14 @@ extern "C" {
                                   * time as the gru_v | gru_a level's) and for every backward level (the wide backward kernel is no slower than the narrow
                                   * one on twice the CUs).  m3t_gru_scan_workgroups() says what a call would launch.  Same results as without the flag up to
                                   * fp32 rounding (the backward kernel scales per producer workgroup instead of per 16-unit tile). */
+#define M3T_SCAN_SPREAD 64       /* m3t_gru_scan_* flags and m3t_gru_scan_workgroups: the caller schedules NOTHING beside this launch, so it may use CUs that
+                                  * would stand idle: row blocks of 8 clips instead of 16 -- twice the groups, every workgroup gathers, publishes and does
+                                  * cell math for 8 clips (half the bytes of the per-step gather; the 16-row MFMA tiles run half empty).  Taken only by the
+                                  * fp16x3 forward kernels (narrow or wide) and the wide producer-split backward kernel, only while
+                                  * n_scans * ceil(B / 8) * H / 16 fits the CUs, no progress marks are armed and the call has been handed an exchange
+                                  * arena (m3t_gru_scan_arena: the doubled exchange tiles live there only); every other launch ignores the flag.
+                                  * Forward results are bit-identical to the 16-row launch; backward results agree to fp32 rounding (a producer's scale
+                                  * is taken over 8 rows).  m3t_gru_scan_workgroups() says what a call with an arena would launch. */
 #define M3T_BF16 2               /* precision flag shared by m3t_sgemm (= M3T_GEMM_BF16), m3t_conv1d_* and m3t_gru_scan_*:
                                   * matmul operands rounded to bf16 (nearest even), fp32 accumulate, fp32 state/epilogue */
 /* m3t_sgemm flags: BACKGROUND caps residency at one workgroup per CU (for GEMMs that run on a side stream

@@ -397,11 +397,18 @@ typedef _Float16 pf16x8 __attribute__((ext_vector_type(8)));
 // requests per CU and step against 500-1000 lines for the gather itself, and the younger waves' stores queued for 1.4 us of a 5.2 us
 // wide backward step (wide forward 2.95 -> 2.51 us per step, wide backward 5.2 -> 3.4; with four cell-math waves -- the narrow form --
 // the extra LDS hop on the chain costs more than it saves: 3.42 vs 3.30).
-template <int NC, bool F16 = false, int UW = 1>
+// RB (M3T_SCAN_SPREAD): clips per row block.  RB = 8: a workgroup serves rows 0..7 of its 16-row tiles (the granules of rows 0-7 and 8-15 of
+// a unit pair are separate 128-byte lines: half the bytes) -- and because the exchange is priced per load INSTRUCTION, not per byte (masking the
+// lanes of rows 8-15 alone gained nothing: NOTEBOOK.md R13), the lanes those rows would have used load the odd unit pairs of rows 0-7 instead:
+// half the load instructions, one DPP rotate per odd pair behind the wait.  Operand rows 8-15 then hold whatever the rotate left there.  That
+// cannot reach a result: row i of an MFMA's output depends on row i of its A operand only, and cells of rows >= RB are never published,
+// stored or handed over (plive / pok / hok below).
+template <int NC, bool F16 = false, int UW = 1, int RB = 16>
 __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPtrs fp, ExPtrs ex, int B, int T, int G, int nrb,
                                                               unsigned* err) {
     constexpr bool CO = UW == 2;
     constexpr int ROWS = 16, KS = NC / 2, NTERM = F16 ? 2 : 3;
+    static_assert(RB == 16 || (RB == 8 && F16), "row blocks: 16 clips, or 8 in the fp16x3 form (the gather deals the units over lane bit 3 for 8 rows)");
     constexpr int H = 128 * NC, nch = H >> 4;
     // partial sums of the waves: [step parity][wave][unit tile][gate][row][UB + 1]; UW = 2 needs 102 KiB: dynamic LDS
     constexpr int RED_FLOATS = 2 * NW * UW * 3 * ROWS * (UB + 1);
@@ -416,7 +423,7 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPt
     const m3t_gru_fwd_desc d = g.d[s];
     const int tu = UW == 1 ? 0 : (tid >> 8);           // the unit tile this thread does cell math for
     const int ub = ubw * UW + tu;
-    const int j0 = ub * UB, r0 = rb * ROWS;
+    const int j0 = ub * UB, r0 = rb * RB;
 
     pbf16x8 wf[UW][KS][3][NTERM];                      // [unit tile][k-step][gate tile][term] (F16: fp16 bit patterns, two terms)
     float winv = 1.f;
@@ -492,7 +499,8 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPt
     const bool pw = tid < ROWS * UB * UW;
     const int prow = (ti >> 1) & 15, pu = ((ti >> 5) & 1) * 8 + 2 * ((ti >> 6) & 3) + (ti & 1);
     const int pb = r0 + prow, pj = j0 + pu;
-    const bool pok = pw && pb < B;
+    const bool plive = pw && prow < RB;                // publishes: live rows past the batch carry zeros (their consumers check every live row's tag)
+    const bool pok = plive && pb < B;
     float br = 0.f, bz = 0.f, bn = 0.f, hprev = 0.f;
     if (pw) { br = d.b_hh[pj]; bz = d.b_hh[H + pj]; bn = d.b_hh[2 * H + pj]; }
 
@@ -503,7 +511,9 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPt
     const size_t pub = grp + (size_t)ubw * UW * TILE + tid;
     // this lane's gather base inside a producer tile: chunk m = 2s + (q >> 1); granule pair 2*hr + 64 jp, hr = (q&1)*16 + row
     const int q = lane >> 4;
-    const size_t lane_off = (size_t)(wave + NW * (q >> 1)) * TILE + 2 * ((q & 1) * 16 + (lane & 15));
+    // (RB = 8: row lane & 7, and lane bit 3 picks the odd unit pair jp, 64 granules on)
+    const size_t lane_off = RB < ROWS ? (size_t)(wave + NW * (q >> 1)) * TILE + 2 * ((q & 1) * 16 + (lane & 7)) + 64 * ((lane >> 3) & 1)
+                                      : (size_t)(wave + NW * (q >> 1)) * TILE + 2 * ((q & 1) * 16 + (lane & 15));
     bool dead = false;
     int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
     __shared__ unsigned poll_fail[2];                  // by step parity
@@ -525,7 +535,7 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPt
     // memory-side identity of this thread (CO; else = its cell) and the LDS slots of the hand-over, padded one per 16
     const int hrow = CO ? (ti >> 4) : prow, hun = CO ? (ti & 15) : pu;
     const int hb = r0 + hrow, hj = j0 + hun;
-    const bool hok = pw && hb < B;
+    const bool hok = pw && hrow < RB && hb < B;
     const int hg = 64 * ((hun >> 1) & 3) + 2 * (hrow + 16 * (hun >> 3)) + (hun & 1);      // granule index of cell (hrow, hun)
     constexpr int SLOTS = 272;
     const int slot_h = tu * SLOTS + hg + (hg >> 4), slot_c = tu * SLOTS + ti + (ti >> 4);
@@ -1121,10 +1131,15 @@ __global__ __launch_bounds__(256) void wfrag_bwd3q_prep_kernel(PrepBwd3pArgs a, 
 
 // PROF: the in-kernel phase stamps (M3T_SCAN_PROF) live in an instantiation of their own -- their 14 VGPRs do not fit beside the rest
 // (that instantiation spills: its stamps overstate the step)
-template <int NC, bool PROF = false>
+// RB (M3T_SCAN_SPREAD): clips per row block, as in gru_persist_fwd6_kernel -- every lane gathers for a row < RB (half the load instructions),
+// operand rows >= RB are garbage, which stays inside rows >= RB of the products.  Everything that leaves a cell is masked by pok / hok (which
+// include row < RB): the workgroup's scale (bnd), the published terms, the bias sums, dh, the stored results and amx -- so neither the scale
+// nor any amax slot can see a garbage row.
+template <int NC, bool PROF = false, int RB = 16>
 __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragPtrs fp, ExPtrs ex, int B, int T, int G, int nrb,
                                                              unsigned* err) {
     constexpr int ROWS = 16, NP = NC / 2;              // NP: producer pairs per wave
+    static_assert(RB == 16 || (RB == 8 && !PROF), "row blocks: 16 clips, or 8 (the gather deals the units over lane bit 3 for 8 rows)");
     constexpr int H = 128 * NC, H3 = 3 * H, nchh = H >> 4;
     __shared__ float red[2][NW][2][ROWS][UB + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1134,7 +1149,7 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
     const m3t_gru_bwd_desc d = g.d[s];
     const int tu = tid >> 8;                           // the unit tile this thread does cell math for
     const int ub = ubw * 2 + tu;
-    const int j0 = ub * UB, r0 = rb * ROWS;
+    const int j0 = ub * UB, r0 = rb * RB;
 
     pu32x4 wb[2][3][NP][2];                            // [unit tile][gate][producer pair of this wave's K-slice][term]: 8 fp16 per lane, 96 VGPRs at H = 512
     float winv[2];                                     // 1 / (scale of the slice's W_hh^T)
@@ -1158,7 +1173,8 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
     const int ti = tid & 255;
     const int prow = ti & 15, pu = 8 * ((ti >> 4) & 1) + (ti >> 5);
     const int pb = r0 + prow, pj = j0 + pu;
-    const bool pok = pb < B;
+    const bool plive = prow < RB;                      // publishes: live rows past the batch carry zeros
+    const bool pok = plive && pb < B;
     float dh_carry = 0.f, z_next = 0.f;                // dh_{t+1} and z_{t+1} of this thread's (row, unit)
     float sb_r = 0.f, sb_z = 0.f, sb_n = 0.f, sb_nr = 0.f;   // sums over t of the gate gradients: the bias gradients of this clip
     float amx = 0.f;                                   // max |dr~|, |dz~|, |dn~| of this thread: the magnitude slot d.amax (fp16x3 GEMMs)
@@ -1170,7 +1186,9 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
     const size_t grp = (size_t)rb * nchh * TILE;
     const size_t pub = grp + (size_t)ubw * 2 * TILE + tid;
     // gather base of this lane inside the group: pair (wave + NW m) = tiles 2 (wave + NW m) + (q >> 1); granule e * 32 + (q & 1) * 16 + row
-    const size_t lane_src = (size_t)(2 * wave + (lane >> 5)) * TILE + ((lane >> 4) & 1) * 16 + (lane & 15);
+    // (RB = 8: row lane & 7, and lane bit 3 picks the odd unit e, 32 granules on)
+    const size_t lane_src = RB < ROWS ? (size_t)(2 * wave + (lane >> 5)) * TILE + ((lane >> 4) & 1) * 16 + (lane & 7) + 32 * ((lane >> 3) & 1)
+                                      : (size_t)(2 * wave + (lane >> 5)) * TILE + ((lane >> 4) & 1) * 16 + (lane & 15);
     bool dead = false;
     int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
     __shared__ unsigned poll_fail[2];                  // by step parity
@@ -1192,7 +1210,7 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
     f32x4 g4A, g4B;                                    // (r, z, n, W_hn h + b_hn) of this (row, unit, t)
     const int hrow = ti >> 4, hun = ti & 15;
     const int hb = r0 + hrow, hj = j0 + hun;
-    const bool hok = hb < B;
+    const bool hok = hrow < RB && hb < B;
     const int hg = (hun & 7) * 32 + (hun >> 3) * 16 + hrow;      // granule index of cell (hrow, hun)
     constexpr int SLOTS = 272;
     const int slot_h = tu * SLOTS + hg + (hg >> 4), slot_c = tu * SLOTS + ti + (ti >> 4);
@@ -1321,22 +1339,26 @@ static int poll_env_early(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
-struct Shape { int nc, rt, G, nrb, grid, active, slot_map; };
+struct Shape { int nc, rt, G, nrb, grid, active, slot_map, rb; };      // rb: clips per row block (16 * rt; 8: M3T_SCAN_SPREAD)
 
 // every scan of the level has the same H = 128 * NC (NC = 1..4: the k-chunks per wave are compile-time, so the gather
 // and the MFMA chain are straight-line code); RT = 1 when the 16-row grid fits one workgroup per CU, else 2
 template <typename D>
-bool level_shape(const D* d, int n, int B, Shape& sh, int uw = 1) {      // uw: 16-unit tiles per workgroup (the "wide" kernels: 2)
+bool level_shape(const D* d, int n, int B, Shape& sh, int uw = 1, bool spread = false) {      // uw: 16-unit tiles per workgroup (the "wide" kernels: 2)
     const int maxh = d[0].H;
     if (maxh % 128 != 0 || maxh > 512) return false;
     for (int i = 1; i < n; ++i)
         if (d[i].H != maxh) return false;
     sh.nc = maxh / 128;
     sh.rt = 0;
+    // spread (M3T_SCAN_SPREAD, asked for by launches that have the chip to themselves): row blocks of 8 clips while the 8-clip groups at
+    // one 16-unit tile per member fit the CUs -- counted like that for the wide kernels too: a wide launch exists to leave half the chip
+    // to its neighbours, and 4 x H=512 must not grow back to 256 workgroups.  Only the callers whose kernels have the form pass it.
+    const bool rb8 = spread && n * cdiv(B, 8) * (maxh / 16) <= device_cus();
     for (int rt = 1; rt <= 2; ++rt) {
         if (uw > 1 && rt > 1) break;
         const int members = maxh / 16 / uw;
-        const int nrb = cdiv(B, 16 * rt), G = n * nrb, active = G * members;
+        const int nrb = rb8 ? cdiv(B, 8) : cdiv(B, 16 * rt), G = n * nrb, active = G * members;
         // launched: 8 XCD slots x ceil(G / 8) groups per slot x H / 16 members (persist_map); blocks of empty slots exit at once,
         // so what must fit the chip at one workgroup per CU is the ACTIVE count
         if (active <= device_cus()) {
@@ -1348,7 +1370,7 @@ bool level_shape(const D* d, int n, int B, Shape& sh, int uw = 1) {      // uw: 
 #define M3T_SCAN_L2_MODE 2
 #endif
             constexpr int l2 = M3T_SCAN_L2_MODE;
-            sh.rt = rt; sh.nrb = nrb; sh.G = G; sh.active = active;
+            sh.rt = rt; sh.nrb = nrb; sh.G = G; sh.active = active; sh.rb = rb8 ? 8 : 16 * rt;
             // round 4: a WIDE launch with fewer than 8 groups puts each group on an XCD of its own as well (16 of its 32 CUs: the GEMMs beside
             // it still find CUs on every XCD, which is what sank this placement for the narrow 32-member groups in round 3): fusion level
             // backward 3.29 -> 3.15 us per step, its exchange served by L2 (traffic 2.5x -> ~1.1x algorithmic)
@@ -1771,6 +1793,30 @@ static int fwd_uw(const FwdGroup& g, int B, int T, int flags, const Shape& sh) {
     return ((flags & M3T_SCAN_WIDE) && fwd_is_f16(g, B, T, flags) && (sh.nc == 4 || sh.nc == 2) && sh.rt == 1 && wide_enabled()) ? 2 : 1;
 }
 
+// M3T_SCAN_SPREAD: the shape of the level's forward launch with 8-clip row blocks, where that form applies -- the fp16x3 kernels, twice the
+// groups still fit the CUs (level_shape); the launch path also requires that no progress marks are armed
+// The doubled exchange tiles live in the exchange ARENA only (m3t_gru_scan_arena; the workspace region a launch without one falls back to is
+// sized for 16-row blocks): `launching` also asks that this call has been handed one.
+static bool spread_exchange_ok(const Shape& s8, int n, int H, int kind, size_t gran_bytes, bool launching) {
+    if ((size_t)n * 2 * s8.nrb * (H / 16) * 256 * gran_bytes > ARENA_SIZE[kind]) return false;
+    return !launching || (g_arena != nullptr && g_arena_bytes >= ARENA_BYTES && ((uintptr_t)g_arena % 16) == 0);
+}
+static bool fwd_spread(const FwdGroup& g, int B, int T, int flags, int uw, Shape& sh, bool launching) {
+    if (!(flags & M3T_SCAN_SPREAD) || !fwd_is_f16(g, B, T, flags)) return false;
+    Shape s8;
+    if (!level_shape(g.d, g.n, B, s8, uw, true) || s8.rb != 8 || !spread_exchange_ok(s8, g.n, g.d[0].H, 1, 8, launching)) return false;
+    sh = s8;
+    return true;
+}
+// the same for the wide producer-split backward launch (the caller has established that the launch takes that kernel)
+static bool bwd_spread(const BwdGroup& g, int B, int flags, Shape& sh, bool launching) {
+    if (!(flags & M3T_SCAN_SPREAD)) return false;
+    Shape s8;
+    if (!level_shape(g.d, g.n, B, s8, 2, true) || s8.rb != 8 || !spread_exchange_ok(s8, g.n, g.d[0].H, 3, 16, launching)) return false;
+    sh = s8;
+    return true;
+}
+
 static int persist_fwd_launch_impl(const FwdGroup& g, const FragPtrs& fp, int B, int T, int flags, hipStream_t s);
 int persist_fwd_launch(const FwdGroup& g, const FragPtrs& fp, int B, int T, int flags, hipStream_t s) {
     ProgressTxn txn;
@@ -1783,6 +1829,7 @@ static int persist_fwd_launch_impl(const FwdGroup& g, const FragPtrs& fp, int B,
     if (!level_shape(g.d, g.n, B, sh) || !ensure_err_word()) return M3T_EINVAL;
     const int uw = fwd_uw(g, B, T, flags, sh);
     if (uw > 1 && !level_shape(g.d, g.n, B, sh, uw)) return M3T_EINVAL;
+    if (!persist_progress_armed()) fwd_spread(g, B, T, flags, uw, sh, true);
     {
         // round 4: a NARROW forward launch with fewer than 8 groups is XCD-aligned too (the fusion level: 4 groups of 32 fill 4 XCDs, exchange
         // served by L2: traffic 1.9x -> ~1.1x algorithmic, step 12.17 -> 12.10 ms).  Round 3 lost 0.3 ms with this placement because the
@@ -1806,6 +1853,13 @@ static int persist_fwd_launch_impl(const FwdGroup& g, const FragPtrs& fp, int B,
         // workgroup's publish, fail, and drive the common adaptive delay past what the cell-math waves need (2.63 us per step;
         // counted from the publish: 1.73; bf16x6: 1.83).  H = 512 is better without (2.55 vs 2.59, fusion level 2.28 vs 2.48).
         if (persist_fwd_uses_x6(g, B, T, flags) && !g.bf16 && (flags & M3T_GEMM_F16X3) && m3t_f16x3_enabled() && sh.nc == 2) ex.poll_align = 1;
+        // 8-clip row blocks (M3T_SCAN_SPREAD): with half the load instructions a gather attempt returns sooner, and the adaptive delay settles
+        // where most first attempts fail (2.57 us per step at 2 x H=512, the 16-row launch 2.28).  Fixed delays, measured at 4 .. 20: a plateau
+        // of 1.81-1.87 (12: 1.81; wide 2.19 against 2.49); H = 256, counted from the publish: 8 -> 1.37 against 1.65 (NOTEBOOK.md R13)
+        if (sh.rb == 8) {
+            ex.poll_fixed = sh.nc == 2 ? 8 : 12;
+            ex.poll_align = sh.nc == 2 ? 1 : 0;
+        }
     }
     const bool x6 = persist_fwd_uses_x6(g, B, T, flags);
     if (persist_progress_armed()) {                        // progress marks: the fp16x3 forward kernels carry them
@@ -1848,10 +1902,15 @@ static int persist_fwd_launch_impl(const FwdGroup& g, const FragPtrs& fp, int B,
             if (uw == 2) {
                 const size_t need = (size_t)2 * NW * 2 * 3 * 16 * (UB + 1) * sizeof(float)           // the kernel's partial sums (RED_FLOATS)
                                     + (size_t)2 * 2 * 272 * 36;                                      // + the staging slots (sx, so, sh)
-                const FwdKernel kk = sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 2> : gru_persist_fwd6_kernel<4, true, 2>;
+                const FwdKernel kk = sh.rb == 8 ? (sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 2, 8> : gru_persist_fwd6_kernel<4, true, 2, 8>)
+                                                : (sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 2> : gru_persist_fwd6_kernel<4, true, 2>);
                 const size_t dyn = exclusive_lds(kk, sh.active, need);
                 if (dyn < need) return M3T_EINVAL;
                 hipLaunchKernelGGL(kk, dim3(sh.grid), dim3(NT), dyn, s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
+            }
+            else if (sh.rb == 8) {
+                const FwdKernel kk = sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 1, 8> : gru_persist_fwd6_kernel<4, true, 1, 8>;
+                hipLaunchKernelGGL(kk, dim3(sh.grid), dim3(NT), exclusive_lds(kk, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
             }
             else if (sh.nc == 2) hipLaunchKernelGGL((gru_persist_fwd6_kernel<2, true>), dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_fwd6_kernel<2, true>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
             else hipLaunchKernelGGL((gru_persist_fwd6_kernel<4, true>), dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_fwd6_kernel<4, true>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
@@ -1907,6 +1966,7 @@ static int persist_bwd_launch_impl(const BwdGroup& g, const FragPtrs& fp, int B,
     const int uw = p3 ? 2 : 1;      // wide workgroups: two unit tiles each, half the grid
     if (uw > 1) {
         if (!level_shape(g.d, g.n, B, sh, uw)) return M3T_EINVAL;
+        if (!persist_progress_armed()) bwd_spread(g, B, flags, sh, true);      // (M3T_SCAN_SPREAD: 8-clip row blocks)
         ex.slot_map = sh.slot_map;
     }
     if (persist_progress_armed()) {                        // progress marks: the wide producer-split backward kernel carries them
@@ -1937,7 +1997,8 @@ static int persist_bwd_launch_impl(const BwdGroup& g, const FragPtrs& fp, int B,
             }
             { const int e = persist_take_after(s); if (e) return e; }
             persist_record_start(s);
-            const BwdKernel kq = sh.nc == 2 ? gru_persist_bwd3q_kernel<2> : (ex.prof ? gru_persist_bwd3q_kernel<4, true> : gru_persist_bwd3q_kernel<4>);
+            const BwdKernel kq = sh.rb == 8 ? (sh.nc == 2 ? gru_persist_bwd3q_kernel<2, false, 8> : gru_persist_bwd3q_kernel<4, false, 8>)
+                                 : sh.nc == 2 ? gru_persist_bwd3q_kernel<2> : (ex.prof ? gru_persist_bwd3q_kernel<4, true> : gru_persist_bwd3q_kernel<4>);
             const size_t need = (size_t)2 * 2 * 272 * 40;                    // the staging slots (sin4, sout, sin2)
             const size_t dyn = exclusive_lds(kq, sh.active, need);
             if (dyn < need) return M3T_EINVAL;
@@ -2044,6 +2105,7 @@ int persist_workgroups(int n, int H, int B, int T, int flags, bool backward) {
         const bool p3 = !b16 && persist_bwd_uses_x6(g, B, T, flags) && (flags & M3T_GEMM_F16X3) && m3t_f16x3_enabled() && bwd3p_enabled() &&
                         wide256 && (sh.nc == 4 || sh.nc == 2) && (unsigned long long)T + 1 < 0xffffffull;
         if (p3 && !level_shape(g.d, g.n, B, sh, 2)) return 0;
+        if (p3) bwd_spread(g, B, flags, sh, false);
         return sh.active;
     }
     FwdGroup g;
@@ -2051,7 +2113,9 @@ int persist_workgroups(int n, int H, int B, int T, int flags, bool backward) {
     g.n = n; g.bf16 = (flags & M3T_BF16) ? 1 : 0;
     for (int i = 0; i < n; ++i) { g.d[i].H = H; g.d[i].w_hh = reinterpret_cast<const float*>(16); }
     if (solo_fwd_ok(g, B, T, flags) || !level_shape(g.d, g.n, B, sh)) return 0;
-    if (fwd_uw(g, B, T, flags, sh) == 2 && !level_shape(g.d, g.n, B, sh, 2)) return 0;
+    const int uw = fwd_uw(g, B, T, flags, sh);
+    if (uw == 2 && !level_shape(g.d, g.n, B, sh, 2)) return 0;
+    fwd_spread(g, B, T, flags, uw, sh, false);
     return sh.active;
 }
 }  // namespace m3t_gru

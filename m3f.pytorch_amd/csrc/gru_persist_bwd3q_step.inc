@@ -17,6 +17,15 @@
 #pragma unroll
             for (int m = 0; m < NP; ++m) {
                 const u32x4* q = src + (size_t)m * NW * 2 * TILE;
+                if (RB < ROWS)
+                    // 8-clip row blocks: HALF the load instructions -- lane (r = lane & 7, hb = (lane >> 3) & 1) takes the units e = 2 i + hb
+                    // of row r (lane_src); the odd units move to the lanes of rows 0..7 behind the wait (DPP, below)
+                    asm volatile("global_load_dwordx4 %0, %4, off sc1\n\t"
+                                 "global_load_dwordx4 %1, %4, off offset:1024 sc1\n\t"
+                                 "global_load_dwordx4 %2, %4, off offset:2048 sc1\n\t"
+                                 "global_load_dwordx4 %3, %4, off offset:3072 sc1"
+                                 : "=&v"(v[m][0]), "=&v"(v[m][2]), "=&v"(v[m][4]), "=&v"(v[m][6]) : "v"(q) : "memory");
+                else
                 asm volatile("global_load_dwordx4 %0, %8, off sc1\n\t"
                              "global_load_dwordx4 %1, %8, off offset:512 sc1\n\t"
                              "global_load_dwordx4 %2, %8, off offset:1024 sc1\n\t"
@@ -34,7 +43,7 @@
 #pragma unroll
             for (int m = 0; m < NP; ++m)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
+                for (int e = 0; e < 8; e += (RB < ROWS ? 2 : 1)) {
                     asm volatile("" : "+v"(v[m][e]));              // defined only after the wait above
                     ok = ok && ((v[m][e].w & 0xffffffu) == tag);
                 }
@@ -51,6 +60,15 @@
         acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int m = 0; m < NP; ++m) {
+            if (RB < ROWS) {
+                // the odd units sit in the lanes 8 up (same row r): rotate each row of 16 lanes by 8.  Lanes 8..15 of a row of 16 end up with
+                // operand rows 8..15 that mean nothing -- and reach nothing: MFMA output row i reads operand row i only
+#pragma unroll
+                for (int e = 0; e < 8; e += 2)
+#pragma unroll
+                    for (int gt = 0; gt < 3; ++gt)
+                        v[m][e + 1][gt] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v[m][e][gt], 0x128, 0xf, 0xf, false);      // row_ror:8
+            }
             f32x4 at[2];
             at[0] = at[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -137,7 +155,7 @@
         }
         float psc, pisc;
         m3t_f16_scale(mxb, psc, pisc);
-        if (step + 1 < T && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)
+        if (step + 1 < T && (RB == ROWS || plive) && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)
             u32x4 gq;
             gq.x = bwd3p_split(p0 * psc); gq.y = bwd3p_split(p1 * psc); gq.z = bwd3p_split(p2 * psc);
             gq.w = ((ex.tag_base + (unsigned)step + 1u) & 0xffffffu) | ((__float_as_uint(psc) >> 23) << 24);

@@ -21,6 +21,13 @@
 #pragma unroll
                 for (int k = 0; k < KS; ++k) {
                     const unsigned long long* qp = src + (size_t)(2 * k) * NW * TILE;
+                    if (RB < ROWS)
+                        // 8-clip row blocks: HALF the load instructions -- lane (r = lane & 7, hb = (lane >> 3) & 1) takes unit pair jp = hb
+                        // and jp = 2 + hb of row r (lane_off8); the odd pairs move to the lanes of rows 0..7 behind the wait (DPP, below)
+                        asm volatile("global_load_dwordx4 %0, %2, off sc1\n\t"
+                                     "global_load_dwordx4 %1, %2, off offset:1024 sc1"
+                                     : "=&v"(v[k][0]), "=&v"(v[k][2]) : "v"(qp) : "memory");
+                    else
                     asm volatile("global_load_dwordx4 %0, %4, off sc1\n\t"
                                  "global_load_dwordx4 %1, %4, off offset:512 sc1\n\t"
                                  "global_load_dwordx4 %2, %4, off offset:1024 sc1\n\t"
@@ -33,7 +40,7 @@
 #pragma unroll
                 for (int k = 0; k < KS; ++k)
 #pragma unroll
-                    for (int jp = 0; jp < 4; ++jp) {
+                    for (int jp = 0; jp < 4; jp += (RB < ROWS ? 2 : 1)) {
                         asm volatile("" : "+v"(v[k][jp]));
                         ok = ok && ((v[k][jp].y >> 16) == tag) && ((v[k][jp].w >> 16) == tag);
                     }
@@ -48,6 +55,17 @@
                 // registers die here), then one unit tile at a time (12 accumulator registers live instead of 24: the wide form with the
                 // coalesced hand-over spilled into scratch -- vector-memory operations in front of the gather's wait -- without this)
                 pf16x8 F1[KS], F2[KS];
+                if (RB < ROWS) {
+                    // the odd unit pairs sit in the lanes 8 up (same row r): rotate each row of 16 lanes by 8.  Lanes 8..15 of a row of 16
+                    // end up with operand rows 8..15 that mean nothing -- and reach nothing: MFMA output row i reads operand row i only
+#pragma unroll
+                    for (int k = 0; k < KS; ++k)
+#pragma unroll
+                        for (int jp = 0; jp < 4; jp += 2) {
+                            v[k][jp + 1].x = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v[k][jp].x, 0x128, 0xf, 0xf, false);      // row_ror:8
+                            v[k][jp + 1].z = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v[k][jp].z, 0x128, 0xf, 0xf, false);
+                        }
+                }
 #pragma unroll
                 for (int k = 0; k < KS; ++k) {
                     pu32x4 a1, a2;
@@ -155,7 +173,7 @@
             float c_xr = CUR(xr), c_xz = CUR(xz), c_xn = CUR(xn);
             if (CO) { const f32x4 x4 = sx[PARV * UW * SLOTS + slot_c]; c_xr = x4[0]; c_xz = x4[1]; c_xn = x4[2]; }
             const GateFwd c = gru_cell_fwd(c_xr, c_xz, c_xn, hr, hz, hn, hprev);
-            if (step + 1 < T && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)
+            if (step + 1 < T && (RB == ROWS || plive) && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)
                 const float hv = pok ? (g.bf16 ? rbf(c.h) : c.h) : 0.f;
                 unsigned long long gq;
                 if (F16) {                                 // two fp16 terms of 2^14 h (|h| <= 1)

@@ -20,6 +20,7 @@ M3T_SCAN_FP32 = 4
 M3T_SCAN_WHH = 8
 M3T_SCAN_FAULT = 16
 M3T_SCAN_WIDE = 32        # room for a second persistent scan beside this one (include/m3t_hip.h)
+M3T_SCAN_SPREAD = 64      # nothing runs beside this launch: 8-clip row blocks on the idle CUs (include/m3t_hip.h)
 M3T_MAX_SCANS = 8
 M3T_JPEG_TRUNC, M3T_JPEG_CODE, M3T_JPEG_RST, M3T_JPEG_EXTRA = 1, 2, 4, 8      # status bits of m3t_jpeg_decode (include/m3t_hip.h)
 

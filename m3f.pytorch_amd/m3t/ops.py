@@ -824,6 +824,15 @@ FORCE_WIDE_FWD = [False]    # tests: every forward scan asks for the wide form (
 SCAN_FP32 = [False]         # tests: keep the persistent forward scan on fp32 MFMAs (bit-identical to the per-step kernels)
 
 
+# 8-clip row blocks (M3T_SCAN_SPREAD, include/m3t_hip.h) for the scan launches of a stack that has the chip to itself -- the fusion GRU: its
+# forward scans (nothing is scheduled beside them) and its first backward scan (only the head's small weight gradients exist by then).  Its
+# layer-0 backward scan shares the chip with layer 1's weight gradients, which end before it does: kept on its own A/B (C3 step 10.88 ms
+# against 11.00 without it, NOTEBOOK.md R13; M3T_SCAN_SPREAD_BWD0=0 takes it out).  M3T_SCAN_SPREAD=0: the 16-clip geometry everywhere
+# (A/B runs).  The encoder level and the audio stack never ask: the CUs they leave are each other's and the GEMMs'.
+SPREAD = [os.environ.get("M3T_SCAN_SPREAD", "1") != "0"]
+SPREAD_BWD0 = [os.environ.get("M3T_SCAN_SPREAD_BWD0", "1") != "0"]
+
+
 _FENCED = [False]     # set by the interleaved schedule of _MultiBiGRU: its side-stream scans are fenced by events
 
 
@@ -1200,10 +1209,10 @@ class _MultiBiGRU(torch.autograd.Function):
 
         alone = not _interleaved(groups) and all(kind == "main" for kind, _ in groups)   # nothing runs beside these GEMMs
 
-        def level_fwd(l, idxs, scan, after=None, wide=False, progress=None):
+        def level_fwd(l, idxs, scan, after=None, wide=False, progress=None, spread=False):
             """scan=False: the input projections of layer l for the stacks idxs; scan=True: their grouped scan (its scan
             kernels fenced behind the event `after`; wide: the launch leaves room for a second persistent scan; progress: time bounds
-            of the launch's progress marks -- returns their `need` table)"""
+            of the launch's progress marks -- returns their `need` table; spread: nothing runs beside the launch, it may take idle CUs)"""
             descs = []
             for s in idxs:
                 H = Hs[s]
@@ -1219,7 +1228,8 @@ class _MultiBiGRU(torch.autograd.Function):
                                                 _vp(gates[l][s], d * B * T * 4 * H), _vp(h_ns[s], (2 * l + d) * B * H),
                                                 H, d, 6 * H, d * 3 * H, outs[l][s].stride(1), d * H))
             if scan:
-                return _scan_fwd(descs, B, T, prec | (_lib.M3T_SCAN_WIDE if (wide or FORCE_WIDE_FWD[0]) else 0), after,
+                return _scan_fwd(descs, B, T, prec | (_lib.M3T_SCAN_WIDE if (wide or FORCE_WIDE_FWD[0]) else 0)
+                                 | (_lib.M3T_SCAN_SPREAD if spread else 0), after,
                                  None if progress is None else (_progress_counters(dev), progress))
 
         def chunk_plan(idxs, wide):
@@ -1357,7 +1367,8 @@ class _MultiBiGRU(torch.autograd.Function):
                     for l in range(L):
                         if l == 0 or tb is None:
                             level_fwd(l, idxs, False)
-                        need = level_fwd(l, idxs, True, progress=tb if l + 1 < L else None)
+                        need = level_fwd(l, idxs, True, progress=tb if l + 1 < L else None,
+                                         spread=SPREAD[0] and kind == "main" and alone and len(idxs) == 1)
                         if tb is not None and l + 1 < L:
                             proj_pieces(l + 1, idxs, tb, need, stream)
             for kind, _ in groups:
@@ -1577,7 +1588,7 @@ class _MultiBiGRU(torch.autograd.Function):
                     _wait_progress(ctr_, 1, need_[2])
             fn()
 
-        def level_scan(l, idxs, after=None, wide=False, progress=None):
+        def level_scan(l, idxs, after=None, wide=False, progress=None, spread=False):
             """every BACKWARD level asks for the wide form (the library applies it where it exists: H = 512 in the fp16x3 mode), not only
             the level that makes room for the audio scans: the wide backward kernel is no slower than the narrow one on half the CUs
             (fusion level 3.15 vs 3.30 us per step, exchange served by one XCD's L2) and the weight-gradient GEMMs get the rest;
@@ -1601,9 +1612,12 @@ class _MultiBiGRU(torch.autograd.Function):
                                             _vp(wfq[(l, s, d)]) if (l, s, d) in wfq else None))      # (dout and out share the layout)
             chain = _ws_tag(dev)
             sm = None
-            if progress is None and chain in held:
+            # (a launch with progress marks keeps the 16-clip geometry: a spread launch takes no start marks, so that M3T_SCAN_FIRST stays a
+            # matter of timing only -- the weight gradients held for it are released right behind the launch)
+            if progress is None and chain in held and not spread:
                 sm = start_marks(idxs)
-            need = _scan_bwd(descs, B, T, prec | (_lib.M3T_SCAN_WHH if direct_whh else 0) | _lib.M3T_SCAN_WIDE, after,
+            need = _scan_bwd(descs, B, T, prec | (_lib.M3T_SCAN_WHH if direct_whh else 0) | _lib.M3T_SCAN_WIDE
+                             | (_lib.M3T_SCAN_SPREAD if spread else 0), after,
                              None if (progress is None and sm is None) else (_progress_counters(dev), progress if progress is not None else sm))
             if progress is not None:
                 pending[(l, tuple(idxs))] = (progress, need)
@@ -1775,7 +1789,10 @@ class _MultiBiGRU(torch.autograd.Function):
                     stream.wait_stream(main)
                 with on_stream(stream):
                     for l in range(L - 1, -1, -1):
-                        level_scan(l, idxs, progress=chunk_plan(l, idxs) if (kind == "main" and len(groups) == 1) else None)
+                        # (8-clip row blocks: see SPREAD -- the stack's first backward scan; layer 0 runs beside layer 1's weight gradients)
+                        level_scan(l, idxs, progress=chunk_plan(l, idxs) if (kind == "main" and len(groups) == 1) else None,
+                                   spread=(SPREAD[0] and kind == "main" and len(groups) == 1 and len(idxs) == 1
+                                           and (l == L - 1 or SPREAD_BWD0[0])))
                         level_gemms(l, idxs)
             for kind, _ in groups:
                 if kind == "side":
