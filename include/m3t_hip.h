@@ -862,6 +862,46 @@ int m3t_eval_gather(const float* rows, long long W, int Q, int T, const long lon
 int m3t_eval_metrics(const double* part, long long W, double* out5, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * The expression head in the evaluation epoch (csrc/evaluate_expr.hip; m3t/evaluate.py, Evaluator(expr=True)).  The
+ * reference trains the head (model.py:169-182) and never validates it; these entry points extend its masking and argmax
+ * (model.py:171-182) and its stitching (model.py:261-297, 354-366) to the 7 expression logits, channels 0..6 of y_hat
+ * (model.py:175).  Class rule everywhere: argmax over the 7 logits as torch.argmax (the first maximal index; a NaN counts
+ * as maximal, so the first NaN wins); class -1 = none.  Classes travel as int8.  Counts are exact integers (LDS integer
+ * atomics); no float atomics, every floating sum in a fixed order.
+ *
+ * m3t_eval_append_mtl, once per batch (model.py:171-182 for the mask and the argmax): everything m3t_eval_append does --
+ * rows and part carry the same bits -- and, with C >= 9, expr_rows [N][7][T] fp32 = the 7 logits of frame t < length, 0
+ * past it (inputs not read).  With labels (label_valence / label_arousal / class_expr / expr_valid: all or none):
+ * class_expr [N][T] int64 (clipped to 0..6), expr_valid [N][T] one byte per frame; expr_gt [N][T] int8 = the label where
+ * t < length and expr_valid, else -1; conf [N][7][7] int32 = the number of those frames with label g and prediction p. */
+int m3t_eval_append_mtl(const float* y_hat, int N, int T, int C, const float* label_valence, const float* label_arousal,
+                        const long long* class_expr, const unsigned char* expr_valid, const long long* length, float* rows,
+                        double* part, float* expr_rows, signed char* expr_gt, int* conf, void* stream);
+/* m3t_eval_gather_expr, once per epoch (model.py:261-297, 354-366): the plan tables of m3t_eval_gather.  logit_tracks
+ * [7][F] fp32: per channel the sequence of m3t_eval_gather (zeros, += per covering segment in ascending start order,
+ * * 0.5f from halve_from on).  pred [F] int8 = the argmax of the stitched logits, -1 for a frame no segment covers.
+ * gt [F] int8 (nullable; needs expr_gt [W][T]) = the expr_gt of the first covering segment in start order, else -1. */
+int m3t_eval_gather_expr(const float* expr_rows, const signed char* expr_gt, long long W, int T, const long long* seg_dst,
+                         const long long* seg_len, const long long* seg_row, const long long* vid_seg_off,
+                         const long long* vid_frame_off, int V, long long F, long long halve_from, float* logit_tracks,
+                         signed char* pred, signed char* gt, void* stream);
+/* m3t_eval_expr_metrics (the figures model.py:180-181 starts: acc_expr): conf [W][7][7] int32 ([label][prediction]) summed
+ * over W -> out24 fp64 = accuracy, macro-F1, score = 0.67 F1 + 0.33 accuracy (the expression track of ABAW 2020), then
+ * precision [7], recall [7], F1 [7].  F1_c = 2 tp / (2 tp + fp + fn); macro-F1 = the mean over the classes with
+ * tp + fp + fn > 0, summed in class order (scikit-learn's f1_score(average='macro')).  A zero denominator is 0 / 0 = NaN:
+ * every figure without a valid frame, precision of a class never predicted, recall of a class never labelled. */
+int m3t_eval_expr_metrics(const int* conf, long long W, double* out24, void* stream);
+/* Mode filter over class tracks (int8, the offsets table of m3t_smooth_tracks), odd window = 2h+1 > 0 (else M3T_EINVAL):
+ * out[i] = the most frequent class among c[max(0,i-h) .. min(n-1,i+h)] of its track, -1 ignored, no padding; a tie goes to
+ * c[i] when it is among the tied classes, else to the smallest; nothing but -1 in reach gives -1.  window 1: identity. */
+int m3t_expr_mode_tracks(const signed char* c, const long long* offsets, int n_tracks, int window, signed char* out,
+                         void* stream);
+/* conf [n_tracks][7][7] int32 = per track the frames with gt = g >= 0 and pred = p >= 0; acc [n_tracks] fp64 (nullable) =
+ * the track's accuracy, NaN without such a frame.  m3t_eval_expr_metrics scores conf with W = n_tracks. */
+int m3t_expr_track_conf(const signed char* pred, const signed char* gt, const long long* offsets, int n_tracks, int* conf,
+                        double* acc, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Audio front-end: the glue kernels of the log-Mel pipeline that the reference runs offline with
  * librosa (process/extract_melspec.py:13-20) and the context stacking of models/dataset.py:83-95.  The DFT and the
  * mel projection themselves are m3t_sgemm calls (see m3t/audio.py).

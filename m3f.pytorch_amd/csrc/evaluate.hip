@@ -6,66 +6,18 @@
 //   ccc_tracks    per report: the per-video CCCs of the smoothed tracks, all videos x {valence, arousal} in one launch
 // Tiny, latency-bound work: plain fp32 / fp64, 256-thread workgroups, no atomics, every sum in a fixed order
 // (block_sum_f64, the reduction of postproc.hip), so a result does not depend on the run.
-#include "common.h"
+#include "evaluate_va.h"
 
 namespace {
 
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-// One workgroup per clip n.  rows[n][q][t], q = v_pred, a_pred (, v_gt, a_gt); a frame t >= length[n] is written as 0 and
-// its inputs are never loaded.  part[n][k][0..7) = n, sum p, sum g, sum p^2, sum g^2, sum p g, sum (p - g)^2 over the valid
-// frames (t < length, |v_gt| <= 1 and |a_gt| <= 1: a NaN label fails the comparison), k = valence, arousal.
+// One workgroup per clip n: eval_append_va (evaluate_va.h), the text m3t_eval_append_mtl runs too.
 __global__ __launch_bounds__(256) void eval_append_kernel(const float* __restrict__ y, int T, int C,
                                                           const float* __restrict__ lv, const float* __restrict__ la,
                                                           const long long* __restrict__ length, float* __restrict__ rows,
                                                           double* __restrict__ part) {
     __shared__ double red[256];
     const long n = blockIdx.x;
-    const long long ln = length[n];
-    const int len = ln < 0 ? 0 : (ln > T ? T : (int)ln);
-    const int Q = lv ? 4 : 2;
-    const float* yn = y + n * (long)T * C + (C - 2);
-    float* rn = rows + n * (long)Q * T;
-    double m[13];
-#pragma unroll
-    for (int k = 0; k < 13; ++k) m[k] = 0.0;
-    for (int t = threadIdx.x; t < T; t += blockDim.x) {
-        const bool in = t < len;
-        const float pv = in ? yn[(long)t * C] : 0.f, pa = in ? yn[(long)t * C + 1] : 0.f;
-        rn[t] = pv;
-        rn[T + t] = pa;
-        if (lv) {
-            const float gv = in ? lv[n * T + t] : 0.f, ga = in ? la[n * T + t] : 0.f;
-            rn[2 * T + t] = gv;
-            rn[3 * T + t] = ga;
-            if (in && fabsf(gv) <= 1.f && fabsf(ga) <= 1.f) {
-                const double p0 = pv, g0 = gv, p1 = pa, g1 = ga;
-                m[0] += 1.0;
-                m[1] += p0; m[2] += g0; m[3] += p0 * p0; m[4] += g0 * g0; m[5] += p0 * g0; m[6] += (p0 - g0) * (p0 - g0);
-                m[7] += p1; m[8] += g1; m[9] += p1 * p1; m[10] += g1 * g1; m[11] += p1 * g1; m[12] += (p1 - g1) * (p1 - g1);
-            }
-        }
-    }
-    if (!lv) return;
-#pragma unroll
-    for (int k = 0; k < 13; ++k) m[k] = block_sum_f64(m[k], red);
-    if (threadIdx.x == 0) {
-        double* pn = part + n * 14;
-        pn[0] = m[0];
-        pn[7] = m[0];
-#pragma unroll
-        for (int k = 1; k < 7; ++k) { pn[k] = m[k]; pn[7 + k] = m[6 + k]; }
-    }
+    eval_append_va(y, n, T, C, eval_clip_len(length[n], T), lv, la, rows, part, red);
 }
 
 // One thread per output frame.  Video v owns the frames vid_frame_off[v] .. vid_frame_off[v+1] of every track and the

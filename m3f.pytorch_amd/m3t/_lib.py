@@ -166,6 +166,11 @@ SIGNATURES = {
     "m3t_eval_gather": [_f, C.c_longlong, _i, _i, _f, _f, _f, _f, _f, _i, C.c_longlong, C.c_longlong, _f, _s],
     "m3t_eval_metrics": [_f, C.c_longlong, _f, _s],
     "m3t_ccc_tracks": [_f, _f, _f, _f, _i, _i, _f, _s],
+    "m3t_eval_append_mtl": [_f, _i, _i, _i] + [_f] * 10 + [_s],
+    "m3t_eval_gather_expr": [_f, _f, C.c_longlong, _i, _f, _f, _f, _f, _f, _i, C.c_longlong, C.c_longlong, _f, _f, _f, _s],
+    "m3t_eval_expr_metrics": [_f, C.c_longlong, _f, _s],
+    "m3t_expr_mode_tracks": [_f, _f, _i, _i, _f, _s],
+    "m3t_expr_track_conf": [_f, _f, _f, _i, _f, _f, _s],
     "m3t_frame_window": [_f, C.c_longlong, _i, _i, _i, _f, _f, C.c_longlong, _s],
     "m3t_power_spectrum": [_f, C.c_longlong, _i, _f, _s],
     "m3t_power_to_db": [_f, C.c_longlong, C.c_float, C.c_float, _f, _f, _z, _s],

@@ -10,6 +10,11 @@ module computes the same tracks bit for bit and the same metrics from fp64 sums.
   res.metrics, res.to_dicts(), res.save('predictions_val.pt'), res.smoothed_report()
 
 `plan_tracks` is the index arithmetic alone (numpy, no GPU).  There is no CPU path for the rest.
+
+Evaluator(..., expr=True) also carries the expression head (channels 0..6 of a 9-channel `mtl` output, which the reference
+trains, model.py:169-182, and never validates; csrc/evaluate_expr.hip): add() is still one launch (m3t_eval_append_mtl),
+finish() still one read-back, and the result gains res.expr (logits [7, F], pred [F], gt [F]), val_acc_expr / val_f1_expr /
+val_score_expr, res.expr_metrics and res.expr_report().  `expr_metrics_from_confusion` is the same arithmetic on the host.
 """
 import ctypes as C
 from collections import namedtuple
@@ -20,7 +25,14 @@ import torch
 from . import _lib
 
 METRIC_KEYS = ("val_ccc_v", "val_ccc_a", "val_mse_v", "val_mse_a", "val_loss")
+EXPR_METRIC_KEYS = ("val_acc_expr", "val_f1_expr", "val_score_expr")
+EXPR_CLASSES = ("Neutral", "Anger", "Disgust", "Fear", "Happiness", "Sadness", "Surprise")
+N_EXPR = len(EXPR_CLASSES)
 NO_HALVING = 1 << 62
+
+# the expression tracks of an epoch on the device: logits [7, F] fp32, pred [F] int8 (-1: no window covers the frame),
+# gt [F] int8 (-1: not annotated; None without labels)
+ExprTracks = namedtuple("ExprTracks", "logits pred gt")
 
 # names: videos in first-seen order; nframes [V]; frame_off / seg_off [V+1]; seg_dst / seg_len / seg_row [S], grouped by
 # video and sorted by destination (seg_row = the window's index in the order it was added); halve_from: see m3t_eval_gather
@@ -68,6 +80,38 @@ def plan_tracks(names, starts, lengths, window, overlap):
                 int(window) // 2 if overlap else NO_HALVING)
 
 
+def expr_metrics_from_confusion(conf):
+    """conf [..., 7, 7] integer counts, conf[g][p] = frames with label g and prediction p (leading axes are summed: windows,
+    videos, shards) -> what m3t_eval_expr_metrics writes, in numpy float64: {'acc', 'f1', 'score', 'precision' [7],
+    'recall' [7], 'f1_class' [7]}.  F1_c = 2 tp / (2 tp + fp + fn); f1 = the mean over the classes with tp + fp + fn > 0 in
+    class order (scikit-learn's f1_score(average='macro')); score = 0.67 f1 + 0.33 acc (ABAW 2020, expression track).  A zero
+    denominator is NaN: everything without a frame, precision of a class never predicted, recall of one never labelled."""
+    c = np.asarray(conf)
+    if c.ndim < 2 or c.shape[-2:] != (N_EXPR, N_EXPR):
+        raise ValueError("expr_metrics_from_confusion: conf must be [..., %d, %d], not %s" % (N_EXPR, N_EXPR, list(c.shape)))
+    c = c.astype(np.int64).reshape(-1, N_EXPR, N_EXPR).sum(0)
+    tp = np.diag(c)
+    fp, fn = c.sum(0) - tp, c.sum(1) - tp
+    f = lambda a: a.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        prec, rec, f1c = f(tp) / f(tp + fp), f(tp) / f(tp + fn), f(2 * tp) / f(2 * tp + fp + fn)
+        present = (tp + fp + fn) > 0
+        f1sum = np.float64(0.0)
+        for k in range(N_EXPR):
+            if present[k]:
+                f1sum = f1sum + f1c[k]
+        acc = np.float64(tp.sum()) / np.float64(c.sum())
+        f1 = f1sum / np.float64(int(present.sum()))
+    return {"acc": float(acc), "f1": float(f1), "score": float(np.float64(0.67) * f1 + np.float64(0.33) * acc),
+            "precision": prec, "recall": rec, "f1_class": f1c}
+
+
+def _expr_table(vals):
+    """out24 of m3t_eval_expr_metrics (a list of floats) -> the three figures and the per-class table"""
+    return vals[:3], {"precision": dict(zip(EXPR_CLASSES, vals[3:10])), "recall": dict(zip(EXPR_CLASSES, vals[10:17])),
+                      "f1": dict(zip(EXPR_CLASSES, vals[17:24]))}
+
+
 def _lib_and_stream():
     from .ops import lib, _stream          # (ops imports torch.distributed and the GRU plumbing: not needed for plan_tracks)
     return lib(), _stream()
@@ -87,15 +131,27 @@ class Evaluator:
     """Collects one epoch of windows on the device.  add() queues work on the current stream and returns; nothing in it
     waits for the device."""
 
-    def __init__(self, window, overlap, with_gt=True):
-        self.window, self.overlap, self.with_gt = int(window), bool(overlap), bool(with_gt)
+    def __init__(self, window, overlap, with_gt=True, expr=False):
+        self.window, self.overlap, self.with_gt, self.expr = int(window), bool(overlap), bool(with_gt), bool(expr)
+        self._reset()
+
+    def _reset(self):
         self._rows, self._part, self._names, self._starts, self._lengths, self._keep = [], [], [], [], [], []
+        self._erows, self._egt, self._conf = [], [], []
 
     def add(self, y_hat, batch):
         """y_hat [N, T, C] (fp32, CUDA): the model's output for `batch`; valence = channel C-2, arousal = C-1.  batch:
         'vid_name' (N names), 'start', 'length' ([N] integer tensors, CPU or CUDA) and, with_gt, 'label_valence' /
-        'label_arousal' [N, T]."""
+        'label_arousal' [N, T].  expr=True: C >= 9, the expression logits are channels 0..6, and with_gt also takes
+        'class_expr' (integer classes) and 'expr_valid' [N, T], CPU or CUDA."""
         y = y_hat.detach()
+        if self.expr:                                # (what can be said without the device comes first)
+            if y.dim() == 3 and y.size(2) < N_EXPR + 2:
+                raise ValueError("Evaluator.add: expr=True needs the %d expression logits and valence, arousal (C >= %d); y_hat has %d "
+                                 "channels -- fusion_type att_dec and losses without `mtl` have no expression head" % (N_EXPR, N_EXPR + 2, y.size(2)))
+            for k in ("class_expr", "expr_valid") if self.with_gt else ():
+                if k not in batch:
+                    raise ValueError("Evaluator.add: expr=True with labels needs batch[%r]" % k)
         if not y.is_cuda or y.dtype != torch.float32 or y.dim() != 3 or y.size(2) < 2:
             raise _lib.M3THipError("Evaluator.add: y_hat must be a float32 CUDA tensor [N, T, C >= 2]")
         y = y.contiguous()
@@ -120,13 +176,30 @@ class Evaluator:
             lv, la = up(batch["label_valence"], torch.float32), up(batch["label_arousal"], torch.float32)
             if tuple(lv.shape) != (N, T) or tuple(la.shape) != (N, T):
                 raise ValueError("Evaluator.add: labels must be [%d, %d]" % (N, T))
+        cls = vld = None
+        if self.expr and self.with_gt:
+            cls, vld = up(torch.as_tensor(batch["class_expr"]), torch.int64), up(torch.as_tensor(batch["expr_valid"]), torch.uint8)
+            if tuple(cls.shape) != (N, T) or tuple(vld.shape) != (N, T):
+                raise ValueError("Evaluator.add: class_expr and expr_valid must be [%d, %d]" % (N, T))
         Q = 4 if self.with_gt else 2
         rows = torch.empty(N, Q, T, dtype=torch.float32, device=dev)
         part = torch.empty(N, 2, 7, dtype=torch.float64, device=dev) if self.with_gt else None
+        opt = lambda t: _ptr(t) if t is not None else None
         lib, stream = _lib_and_stream()
-        rc = lib.m3t_eval_append(_ptr(y), N, T, Cn, _ptr(lv) if self.with_gt else None, _ptr(la) if self.with_gt else None,
-                                 _ptr(len_dev), _ptr(rows), _ptr(part) if self.with_gt else None, stream)
-        _lib.check(rc, "m3t_eval_append")
+        if self.expr:
+            erows = torch.empty(N, N_EXPR, T, dtype=torch.float32, device=dev)
+            egt = torch.empty(N, T, dtype=torch.int8, device=dev) if self.with_gt else None
+            conf = torch.empty(N, N_EXPR, N_EXPR, dtype=torch.int32, device=dev) if self.with_gt else None
+            rc = lib.m3t_eval_append_mtl(_ptr(y), N, T, Cn, opt(lv), opt(la), opt(cls), opt(vld), _ptr(len_dev), _ptr(rows),
+                                         opt(part), _ptr(erows), opt(egt), opt(conf), stream)
+            _lib.check(rc, "m3t_eval_append_mtl")
+            self._erows.append(erows)
+            if self.with_gt:
+                self._egt.append(egt)
+                self._conf.append(conf)
+        else:
+            rc = lib.m3t_eval_append(_ptr(y), N, T, Cn, opt(lv), opt(la), _ptr(len_dev), _ptr(rows), opt(part), stream)
+            _lib.check(rc, "m3t_eval_append")
         self._rows.append(rows)
         if self.with_gt:
             self._part.append(part)
@@ -160,23 +233,43 @@ class Evaluator:
         rc = lib.m3t_eval_gather(_ptr(rows), W, Q, T, at(0), at(S), at(2 * S), at(3 * S), at(3 * S + V + 1), V, F,
                                  plan.halve_from, _ptr(tracks), stream)
         _lib.check(rc, "m3t_eval_gather")
-        metrics = None
+        one = lambda parts: torch.cat(parts) if len(parts) > 1 else parts[0]
+        expr = None
+        if self.expr:
+            erows, egt = one(self._erows), one(self._egt) if self.with_gt else None
+            expr = ExprTracks(torch.empty(N_EXPR, F, dtype=torch.float32, device=dev), torch.empty(F, dtype=torch.int8, device=dev),
+                              torch.empty(F, dtype=torch.int8, device=dev) if self.with_gt else None)
+            rc = lib.m3t_eval_gather_expr(_ptr(erows), _ptr(egt) if self.with_gt else None, W, T, at(0), at(S), at(2 * S), at(3 * S),
+                                          at(3 * S + V + 1), V, F, plan.halve_from, _ptr(expr.logits), _ptr(expr.pred),
+                                          _ptr(expr.gt) if self.with_gt else None, stream)
+            _lib.check(rc, "m3t_eval_gather_expr")
+        metrics = expr_metrics = None
         if self.with_gt:
-            part = torch.cat(self._part) if len(self._part) > 1 else self._part[0]
-            out = torch.empty(5, dtype=torch.float64, device=dev)
+            part = one(self._part)
+            out = torch.empty(5 + 24 * self.expr, dtype=torch.float64, device=dev)         # the VA figures, then the expression ones
             _lib.check(lib.m3t_eval_metrics(_ptr(part), W, _ptr(out), stream), "m3t_eval_metrics")
-            metrics = dict(zip(METRIC_KEYS, out.tolist()))         # the epoch's one read-back
-        self._rows, self._part, self._names, self._starts, self._lengths, self._keep = [], [], [], [], [], []     # ready for the next epoch
-        return EvalResult(plan.names, plan.frame_off, tracks, metrics)
+            if self.expr:
+                conf = one(self._conf)
+                _lib.check(lib.m3t_eval_expr_metrics(_ptr(conf), W, C.c_void_p(out.data_ptr() + 8 * 5), stream), "m3t_eval_expr_metrics")
+            vals = out.tolist()                                    # the epoch's one read-back
+            metrics = dict(zip(METRIC_KEYS, vals[:5]))
+            if self.expr:
+                three, expr_metrics = _expr_table(vals[5:])
+                metrics.update(zip(EXPR_METRIC_KEYS, three))
+        self._reset()                                              # ready for the next epoch
+        return EvalResult(plan.names, plan.frame_off, tracks, metrics, expr, expr_metrics)
 
 
 class EvalResult:
     """names: the videos; frame_off [V+1] (numpy int64); tracks [Q, F] fp32 on the device, Q = valence_pred, arousal_pred
     (, valence_gt, arousal_gt), video v at tracks[:, frame_off[v]:frame_off[v+1]]; metrics: stitch.val_metrics' keys as
-    Python floats (None without labels)."""
+    Python floats (None without labels).  From Evaluator(expr=True): expr = ExprTracks(logits [7, F], pred [F], gt [F] or
+    None) on the device with the same frame layout, metrics also holds val_acc_expr / val_f1_expr / val_score_expr, and
+    expr_metrics = {'precision' | 'recall' | 'f1': {class name: float}}; otherwise expr and expr_metrics are None."""
 
-    def __init__(self, names, frame_off, tracks, metrics=None):
+    def __init__(self, names, frame_off, tracks, metrics=None, expr=None, expr_metrics=None):
         self.names, self.frame_off, self.tracks, self.metrics = list(names), np.asarray(frame_off, dtype=np.int64), tracks, metrics
+        self.expr, self.expr_metrics = expr, expr_metrics
 
     @property
     def with_gt(self):
@@ -184,13 +277,22 @@ class EvalResult:
 
     def to_dicts(self):
         """the dict validation_end saves as predictions_val.pt (test_end: predictions_test.pt, predictions only): per-video
-        CPU tensors"""
+        CPU tensors.  A result with expression tracks adds expr_logits {video: [n, 7] fp32}, expr_pred {video: [n] int8} and,
+        with labels, expr_gt {video: [n] int8}."""
         host = self.tracks.cpu()
         lens = np.diff(self.frame_off).tolist()
-        per = lambda q: {n: t.clone() for n, t in zip(self.names, torch.split(host[q], lens))}
+        split = lambda t: {n: x.clone() for n, x in zip(self.names, torch.split(t, lens))}
+        per = lambda q: split(host[q])
         if self.with_gt:
-            return {"valence_gt": per(2), "arousal_gt": per(3), "valence_pred": per(0), "arousal_pred": per(1)}
-        return {"valence_pred": per(0), "arousal_pred": per(1)}
+            d = {"valence_gt": per(2), "arousal_gt": per(3), "valence_pred": per(0), "arousal_pred": per(1)}
+        else:
+            d = {"valence_pred": per(0), "arousal_pred": per(1)}
+        if self.expr is not None:
+            d["expr_logits"] = split(self.expr.logits.t().contiguous().cpu())
+            d["expr_pred"] = split(self.expr.pred.cpu())
+            if self.expr.gt is not None:
+                d["expr_gt"] = split(self.expr.gt.cpu())
+        return d
 
     def save(self, path):
         torch.save(self.to_dicts(), path)
@@ -204,7 +306,16 @@ class EvalResult:
         flat = lambda x: torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).detach().reshape(-1).to(torch.float32)
         lens = [int(flat(d[keys[0]][n]).numel()) for n in names]
         tracks = torch.stack([torch.cat([flat(d[k][n]) for n in names]) for k in keys]).to(dev)
-        return cls(names, np.concatenate([[0], np.cumsum(lens)]), tracks, None)
+        expr = None
+        if "expr_logits" in d:
+            ten = lambda x: torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).detach()
+            logits = torch.cat([ten(d["expr_logits"][n]).to(torch.float32).reshape(-1, N_EXPR) for n in names])
+            if logits.size(0) != sum(lens):
+                raise ValueError("from_dicts: expr_logits hold %d frames, the valence tracks %d" % (logits.size(0), sum(lens)))
+            cat8 = lambda k: torch.cat([ten(d[k][n]).reshape(-1).to(torch.int8) for n in names]).to(dev)
+            pred = cat8("expr_pred") if "expr_pred" in d else logits.argmax(1).to(torch.int8).to(dev)
+            expr = ExprTracks(logits.t().contiguous().to(dev), pred, cat8("expr_gt") if "expr_gt" in d else None)
+        return cls(names, np.concatenate([[0], np.cumsum(lens)]), tracks, None, expr)
 
     def smoothed_report(self, window=35, mode="wiener", top=10, out=print):
         """postproc.smoothed_ccc_report (get_smoothed_ccc.py:6-43) on the tracks where they are: one smoothing launch, one
@@ -244,3 +355,39 @@ class EvalResult:
             for name, val in sorted(table.items(), key=lambda kv: sign * kv[1])[:top]:
                 out("%s %s" % (name, val))
         return {"ccc_v": ccc_v, "ccc_a": ccc_a, "ccc_v_all": all_v, "ccc_a_all": all_a}
+
+    def expr_report(self, window=1, top=10, out=print):
+        """The expression counterpart of smoothed_report: a mode filter of `window` frames (odd; 1 = none) over the predicted
+        class tracks, one confusion per video, the figures over every frame once -- three launches, one read-back.  Prints
+        accuracy, macro-F1 and score = 0.67 F1 + 0.33 accuracy over all videos, then the videos with the lowest and highest
+        accuracy (a video without an annotated frame has accuracy NaN and is in neither list), and returns them."""
+        if self.expr is None or self.expr.gt is None:
+            raise ValueError("expr_report needs expression tracks with labels (Evaluator(expr=True) on a validation epoch)")
+        if int(window) < 1 or int(window) % 2 == 0:
+            raise ValueError("expr_report: the window must be odd and positive, not %d" % int(window))
+        V, F = len(self.names), int(self.frame_off[-1])
+        if V == 0:
+            raise ValueError("expr_report: no videos")
+        pred, gt = self.expr.pred.contiguous(), self.expr.gt.contiguous()
+        dev = pred.device
+        offs = torch.from_numpy(self.frame_off).to(dev)
+        sm = torch.empty(F, dtype=torch.int8, device=dev)
+        conf = torch.empty(V, N_EXPR, N_EXPR, dtype=torch.int32, device=dev)
+        res = torch.empty(24 + V, dtype=torch.float64, device=dev)     # the figures over all videos, then an accuracy per video
+        lib, stream = _lib_and_stream()
+        _lib.check(lib.m3t_expr_mode_tracks(_ptr(pred), _ptr(offs), V, int(window), _ptr(sm), stream), "m3t_expr_mode_tracks")
+        _lib.check(lib.m3t_expr_track_conf(_ptr(sm), _ptr(gt), _ptr(offs), V, _ptr(conf), C.c_void_p(res.data_ptr() + 8 * 24),
+                                           stream), "m3t_expr_track_conf")
+        _lib.check(lib.m3t_eval_expr_metrics(_ptr(conf), V, _ptr(res), stream), "m3t_eval_expr_metrics")
+        vals = res.tolist()                                            # the one read-back
+        (acc_all, f1_all, score_all), per_class = _expr_table(vals[:24])
+        acc = dict(zip(self.names, vals[24:]))
+        out(acc_all)
+        out(f1_all)
+        out(score_all)
+        ranked = [kv for kv in acc.items() if kv[1] == kv[1]]
+        for title, sign in (("Lowest acc-expr:", 1), ("Highest acc-expr:", -1)):
+            out(title)
+            for name, val in sorted(ranked, key=lambda kv: sign * kv[1])[:top]:
+                out("%s %s" % (name, val))
+        return {"acc": acc, "acc_all": acc_all, "f1_all": f1_all, "score_all": score_all, "per_class": per_class}

@@ -7,6 +7,7 @@ Same names, arguments and file formats as the reference:
   concordance_cc2_np(r1, r2)                                   models/utils.py:20-22
   smoothed_ccc_report('predictions_val.pt')                    get_smoothed_ccc.py:6-43 (prints the same lines)
   run_ensemble(eval_list, score_list)                          create_submission.py:14-39 (VA-Track/<video>.txt)
+and, with no counterpart there, run_expr_ensemble(eval_list, score_list) for the expression head (EXPR-Track/<video>.txt).
 There is no CPU path: the library must be loadable and a GPU present.
 """
 import ctypes as C
@@ -138,4 +139,48 @@ def run_ensemble(eval_list, score_list, out_dir="VA-Track"):
             fp.write("valence,arousal\n")
             for a, b in zip(val, aro):
                 fp.write("{:.3f},{:.3f}\n".format(a, b))
+    return out_dir
+
+
+def run_expr_ensemble(eval_list, score_list, out_dir="EXPR-Track", window=1):
+    """run_ensemble's counterpart for the expression track of the challenge: sum the `expr_logits` of several prediction
+    files (EvalResult.save from Evaluator(expr=True)) in list order, divide by their number, argmax on the device, mode filter
+    of `window` frames (m3t_expr_mode_tracks; odd, 1 = none) and write `<out_dir>/<video>.txt`: the header line of class names,
+    then one integer per frame.  A frame that no listed file predicts (its `expr_pred` is -1 in every file that has one: no
+    window covered it) is written as -1.  eval_list / score_list as in run_ensemble.  ValueError: a file without expr_logits."""
+    from .evaluate import EXPR_CLASSES
+    def lines(f):
+        return open(f.name if hasattr(f, "name") else f, "r").read().splitlines()
+    if int(window) < 1 or int(window) % 2 == 0:
+        raise ValueError("run_expr_ensemble: the window must be odd and positive, not %d" % int(window))
+    video_names, score_names = lines(eval_list), lines(score_list)
+    dev = _device()
+    total, none = {}, {}
+    for i, fname in enumerate(score_names):
+        scores = torch.load(fname, map_location="cpu")
+        if "expr_logits" not in scores:
+            raise ValueError("run_expr_ensemble: %s holds no expr_logits (save it from Trainer.evaluate(expr=True))" % fname)
+        for v in video_names:
+            x = torch.as_tensor(scores["expr_logits"][v]).to(dev, torch.float32).reshape(-1, len(EXPR_CLASSES))
+            miss = (torch.as_tensor(scores["expr_pred"][v]).to(dev).reshape(-1) < 0) if "expr_pred" in scores else \
+                torch.zeros(x.size(0), dtype=torch.bool, device=dev)
+            total[v], none[v] = (x, miss) if i == 0 else (total[v] + x, none[v] & miss)
+    os.makedirs(out_dir, exist_ok=True)
+    nb = len(score_names)
+    cls = []
+    for v in video_names:
+        c = torch.argmax(total[v] / nb, dim=1).to(torch.int8)
+        c[none[v]] = -1
+        cls.append(c)
+    lens = [int(c.numel()) for c in cls]
+    flat = torch.cat(cls).contiguous()
+    offs = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev)
+    sm = torch.empty_like(flat)
+    _lib.check(lib().m3t_expr_mode_tracks(C.c_void_p(flat.data_ptr()), C.c_void_p(offs.data_ptr()), len(video_names), int(window),
+                                          C.c_void_p(sm.data_ptr()), _stream()), "m3t_expr_mode_tracks")
+    for v, track in zip(video_names, torch.split(sm.cpu(), lens)):
+        with open(os.path.join(out_dir, v + ".txt"), "w") as fp:
+            fp.write(",".join(EXPR_CLASSES) + "\n")
+            for k in track.tolist():
+                fp.write("%d\n" % k)
     return out_dir

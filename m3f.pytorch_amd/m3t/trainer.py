@@ -122,18 +122,21 @@ class Trainer:
         res = self.model.validation_end(outputs)
         return res
 
-    def evaluate(self, batches, test=False, out_path=None):
+    def evaluate(self, batches, test=False, out_path=None, expr=False):
         """validate() without a read-back per batch (m3t/evaluate.py): the forward passes are queued back to back, the windows
         are stitched and scored on the device, and the epoch ends with one read-back of the five metrics.  Follows the module's
         hooks: validation_step / validation_end, or with test=True test_step / test_end -- predictions only, overlap-added,
         saved as predictions_test.pt, result {}; under hparams.test_on_val those are the validation hooks with overlap-add, as
         in the reference.  Same tracks bit for bit, same file layout (out_path: another file name); the result is
-        validation_end's dict with Python floats.  Each rank scores its own shard, as in validate()."""
+        validation_end's dict with Python floats.  Each rank scores its own shard, as in validate().
+        expr=True (a 9-channel `mtl` model; batches with class_expr / expr_valid when labelled) also stitches and scores the
+        expression head, which the reference trains and never validates: `log` gains val_acc_expr / val_f1_expr /
+        val_score_expr, progress_bar val_acc_expr, the file expr_logits / expr_pred (/ expr_gt); still one read-back."""
         from .evaluate import Evaluator
         hp = self.model.hparams
         test_on_val = bool(getattr(hp, "test_on_val", False))
         with_gt = test_on_val or not test
-        ev = Evaluator(hp.window, overlap=test_on_val or test, with_gt=with_gt)
+        ev = Evaluator(hp.window, overlap=test_on_val or test, with_gt=with_gt, expr=expr)
         self.model.eval()
         with torch.no_grad():
             for b in batches:
@@ -144,8 +147,10 @@ class Trainer:
         if not with_gt:
             return {}
         m = res.metrics
-        return {"val_loss": m["val_loss"], "progress_bar": {"val_ccc_v": m["val_ccc_v"], "val_ccc_a": m["val_ccc_a"]},
-                "log": dict(m)}
+        bar = {"val_ccc_v": m["val_ccc_v"], "val_ccc_a": m["val_ccc_a"]}
+        if expr:
+            bar["val_acc_expr"] = m["val_acc_expr"]
+        return {"val_loss": m["val_loss"], "progress_bar": bar, "log": dict(m)}
 
     # ------------------------------------------------------------------ rank plumbing
     @property

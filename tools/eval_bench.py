@@ -13,6 +13,15 @@ synchronise, after one warm-up epoch each: --repeats epochs in turn, median.  Th
 run fails.  One JSON line.
 
     python tools/eval_bench.py [--videos 145] [--frames 2000] [--window 32] [--batch 32] [--repeats 3]
+
+--expr: what scoring the expression head costs (m3t/evaluate.py, Evaluator(expr=True)).  The same epoch with expression
+labels, three routes in turn in one process, --repeats rounds after one warm-up each, median and spread (max - min):
+
+  va         Trainer.evaluate(batches)                 valence / arousal only
+  va_expr    Trainer.evaluate(batches, expr=True)      + the expression head on the device: still one read-back
+  host_expr  the va route with the expression part by hand: per batch y_hat[..., :7].argmax(-1).cpu(), a numpy confusion
+
+va_expr and host_expr must agree on the epoch's confusion (through val_acc_expr) or the run fails.
 """
 import argparse
 import json
@@ -21,6 +30,7 @@ import sys
 import tempfile
 import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -29,6 +39,7 @@ sys.path.insert(0, os.path.join(ROOT, "m3f.pytorch_amd"))
 
 from models.model import AffWild2VA  # noqa: E402
 from m3t import postproc  # noqa: E402
+from m3t.evaluate import Evaluator  # noqa: E402
 from m3t.trainer import Trainer  # noqa: E402
 from m3t.workloads import AVFeatureGraph  # noqa: E402
 
@@ -71,6 +82,9 @@ def epoch(args, dims, pool=8):
         lv, la = rnd(args.batch, W), rnd(args.batch, W)
         lv[torch.rand(args.batch, W, device=DEV, generator=gen) < 0.2] = -5.0         # unannotated frames
         labels.append((lv, la))
+    expr = getattr(args, "expr", False)                # (drawn after everything else: the plain epoch keeps its values)
+    exprs = [(torch.randint(0, 7, (args.batch, W), device=DEV, generator=gen),
+              torch.rand(args.batch, W, device=DEV, generator=gen) < 0.8) for _ in range(pool if expr else 0)]
     batches = []
     for i in range(0, len(wins), args.batch):
         chunk, j = wins[i:i + args.batch], (i // args.batch) % pool
@@ -78,6 +92,8 @@ def epoch(args, dims, pool=8):
         b = {k: v[:n] for k, v in feats[j].items()}
         b.update({"label_valence": labels[j][0][:n], "label_arousal": labels[j][1][:n], "vid_name": [c[0] for c in chunk],
                   "start": torch.tensor([c[1] for c in chunk]), "length": torch.tensor([c[2] for c in chunk])})
+        if expr:
+            b.update({"class_expr": exprs[j][0][:n], "expr_valid": exprs[j][1][:n]})
         batches.append(b)
     return batches, len(wins)
 
@@ -123,6 +139,41 @@ def bench(name, model, dims, args):
             "max_report_diff": gap}
 
 
+def bench_expr(name, model, dims, args):
+    tr = Trainer.from_hparams(model, model.hparams)
+    batches, n_windows = epoch(args, dims)
+    kept = {}
+
+    def va():
+        tr.evaluate(batches, out_path="predictions_val_va.pt")
+
+    def va_expr():
+        kept["device"] = tr.evaluate(batches, out_path="predictions_val_expr.pt", expr=True)["log"]["val_acc_expr"]
+
+    def host_expr():
+        conf = np.zeros((7, 7), np.int64)
+        ev = Evaluator(args.window, overlap=True, with_gt=True)                    # Trainer.evaluate's loop under test_on_val
+        model.eval()
+        with torch.no_grad():
+            for b in batches:
+                y = model.forward(b)
+                ev.add(y, b)
+                pred = y[..., :7].argmax(-1).cpu().numpy()                         # the read-back per batch
+                ok = b["expr_valid"].cpu().numpy() & (np.arange(pred.shape[1])[None, :] < b["length"].numpy()[:, None])
+                np.add.at(conf, (b["class_expr"].cpu().numpy()[ok], pred[ok]), 1)
+        tr.ddp.agree_on_scan_error()
+        ev.finish().save("predictions_val_host_expr.pt")
+        kept["host"] = float(np.trace(conf)) / float(conf.sum())
+
+    meds, samples = timed([va, va_expr, host_expr], args.repeats)
+    assert abs(kept["device"] - kept["host"]) <= 1e-15, "the two expression routes disagree: %r" % kept
+    out = {"model": name, "windows": n_windows, "batches": len(batches), "val_acc_expr": kept["device"]}
+    for key, med, xs in zip(("va", "va_expr", "host_expr"), meds, samples):
+        out[key + "_s"], out[key + "_spread_s"], out[key + "_all_s"] = round(med, 4), round(max(xs) - min(xs), 4), [round(t, 4) for t in xs]
+    out["expr_over_va_s"] = round(meds[1] - meds[0], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--videos", type=int, default=145)
@@ -131,6 +182,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--models", default="c3,audio")
+    ap.add_argument("--expr", action="store_true", help="time the expression head: va / va_expr / host_expr (see above)")
     args = ap.parse_args()
     torch.manual_seed(0)
     results = []
@@ -145,10 +197,10 @@ def main():
                 model, dims = AffWild2VA(hp).to(DEV), {"audio": 200}
             else:
                 raise SystemExit("unknown model %r (c3, audio)" % name)
-            results.append(bench(name, model, dims, args))
+            results.append((bench_expr if args.expr else bench)(name, model, dims, args))
         os.chdir(ROOT)
     print(json.dumps({"videos": args.videos, "frames": args.frames, "window": args.window, "batch": args.batch,
-                      "repeats": args.repeats, "results": results}))
+                      "repeats": args.repeats, "expr": args.expr, "results": results}))
 
 
 if __name__ == "__main__":
