@@ -71,7 +71,7 @@ static __device__ __forceinline__ void m3t_drop_mask4(const M3TDrop& d, uint32_t
     m[2] = c2 < d.thr ? d.scale : 0.f; m[3] = c3 < d.thr ? d.scale : 0.f;
 }
 
-// ---- fp16x3 GEMM operands (gemm_x6.hip / gemm_x6d.hip, NS = 4) ----------------------------------------------------------------
+// ---- fp16x3 GEMM operands (x6_tile.h, split3_pair<4>) --------------------------------------------------------------------------
 // An operand is staged as two fp16 terms of s x, s the power of two that puts max |x| into [2^14, 2^15) (fp16 overflows at 65504).
 // bits = the fp32 bit pattern of max |x| over (a superset of) the operand, measured on the device right before the GEMM
 // (gemm.hip, the backward scans).  Componentwise this is NOT fp32 (error model; tests/test_gpu_parity.py::

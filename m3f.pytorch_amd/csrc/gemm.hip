@@ -4,7 +4,7 @@
 // conflict-free 32-lane fragment reads, 2-way (free) transposing writes); global loads
 // for tile k+1 are issued before the MFMAs of tile k (register prefetch, double LDS buffer).
 // Split-K goes through fp32 slabs + a fixed-order reduce: deterministic, no atomics.
-#include "common.h"
+#include "x6_tile.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -125,13 +125,8 @@ __global__ __launch_bounds__(256) void sgemm_kernel(GemmParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hi = lane >> 5;
-    // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (private L2s), so give each XCD a
-    // CONTIGUOUS run of tiles (column tile fastest): neighbours then share their A row-panel in that XCD's L2.
-    // Bijective for any tile count; placement only affects speed.
     const int tn_ = gridDim.x, nt_ = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * tn_ + blockIdx.x;
-    const int xq = nt_ >> 3, xr = nt_ & 7, xcd = lin & 7, slot = lin >> 3;
-    const int til = xcd * xq + min(xcd, xr) + slot;
+    const int til = m3t_xcd_tile(blockIdx.y * tn_ + blockIdx.x, nt_);      // XCD-contiguous tile order (x6_tile.h)
     const int bm = (til / tn_) * BM, bn = (til % tn_) * BN;
     const int k_begin = blockIdx.z * p.kchunk;
     const int k_end = min(p.K, k_begin + p.kchunk);
@@ -908,8 +903,6 @@ static void taps_split(long long rows, int Cd, int K, float* ws, size_t ws_bytes
 }
 
 namespace {
-typedef _Float16 sp_f16x2 __attribute__((ext_vector_type(2)));
-typedef float sp_f32x2 __attribute__((ext_vector_type(2)));
 // the "P4" image of a K-contiguous fp16x3 operand (gemm_x6.hip, kc_store<PRE>): per four consecutive values {hi 0|1, hi 2|3, lo 0|1, lo 2|3}
 __global__ __launch_bounds__(256) void f16x3_split_kernel(const float* __restrict__ x, float* __restrict__ out, size_t rows, int c4, size_t ld,
                                                           size_t ldo, const unsigned long long* __restrict__ slot) {
@@ -919,14 +912,7 @@ __global__ __launch_bounds__(256) void f16x3_split_kernel(const float* __restric
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t r = i / c4; const int c = (int)(i - r * c4);
         const float4 v = *reinterpret_cast<const float4*>(x + r * ld + 4 * (size_t)c);
-        const sp_f32x2 a = (sp_f32x2){v.x, v.y} * sc, b = (sp_f32x2){v.z, v.w} * sc;
-        const sp_f16x2 ha = __builtin_convertvector(a, sp_f16x2), hb = __builtin_convertvector(b, sp_f16x2);
-        const sp_f16x2 la = __builtin_convertvector(a - __builtin_convertvector(ha, sp_f32x2), sp_f16x2);
-        const sp_f16x2 lb = __builtin_convertvector(b - __builtin_convertvector(hb, sp_f32x2), sp_f16x2);
-        float4 o;
-        o.x = __uint_as_float(__builtin_bit_cast(unsigned, ha)); o.y = __uint_as_float(__builtin_bit_cast(unsigned, hb));
-        o.z = __uint_as_float(__builtin_bit_cast(unsigned, la)); o.w = __uint_as_float(__builtin_bit_cast(unsigned, lb));
-        *reinterpret_cast<float4*>(out + r * ldo + 4 * (size_t)c) = o;
+        *reinterpret_cast<float4*>(out + r * ldo + 4 * (size_t)c) = f16x3_record((f32x2){v.x, v.y}, (f32x2){v.z, v.w}, sc);
     }
 }
 // ... of a PERMUTED view of a small tensor (round 6: a convolution's weights [Co][Ci][taps] as the K-contiguous matrices the walks read --
@@ -944,14 +930,11 @@ __global__ __launch_bounds__(256) void f16x3_split_perm_kernel(const float* __re
         const int t = (int)(rt % (size_t)T);
         const size_t r = rt / (size_t)T;
         const float* q = w + r * sR + (size_t)t * sT + (size_t)(4 * c) * sC;
-        const sp_f32x2 a = (sp_f32x2){q[0], q[sC]} * sc, b = (sp_f32x2){q[2 * sC], q[3 * sC]} * sc;
-        const sp_f16x2 ha = __builtin_convertvector(a, sp_f16x2), hb = __builtin_convertvector(b, sp_f16x2);
-        const sp_f16x2 la = __builtin_convertvector(a - __builtin_convertvector(ha, sp_f32x2), sp_f16x2);
-        const sp_f16x2 lb = __builtin_convertvector(b - __builtin_convertvector(hb, sp_f32x2), sp_f16x2);
-        float4 o;
-        o.x = __uint_as_float(__builtin_bit_cast(unsigned, ha)); o.y = __uint_as_float(__builtin_bit_cast(unsigned, hb));
-        o.z = __uint_as_float(__builtin_bit_cast(unsigned, la)); o.w = __uint_as_float(__builtin_bit_cast(unsigned, lb));
-        *reinterpret_cast<float4*>(out + (r * T + t) * (size_t)Cc + 4 * (size_t)c) = o;
+        unsigned a[3], b[3];                                   // (f16x3_record, spelled out: through it the address arithmetic is scheduled differently)
+        split3_pair<4>((f32x2){q[0], q[sC]}, a, sc);
+        split3_pair<4>((f32x2){q[2 * sC], q[3 * sC]}, b, sc);
+        *reinterpret_cast<float4*>(out + (r * T + t) * (size_t)Cc + 4 * (size_t)c) =
+            make_float4(__uint_as_float(a[0]), __uint_as_float(b[0]), __uint_as_float(a[1]), __uint_as_float(b[1]));
     }
 }
 }  // namespace
@@ -988,10 +971,9 @@ __global__ __launch_bounds__(256) void f16x3_image_b_kernel(const float* __restr
         unsigned hi[4], lo[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const sp_f32x2 a = (sp_f32x2){x[2 * e], x[2 * e + 1]} * sc;
-            const sp_f16x2 h = __builtin_convertvector(a, sp_f16x2);
-            const sp_f16x2 l = __builtin_convertvector(a - __builtin_convertvector(h, sp_f32x2), sp_f16x2);
-            hi[e] = __builtin_bit_cast(unsigned, h); lo[e] = __builtin_bit_cast(unsigned, l);
+            unsigned o[3];
+            split3_pair<4>((f32x2){x[2 * e], x[2 * e + 1]}, o, sc);
+            hi[e] = o[0]; lo[e] = o[1];
         }
         unsigned char* dst = img + (((size_t)rb * K8 + o) * 2) * 1024 + (size_t)r * 16;
         *reinterpret_cast<uint4*>(dst) = make_uint4(hi[0], hi[1], hi[2], hi[3]);

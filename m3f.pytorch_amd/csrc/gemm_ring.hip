@@ -16,14 +16,10 @@
 // LDS image of one operand's stage: 16 pieces of 1 KiB (one wave instruction each) = 16 rows x 64 B; inside a piece the 16-B quad q of row r sits at
 // slot q ^ (r >> 2): the swizzle is applied to the SOURCE address (lane (r, c) fetches quad c ^ (r >> 2)) and again on the fragment read, the LDS
 // destination stays lane-linear (guide, rule 21).  A 16-lane group of a ds_read_b128 then covers 16 distinct 16-B bank groups.
-#include "common.h"
+#include "x6_tile.h"
 #include <cstdlib>
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int RM = 256, RN = 256, RKS = 16, RTH = 512, RING = 4;
 constexpr int OPB = 256 * 64;                      // one operand's stage: 256 rows x 16 k x 4 B
@@ -38,7 +34,7 @@ struct RingParams {
     const unsigned long long* amax_b;
 };
 
-// the exact split of gemm_x6d.hip (NS = 4), eight values at once.  MIX: the low term by v_fma_mix{lo,hi}_f16 -- fp16(fma(x, s, -hi)) in ONE
+// the exact split (split3_pair<4>, x6_tile.h), eight values at once.  MIX: the low term by v_fma_mix{lo,hi}_f16 -- fp16(fma(x, s, -hi)) in ONE
 // instruction per value (s x is exact, so is the difference: the same rounding as fp16(s x - float(hi))) instead of cvt_f32_f16 + fma + cvt:
 // 16 instead of 24 VALU instructions per fragment.
 template <bool MIX, bool NOSPLIT = false>
@@ -51,24 +47,30 @@ __device__ __forceinline__ void split8(const f32x4& v0, const f32x4& v1, float s
     unsigned hw[4], lw[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const f32x2 vs = (f32x2){x[2 * e], x[2 * e + 1]} * sc;
-        const f16x2 hh = __builtin_convertvector(vs, f16x2);
-        hw[e] = __builtin_bit_cast(unsigned, hh);
         if (MIX) {
+            const f32x2 vs = (f32x2){x[2 * e], x[2 * e + 1]} * sc;
+            hw[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(vs, f16x2));
             unsigned L;
             asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(L) : "v"(x[2 * e]), "s"(sc), "v"(hw[e]));
             asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(L) : "v"(x[2 * e + 1]), "s"(sc), "v"(hw[e]));
             lw[e] = L;
         } else {
-            const f32x2 r1 = vs - __builtin_convertvector(hh, f32x2);
-            const f16x2 ll = __builtin_convertvector(r1, f16x2);
-            lw[e] = __builtin_bit_cast(unsigned, ll);
+            unsigned o[3];
+            split3_pair<4>((f32x2){x[2 * e], x[2 * e + 1]}, o, sc);
+            hw[e] = o[0]; lw[e] = o[1];
         }
     }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     h = __builtin_bit_cast(f16x8, (u32x4){hw[0], hw[1], hw[2], hw[3]});
     l = __builtin_bit_cast(f16x8, (u32x4){lw[0], lw[1], lw[2], lw[3]});
 }
+
+// the products of B fragment j with both A fragments, in x6_mac<4>'s order (x6_tile.h): lo hi, hi lo, hi hi -- on the kernels' al, ah, bl, bh, acc
+#define RING_MFMA6(j)                                                                                                                          \
+    do {                                                                                                                                       \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);     \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);     \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);     \
+    } while (0)
 
 template <int VAR>
 __global__ __launch_bounds__(RTH, 1) void sgemm_ring_kernel(RingParams p) {
@@ -79,9 +81,7 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ring_kernel(RingParams p) {
     const int l31 = lane & 31, hi = lane >> 5;
 
     const int tn_ = gridDim.x, nt_ = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * tn_ + blockIdx.x;
-    const int xq = nt_ >> 3, xr = nt_ & 7, xcd = lin & 7, slot = lin >> 3;
-    const int til = xcd * xq + min(xcd, xr) + slot;           // XCD-contiguous tile order (see gemm.hip)
+    const int til = m3t_xcd_tile(blockIdx.y * tn_ + blockIdx.x, nt_);      // XCD-contiguous tile order (x6_tile.h)
     const int bm = (til / tn_) * RM, bn = (til % tn_) * RN;
     const int k_begin = blockIdx.z * p.kchunk;
     const int k_end = min(p.K, k_begin + p.kchunk);
@@ -139,12 +139,6 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ring_kernel(RingParams p) {
     const unsigned ra0 = lds0 + fa_off + q0, ra1 = lds0 + fa_off + q1, rb0 = lds0 + fb_off + q0, rb1 = lds0 + fb_off + q1;
 #define RING_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define RING_WAIT_LGKM(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define RING_MFMA6(j)                                                                                                                          \
-    do {                                                                                                                                       \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);     \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);     \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);     \
-    } while (0)
     constexpr bool PIPE = (VAR & 1) != 0, MIX = (VAR & 2) != 0, PAIR = (VAR & 4) != 0;
     constexpr bool NODMA = (VAR & 8) != 0, NOMM = (VAR & 16) != 0, NOSP = (VAR & 32) != 0;     // ablations (timing only: wrong results)
     f32x4 va[2][2], vb[4][2];
@@ -227,13 +221,12 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ring_kernel(RingParams p) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-#undef RING_MFMA6
 #undef RING_WAIT_LGKM
 #undef RING_RD
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the unread tail stages: no LDS-DMA may outlive the workgroup
 
     const bool direct = p.splits == 1;
-    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;
+    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;      // one K pass: C itself; else this split's slab, [M][N] dense
     const int ldd = direct ? p.ldc : p.N;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -245,14 +238,7 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ring_kernel(RingParams p) {
             for (int r = 0; r < 16; ++r) {
                 const int row = bm + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 if (row >= p.M) continue;
-                float v = acc[i][j][r] * sc_ia * sc_ib;      // (exact: powers of two)
-                float* q = dst + (size_t)row * ldd + col;
-                if (direct) {
-                    v += bv;
-                    if (p.act == 1) v = m3t_relu(v);
-                    if (p.accumulate) v += *q;
-                }
-                *q = v;
+                x6_plain_out(acc[i][j][r] * sc_ia * sc_ib, dst + (size_t)row * ldd + col, bv, direct, p.act, p.accumulate);      // (scales: exact, powers of two)
             }
         }
 }
@@ -273,9 +259,7 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ringt_kernel(RingParams p) {
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hi = lane >> 5;
     const int tn_ = gridDim.x, nt_ = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * tn_ + blockIdx.x;
-    const int xq = nt_ >> 3, xr = nt_ & 7, xcd = lin & 7, slot = lin >> 3;
-    const int til = xcd * xq + min(xcd, xr) + slot;
+    const int til = m3t_xcd_tile(blockIdx.y * tn_ + blockIdx.x, nt_);      // XCD-contiguous tile order (x6_tile.h)
     const int bm = (til / tn_) * RM, bn = (til % tn_) * RN;
     const int k_begin = blockIdx.z * p.kchunk;
     const int k_end = min(p.K, k_begin + p.kchunk);
@@ -342,11 +326,10 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ringt_kernel(RingParams p) {
     // K-contiguous: two ds_read_b128 at ra0 / ra1 (+ 2048 per 32 rows); row-contiguous: rows 8 hi + e at 1 KiB each, column (tile row) x 4 B
     const unsigned ra0 = lds0 + (AM ? hi * 8192 + (wm * 64 + l31) * 4 : wm * 4096 + fro + q0), ra1 = lds0 + wm * 4096 + fro + q1;
     const unsigned rb0 = lds0 + OPB + (BM ? hi * 8192 + (wn * 128 + l31) * 4 : wn * 8192 + fro + q0), rb1 = lds0 + OPB + wn * 8192 + fro + q1;
-    typedef unsigned ru32x2 __attribute__((ext_vector_type(2)));
 #define RT_RD128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define RT_RD2(dst, addr, o0, o1) asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(dst) : "v"(addr), "n"(o0), "n"(o1))
 #define RT_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-    struct Raw { f32x4 q[2]; ru32x2 d[4]; };
+    struct Raw { f32x4 q[2]; u32x2 d[4]; };
     // one fragment's reads: `idx` = 32-row block of the operand's wave tile
     auto rd_a = [&](Raw& r, unsigned so, int idx) {
         if (AM) {
@@ -395,12 +378,7 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ringt_kernel(RingParams p) {
             } else RT_WAIT(0);
             f16x8 bh, bl;
             split_raw(xb[j & 1], BM, sc_b, bh, bl);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+            RING_MFMA6(j);
         }
     }
 #undef RT_WAIT
@@ -409,7 +387,7 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ringt_kernel(RingParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     const bool direct = p.splits == 1;
-    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;
+    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;      // one K pass: C itself; else this split's slab, [M][N] dense
     const int ldd = direct ? p.ldc : p.N;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -421,17 +399,12 @@ __global__ __launch_bounds__(RTH, 1) void sgemm_ringt_kernel(RingParams p) {
             for (int r = 0; r < 16; ++r) {
                 const int row = bm + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 if (row >= p.M) continue;
-                float v = acc[i][j][r] * sc_ia * sc_ib;
-                float* q = dst + (size_t)row * ldd + col;
-                if (direct) {
-                    v += bv;
-                    if (p.act == 1) v = m3t_relu(v);
-                    if (p.accumulate) v += *q;
-                }
-                *q = v;
+                x6_plain_out(acc[i][j][r] * sc_ia * sc_ib, dst + (size_t)row * ldd + col, bv, direct, p.act, p.accumulate);
             }
         }
 }
+
+#undef RING_MFMA6
 
 }  // namespace
 
@@ -453,19 +426,12 @@ int m3t_sgemm_ring_launch(int transA, int transB, int M, int N, int K, const flo
     p.seg_len = seg_len; p.seg_stride = seg_stride; p.a_off = a_off; p.b_off = b_off;
     dim3 grid(N / RN, cdiv(M, RM), splits), block(RTH);
     const size_t lds = (size_t)RING * STG;
-    static bool attr_set[16][72] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return M3T_EINVAL;
-#define M3T_RING_LAUNCH(SLOT_, KERNEL_)                                                                                                 \
+#define M3T_RING_LAUNCH(KERNEL_)                                                                                                        \
     do {                                                                                                                                 \
-        if (!attr_set[dev][SLOT_]) {                                                                                                     \
-            hipError_t ea = hipFuncSetAttribute((const void*)KERNEL_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-            if (ea != hipSuccess) return (int)ea;                                                                                        \
-            attr_set[dev][SLOT_] = true;                                                                                                 \
-        }                                                                                                                                \
-        KERNEL_<<<grid, block, lds, s>>>(p);                                                                                             \
+        const int el = x6_launch_dyn_lds<KERNEL_>(grid, block, lds, s, p);                                                               \
+        if (el) return el;                                                                                                               \
     } while (0)
-#define M3T_RING_GO(V_) M3T_RING_LAUNCH(V_, sgemm_ring_kernel<V_>)
+#define M3T_RING_GO(V_) M3T_RING_LAUNCH(sgemm_ring_kernel<V_>)
     if (transA == 0 && transB == 1) {
         switch (variant) {
             case 0: M3T_RING_GO(0); break;
@@ -479,9 +445,9 @@ int m3t_sgemm_ring_launch(int transA, int transB, int M, int N, int K, const flo
             case 43: M3T_RING_GO(43); break;
             default: return M3T_EINVAL;
         }
-    } else if (transA == 0) M3T_RING_LAUNCH(64, (sgemm_ringt_kernel<false, true, false>));
-    else if (seg_len > 0) M3T_RING_LAUNCH(65, (sgemm_ringt_kernel<true, true, true>));
-    else M3T_RING_LAUNCH(66, (sgemm_ringt_kernel<true, true, false>));
+    } else if (transA == 0) M3T_RING_LAUNCH((sgemm_ringt_kernel<false, true, false>));
+    else if (seg_len > 0) M3T_RING_LAUNCH((sgemm_ringt_kernel<true, true, true>));
+    else M3T_RING_LAUNCH((sgemm_ringt_kernel<true, true, false>));
 #undef M3T_RING_GO
 #undef M3T_RING_LAUNCH
     return (int)hipGetLastError();

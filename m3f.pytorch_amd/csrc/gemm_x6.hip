@@ -16,25 +16,20 @@
 // operands hold (4 rows, one k-quad) per thread, and the lane 32 away holds the other k-quad of the same octet: two
 // v_permlane32_swap per split and dword pair leave every lane with two complete 16-B records (32 contiguous bytes).
 // Global loads of tile t+1 stay in flight in registers while tile t is multiplied.
-#include "common.h"
+#include "x6_tile.h"
 #include <cstdlib>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int XM = 128, XN = 128, XK = 32;
 constexpr int PLANE = XM * 16 + 64;                // one k-octet plane: 128 rows x 16 B (+64 B: conflict-free K-contiguous stores)
 constexpr int SPLIT_BYTES = 4 * PLANE;             // one split of one operand: 4 k-octets
 constexpr int OPER_BYTES = 3 * SPLIT_BYTES;        // 24.75 KiB
-// TR (NS = 4): a row-contiguous operand lies in LDS as it lies in memory -- per term [k 32][128 rows] halves, a k-row every 320 B (256 + 64:
-// the four k-rows of one transposed read, and the two 16-row blocks of a 32-lane half, cover the 64 banks once) -- and a fragment is two
-// ds_read_b64_tr_b16 (four k each).  Two terms of 10 240 B fit the operand's 25 344.
+// TR (NS = 4): the transposed-read image of a row-contiguous operand (x6_tile.h), here 32 k-rows of 320 B per term: two terms of 10 240 B fit the
+// operand's 25 344
 constexpr int TRROW = XM * 2 + 64;
 constexpr int TRTERM = XK * TRROW;
 static_assert(2 * TRTERM <= OPER_BYTES, "the transposed-read image must fit the operand's LDS");
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 struct X6Params {
     const float* A; const float* B; float* C; const float* bias; float* ws;
@@ -66,54 +61,7 @@ struct X6Batch {
     int accumulate[M3T_WINDOW_BATCH];
 };
 
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)x;
-    const float r1 = x - (float)h;
-    m = (__bf16)r1;
-    const float r2 = r1 - (float)m;
-    l = (__bf16)r2;
-}
-
-// The same exact split on a PAIR of values with packed instructions: one v_cvt_pk_bf16_f32 rounds both (nearest even),
-// the two bf16 are widened back with a shift / a mask, one v_pk_add_f32 forms both remainders.  9 VALU instructions per
-// pair for all three terms, against ~17 per ELEMENT when hipcc scalarises split3 -- the splitting, not the MFMAs, was
-// what bounded this kernel.  o[s] = the pair's term s, packed (first value in the low half).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// NS = 4, "fp16x3": the operand, scaled by a power of two s that puts its largest magnitude into [2^14, 2^15), is the sum of TWO fp16
-// terms (hi = rn(s x), lo = rn(s x - hi): 22 significant bits wherever lo is a normal number, absolute error <= 2^-25 / s below that);
-// a product is the three fp16 MFMAs hi hi + hi lo + lo hi (exact in fp32; the dropped lo lo is <= 2^-22 relative), the scales leave
-// in the epilogue.  6 VALU instructions per pair (v_pk_mul, v_cvt_pk_f16_f32, 2 v_cvt_f32_f16, v_pk_fma, v_cvt_pk_f16_f32).
-constexpr int planes_of(int NS) { return NS == 4 ? 2 : NS; }
-template <int NS>
-__device__ __forceinline__ void split3_pair(f32x2 v, unsigned (&o)[3], float scale = 1.f) {
-    if (NS == 4) {
-        const f32x2 vs = v * scale;
-        const f16x2 h = __builtin_convertvector(vs, f16x2);
-        o[0] = __builtin_bit_cast(unsigned, h);
-        const f32x2 r1 = vs - __builtin_convertvector(h, f32x2);
-        const f16x2 l = __builtin_convertvector(r1, f16x2);
-        o[1] = __builtin_bit_cast(unsigned, l);
-        return;
-    }
-    const bf16x2 h = __builtin_convertvector(v, bf16x2);
-    o[0] = __builtin_bit_cast(unsigned, h);
-    if (NS == 1) return;
-    f32x2 hf;
-    hf.x = __uint_as_float(o[0] << 16); hf.y = __uint_as_float(o[0] & 0xffff0000u);
-    const f32x2 r1 = v - hf;
-    const bf16x2 m = __builtin_convertvector(r1, bf16x2);
-    o[1] = __builtin_bit_cast(unsigned, m);
-    if (NS == 2) return;
-    f32x2 mf;
-    mf.x = __uint_as_float(o[1] << 16); mf.y = __uint_as_float(o[1] & 0xffff0000u);
-    const f32x2 r2 = r1 - mf;
-    const bf16x2 l = __builtin_convertvector(r2, bf16x2);
-    o[2] = __builtin_bit_cast(unsigned, l);
-}
+// the exact split (split3_pair<NS>: a pair of values into its packed terms), tr_frag and the product order: x6_tile.h
 
 // ---- K-contiguous operand ([rows][K]): 8 lanes cover one row's 32 k (a full 128-B line); thread = (k-quad c =
 // tid&7, rows (tid>>3) + 32 i): every wave load instruction fetches 8 whole lines
@@ -152,7 +100,6 @@ template <int NS, bool PRE = false>
 __device__ __forceinline__ void mc_store(unsigned char* __restrict__ S, const float4 (&r)[4], float scale = 1.f) {
     const int tid = threadIdx.x & 255;
     const int wave = tid >> 6, h = (tid >> 5) & 1, row0 = (tid & 31) * 4;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     unsigned lo[4][3], hi2[4][3];                     // [row][split]: k pairs (0,1) and (2,3) of this thread's k-quad
     if (PRE && NS == 4) {
 #pragma unroll
@@ -211,15 +158,6 @@ __device__ __forceinline__ void mc_store_tr(unsigned char* __restrict__ S, const
         for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * TRTERM + e * TRROW) = (u32x2){a[s], b[s]};
     }
 }
-// the 32x32x16 operand (lane: row lane & 31, k 8 (lane >> 5) ..+7) from a TR image: per 16-lane group a 4 k x 16 row block, lane 4 q + p of the
-// group addressing k-row q, rows 4 p ..+3; `at` = this lane's address for the first four k, the next four lie 4 k-rows on.  (EXEC is all ones
-// at every call: the callers sit in uniform control flow.)  The same eight halves in the same order as the 16-B record of the permlane path.
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* at) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at + 4 * TRROW));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // NS = 3: fp32-accurate product from 3 bf16 terms per operand (6 MFMAs per tile step);
 // NS = 1: plain bf16 operands (round to nearest even), fp32 accumulate -- the mixed-precision mode (M3T_GEMM_BF16)
@@ -266,9 +204,7 @@ __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt
     const int l31 = lane & 31, hi = lane >> 5;
 
     const int tn_ = gridDim.x, nt_ = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * tn_ + blockIdx.x;
-    const int xq = nt_ >> 3, xr = nt_ & 7, xcd = lin & 7, slot = lin >> 3;
-    const int til = xcd * xq + min(xcd, xr) + slot;           // XCD-contiguous tile order (see gemm.hip)
+    const int til = m3t_xcd_tile(blockIdx.y * tn_ + blockIdx.x, nt_);      // XCD-contiguous tile order (x6_tile.h)
     const int bm = (til / tn_) * XM, bn = (til % tn_) * XNT;
     const bool bcol = XNT == 128 || (tid & 31) < 16;      // row-contiguous B: this thread's 4 columns lie inside the tile
     const int k_begin = MW ? 0 : blockIdx.z * p.kchunk;
@@ -478,10 +414,10 @@ __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt
             for (int s = 0; s < NP; ++s)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    if (TRA) fa[s][i] = tr_frag(As + tro + s * TRTERM + kh * 16 * TRROW + (wm * 64 + i * 32) * 2);
+                    if (TRA) fa[s][i] = tr_frag<TRROW>(As + tro + s * TRTERM + kh * 16 * TRROW + (wm * 64 + i * 32) * 2);
                     else fa[s][i] = *reinterpret_cast<const bf16x8*>(As + s * SPLIT_BYTES + (kh * 2 + hi) * PLANE + (wm * 64 + i * 32 + l31) * 16);
                     if (i < NJ) {
-                        if (TRB) fb[s][i] = tr_frag(Bs + tro + s * TRTERM + kh * 16 * TRROW + (wn * 32 * NJ + i * 32) * 2);
+                        if (TRB) fb[s][i] = tr_frag<TRROW>(Bs + tro + s * TRTERM + kh * 16 * TRROW + (wn * 32 * NJ + i * 32) * 2);
                         else fb[s][i] = *reinterpret_cast<const bf16x8*>(Bs + s * SPLIT_BYTES + (kh * 2 + hi) * PLANE + (wn * 32 * NJ + i * 32 + l31) * 16);
                     }
                 }
@@ -489,30 +425,8 @@ __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    f32x16 c = acc[i][j];      // smallest terms first
-                    if (NS == 4) {                 // fp16x3: lo hi, hi lo, hi hi
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[1][i]), __builtin_bit_cast(f16x8, fb[0][j]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0][i]), __builtin_bit_cast(f16x8, fb[1][j]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0][i]), __builtin_bit_cast(f16x8, fb[0][j]), c, 0, 0, 0);
-                        acc[i][j] = c;
-                        continue;
-                    }
-                    if (NS == 2) {                 // "high" mode: two bf16 terms per operand (16 mantissa bits), four products
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1][i], fb[1][j], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1][i], fb[0][j], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][i], fb[1][j], c, 0, 0, 0);
-                    }
-                    if (NS == 3) {
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[NS - 1][i], fb[0][j], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[NS / 2][i], fb[NS / 2][j], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][i], fb[NS - 1][j], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[NS / 2][i], fb[0][j], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][i], fb[NS / 2][j], c, 0, 0, 0);
-                    }
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][i], fb[0][j], c, 0, 0, 0);
-                    acc[i][j] = c;
-                }
+                for (int j = 0; j < NJ; ++j)
+                    acc[i][j] = x6_mac<NS>(acc[i][j], fa, i, fb, j);      // smallest terms first
         }
         __builtin_amdgcn_sched_barrier(0);     // bf16 splitting of the next tile happens after this tile's MFMAs
         __syncthreads();                       // everyone is done reading this tile
@@ -523,7 +437,7 @@ __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt
     }
 
     const bool direct = p.splits == 1;
-    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;
+    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;      // one K pass: C itself; else this split's slab, [M][N] dense
     const int ldd = direct ? p.ldc : p.N;
     if constexpr (C3 == 1 || C3 == 3) {
         // the walk's result straight into the planes layout the next operator reads (BatchNorm / pooling / CBAM work on [N, C, T, H, W]): a
@@ -585,12 +499,8 @@ __global__ __launch_bounds__(256, 3) void sgemm_x6_kernel(X6Params p, X6Batch bt
                     else if (p.act == 2) v = m3t_relu(m3t_relu(v) * mk + p.cv_res[o]);
                     else if (p.cv_res) v += p.cv_res[o];
                     vmax = fmaxf(vmax, m3t_fin_abs(v));
-                } else if (direct) {
-                    v += bv;
-                    if (p.act == 1) v = m3t_relu(v);
-                    if (p.accumulate) v += *q;
-                }
-                *q = v;
+                    *q = v;
+                } else x6_plain_out(v, q, bv, direct, p.act, p.accumulate);
             }
         }
     if (CONV && p.cv_amax) {                         // (uniform: every thread of the block gets here)

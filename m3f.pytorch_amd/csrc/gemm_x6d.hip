@@ -9,33 +9,20 @@
 // per fragment) as gemm_x6.hip, whose loaders this file shares in 256-thread form: results are bit-identical to
 // gemm_x6.hip's.  130 VGPRs, 51 KiB of LDS: three workgroups per CU, and two fit beside a persistent scan workgroup.
 // Measured (tools/x6d_bench.py, tools/gemm_bench.py): 9600 x 1536 x 1024 NT 226 -> 177 us (171 TFLOP/s algorithmic), 2048^3 118 -> 95 us.
-#include "common.h"
+#include "x6_tile.h"
 #include <cstdlib>
-#include <type_traits>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int BM = 128, BN = 128, BKS = 16, NTH = 256;
+constexpr int BM = 128, BN = 128, BKS = X6_STAGE_K, NTH = 256;
 constexpr int PLANEB = BM * 16 + 128;              // one k-octet plane: 128 rows x 16 B; +128 B: 2 planes x 8 rows hit 64 distinct banks
 constexpr int SPLITB = 2 * PLANEB;
 constexpr int OPERB = 3 * SPLITB;
 constexpr int STAGEB = 2 * OPERB;                  // 26 112 B
-// TR (NS = 4): a row-contiguous operand lies in LDS as it lies in memory -- per term [k 16][128 rows] halves, a k-row every 320 B (256 + 64:
-// the four k-rows of one transposed read, and the two 16-row blocks of a 32-lane half, cover the 64 banks once) -- and a fragment is two
-// ds_read_b64_tr_b16 (four k each).  Two terms of 5 120 B fit the operand's 13 056.
+// TR (NS = 4): the transposed-read image of a row-contiguous operand (x6_tile.h), a k-row every 320 B; two terms of 5 120 B fit the operand's 13 056
 constexpr int TRROW = BM * 2 + 64;
-constexpr int TRTERM = BKS * TRROW;
+constexpr int TRTERM = X6_STAGE_K * TRROW;
 static_assert(2 * TRTERM <= OPERB, "the transposed-read image must fit the operand's LDS");
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 struct X6DParams {
     const float* A; const float* B; float* C; const float* bias; float* ws;
@@ -51,98 +38,7 @@ struct X6DParams {
     const unsigned long long* amax_b;
 };
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-constexpr int planes_of(int NS) { return NS == 4 ? 2 : NS; }      // NS = 4: fp16x3, two fp16 terms of the scaled operand (gemm_x6.hip)
-template <int NS>
-__device__ __forceinline__ void split3_pair(f32x2 v, unsigned (&o)[3], float scale = 1.f) {
-    if (NS == 4) {
-        const f32x2 vs = v * scale;
-        const f16x2 h = __builtin_convertvector(vs, f16x2);
-        o[0] = __builtin_bit_cast(unsigned, h);
-        const f32x2 r1 = vs - __builtin_convertvector(h, f32x2);
-        const f16x2 l = __builtin_convertvector(r1, f16x2);
-        o[1] = __builtin_bit_cast(unsigned, l);
-        return;
-    }
-    const bf16x2 h = __builtin_convertvector(v, bf16x2);
-    o[0] = __builtin_bit_cast(unsigned, h);
-    if (NS == 1) return;
-    f32x2 hf;
-    hf.x = __uint_as_float(o[0] << 16); hf.y = __uint_as_float(o[0] & 0xffff0000u);
-    const f32x2 r1 = v - hf;
-    const bf16x2 m = __builtin_convertvector(r1, bf16x2);
-    o[1] = __builtin_bit_cast(unsigned, m);
-    if (NS == 2) return;
-    f32x2 mf;
-    mf.x = __uint_as_float(o[1] << 16); mf.y = __uint_as_float(o[1] & 0xffff0000u);
-    const f32x2 r2 = r1 - mf;
-    const bf16x2 l = __builtin_convertvector(r2, bf16x2);
-    o[2] = __builtin_bit_cast(unsigned, l);
-}
-
-// K-contiguous operand: thread = (k-quad tid & 3, rows (tid >> 2) + 64 i); r[i] = 4 k of row i
-template <int NS>
-__device__ __forceinline__ void kc_store_c(unsigned char* __restrict__ S, const f32x4 (&r)[2], float scale) {
-    const int tid = threadIdx.x;
-    unsigned char* q = S + ((tid >> 1) & 1) * PLANEB + (tid >> 2) * 16 + (tid & 1) * 8;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        unsigned lo[3], hi2[3];
-        split3_pair<NS>((f32x2){r[i].x, r[i].y}, lo, scale);
-        split3_pair<NS>((f32x2){r[i].z, r[i].w}, hi2, scale);
-#pragma unroll
-        for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * SPLITB + i * 1024) = (u32x2){lo[s], hi2[s]};
-    }
-}
-// row-contiguous operand: wave w holds k-octet w >> 1 of rows 64 (w & 1) ..+63; lane = (k-pair g = lane >> 4, rows
-// 4 (lane & 15) ..+3); r[e] = those 4 rows at k = 8 (w >> 1) + 2 g + e.  The four lanes 16 apart hold the four k-pairs of
-// the same 4 rows: a 4 x 4 transpose across them (v_permlane16_swap, then v_permlane32_swap: 4 per split) leaves lane
-// g with the complete 16-B record of row g -- a wave stores 1 KiB contiguous per split.
-template <int NS>
-__device__ __forceinline__ void mc_store_c(unsigned char* __restrict__ S, const f32x4 (&r)[2], float scale) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned o[4][3];
-    split3_pair<NS>((f32x2){r[0].x, r[1].x}, o[0], scale);
-    split3_pair<NS>((f32x2){r[0].y, r[1].y}, o[1], scale);
-    split3_pair<NS>((f32x2){r[0].z, r[1].z}, o[2], scale);
-    split3_pair<NS>((f32x2){r[0].w, r[1].w}, o[3], scale);
-    unsigned char* q = S + (w >> 1) * PLANEB + ((w & 1) * 64 + (lane & 15) * 4 + (lane >> 4)) * 16;
-#pragma unroll
-    for (int s = 0; s < planes_of(NS); ++s) {
-        // X[g][i] = o[i][s] in lane group g.  permlane16_swap(a, b): a.group1 <-> b.group0, a.group3 <-> b.group2;
-        // permlane32_swap(a, b): a.groups{2,3} <-> b.groups{0,1}.  After both: (c0, c1, c2, c3) in group g = X[0..3][g].
-        const u32x2 p01 = __builtin_amdgcn_permlane16_swap(o[0][s], o[1][s], false, false);
-        const u32x2 p23 = __builtin_amdgcn_permlane16_swap(o[2][s], o[3][s], false, false);
-        const u32x2 c02 = __builtin_amdgcn_permlane32_swap(p01.x, p23.x, false, false);
-        const u32x2 c13 = __builtin_amdgcn_permlane32_swap(p01.y, p23.y, false, false);
-        *reinterpret_cast<u32x4*>(q + s * SPLITB) = (u32x4){c02.x, c13.x, c02.y, c13.y};
-    }
-}
-
-// TR form of mc_store_c (same thread map): the four rows' terms at one k are one 8-byte store per term, no cross-lane traffic
-template <int NS>
-__device__ __forceinline__ void mc_store_tr(unsigned char* __restrict__ S, const f32x4 (&r)[2], float scale) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned char* q = S + (8 * (w >> 1) + 2 * (lane >> 4)) * TRROW + ((w & 1) * 64 + (lane & 15) * 4) * 2;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        unsigned a[3], b[3];
-        split3_pair<NS>((f32x2){r[e].x, r[e].y}, a, scale);
-        split3_pair<NS>((f32x2){r[e].z, r[e].w}, b, scale);
-#pragma unroll
-        for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * TRTERM + e * TRROW) = (u32x2){a[s], b[s]};
-    }
-}
-// the 32x32x16 operand (lane: row lane & 31, k 8 (lane >> 5) ..+7) from a TR image: per 16-lane group a 4 k x 16 row block, lane 4 q + p of the
-// group addressing k-row q, rows 4 p ..+3; `at` = this lane's address for the first four k, the next four lie 4 k-rows on.  (EXEC is all ones
-// at every call: the callers sit in uniform control flow.)  The same eight halves in the same order as the 16-B record of the permlane path.
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* at) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at + 4 * TRROW));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
+// the split, the LDS stores (kc_store_w, mc_store_w, mc_store_wtr), tr_frag and the product order: x6_tile.h
 
 // CONV (TA == 0): k = (tap j, channel c), A[m][k] = x[m + off_j][c] with rows whose source frame falls outside the clip read as zero
 // (a 16-deep stage lies inside one tap: C % 32 == 0); TB == 1: B = one [Co][Ci] plane per tap; TB == 0 (data gradient): the
@@ -158,9 +54,7 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
     const int l31 = lane & 31, hi = lane >> 5;
 
     const int tn_ = gridDim.x, nt_ = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * tn_ + blockIdx.x;
-    const int xq = nt_ >> 3, xr = nt_ & 7, xcd = lin & 7, slot = lin >> 3;
-    const int til = xcd * xq + min(xcd, xr) + slot;           // XCD-contiguous tile order (see gemm.hip)
+    const int til = m3t_xcd_tile(blockIdx.y * tn_ + blockIdx.x, nt_);      // XCD-contiguous tile order (x6_tile.h)
     const int bm = (til / tn_) * BM, bn = (til % tn_) * BN;
     const int k_begin = blockIdx.z * p.kchunk;
     const int k_end = min(p.K, k_begin + p.kchunk);
@@ -269,15 +163,14 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
         ++loaded;
     };
     auto sstore = [&](unsigned char* st, const f32x4 (&ra)[2], const f32x4 (&rb)[2]) {
-        if (TA == 0) kc_store_c<NS>(st, ra, sc_a); else if (TRA) mc_store_tr<NS>(st, ra, sc_a); else mc_store_c<NS>(st, ra, sc_a);
-        if (TB == 1) kc_store_c<NS>(st + OPERB, rb, sc_b); else if (TRB) mc_store_tr<NS>(st + OPERB, rb, sc_b); else mc_store_c<NS>(st + OPERB, rb, sc_b);
+        if (TA == 0) kc_store_w<NS, 2, PLANEB>(st, ra, sc_a);
+        else if (TRA) mc_store_wtr<NS, TRROW>(st, ra[0], ra[1], sc_a, 0);
+        else mc_store_w<NS, PLANEB>(st, ra[0], ra[1], sc_a, 0);
+        if (TB == 1) kc_store_w<NS, 2, PLANEB>(st + OPERB, rb, sc_b);
+        else if (TRB) mc_store_wtr<NS, TRROW>(st + OPERB, rb[0], rb[1], sc_b, 0);
+        else mc_store_w<NS, PLANEB>(st + OPERB, rb[0], rb[1], sc_b, 0);
     };
 
-    // the products, smallest first.  NS = 3: (a3,b1) (a2,b2) (a1,b3) (a2,b1) (a1,b2) (a1,b1); NS = 2 ("high" mode): the last four
-    // entries read (a2,b2) (a2,b1) (a1,b2) (a1,b1); NS = 1: (a1,b1)
-    constexpr int NSB = NS == 4 ? 2 : NS;             // (the bf16 product table; unused when NS = 4)
-    constexpr int PA[6] = {NSB - 1, NSB / 2, NSB == 2 ? 1 : 0, NSB == 2 ? 1 : NSB / 2, 0, 0};
-    constexpr int PB[6] = {0, NSB / 2, NSB == 2 ? 1 : NSB - 1, 0, NSB == 2 ? 1 : NSB / 2, 0};
     const int tro = (8 * hi + ((lane >> 2) & 3)) * TRROW + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;      // TR: this lane's block address
     const int fro_a = TRA ? tro + wm * 128 : hi * PLANEB + (wm * 64 + l31) * 16;
     const int fro_b = OPERB + (TRB ? tro + wn * 128 : hi * PLANEB + (wn * 64 + l31) * 16);
@@ -290,28 +183,17 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
         for (int s = 0; s < NP; ++s)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                if (TRA) fa[s][i] = tr_frag(cur + fro_a + s * TRTERM + i * 64);
+                if (TRA) fa[s][i] = tr_frag<TRROW>(cur + fro_a + s * TRTERM + i * 64);
                 else fa[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_a + s * SPLITB + i * 512);
-                if (TRB) fb[s][i] = tr_frag(cur + fro_b + s * TRTERM + i * 64);
+                if (TRB) fb[s][i] = tr_frag<TRROW>(cur + fro_b + s * TRTERM + i * 64);
                 else fb[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_b + s * SPLITB + i * 512);
             }
         sstore(nxt, ua, ub);                                  // (after the last stage: a stage nobody reads)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                f32x16 c = acc[i][j];
-                if (NS == 4) {                 // fp16x3: lo hi, hi lo, hi hi
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[1][i]), __builtin_bit_cast(f16x8, fb[0][j]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0][i]), __builtin_bit_cast(f16x8, fb[1][j]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0][i]), __builtin_bit_cast(f16x8, fb[0][j]), c, 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int q = (NS == 3 ? 0 : (NS == 2 ? 2 : 5)); q < 6; ++q)
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[q]][i], fb[PB[q]][j], c, 0, 0, 0);
-                }
-                acc[i][j] = c;
-            }
+            for (int j = 0; j < 2; ++j)
+                acc[i][j] = x6_mac<NS>(acc[i][j], fa, i, fb, j);
     };
 
     unsigned char* buf0 = ldsb;
@@ -332,7 +214,7 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
     }
 
     const bool direct = p.splits == 1;
-    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;
+    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;      // one K pass: C itself; else this split's slab, [M][N] dense
     const int ldd = direct ? p.ldc : p.N;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -356,12 +238,8 @@ __global__ __launch_bounds__(NTH, 3) void sgemm_x6d_kernel(X6DParams p) {
                     if (p.act == 1) v = m3t_relu(v) * mk;
                     else if (p.act == 2) v = m3t_relu(m3t_relu(v) * mk + p.cv_res[o]);
                     else if (p.cv_res) v += p.cv_res[o];
-                } else if (direct) {
-                    v += bv;
-                    if (p.act == 1) v = m3t_relu(v);
-                    if (p.accumulate) v += *q;
-                }
-                *q = v;
+                    *q = v;
+                } else x6_plain_out(v, q, bv, direct, p.act, p.accumulate);
             }
         }
 }
@@ -388,14 +266,8 @@ int m3t_sgemm_x6d_launch(int transA, int transB, int M, int N, int K, const floa
     const bool tr = m3t_gemm_tr_enabled();
 #define M3T_X6D_GO(TA_, TB_, SEG_, NS_, TR_)                                                                          \
     do {                                                                                                               \
-        static bool attr_set = false;                                                                                  \
-        if (!attr_set) {                                                                                               \
-            hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6d_kernel<TA_, TB_, SEG_, NS_, false, TR_>,        \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-            if (ea != hipSuccess) return (int)ea;                                                                      \
-            attr_set = true;                                                                                           \
-        }                                                                                                              \
-        sgemm_x6d_kernel<TA_, TB_, SEG_, NS_, false, TR_><<<grid, block, lds, s>>>(p);                                 \
+        const int el = x6_launch_dyn_lds<sgemm_x6d_kernel<TA_, TB_, SEG_, NS_, false, TR_>>(grid, block, lds, s, p);   \
+        if (el) return el;                                                                                             \
     } while (0)
 #define M3T_X6D_DISPATCH(NS_, TR_)                                                                                   \
     do {                                                                                                               \
@@ -432,14 +304,8 @@ int m3t_conv_x6d_launch(const float* x, const float* w_t, const float* bias, con
     const size_t lds = 2 * (size_t)STAGEB;
 #define M3T_CONVD_GO(TB_, NS_)                                                                                            \
     do {                                                                                                                   \
-        static bool attr_set = false;                                                                                      \
-        if (!attr_set) {                                                                                                   \
-            hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6d_kernel<0, TB_, false, NS_, true>,                   \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
-            if (ea != hipSuccess) return (int)ea;                                                                          \
-            attr_set = true;                                                                                               \
-        }                                                                                                                  \
-        sgemm_x6d_kernel<0, TB_, false, NS_, true><<<grid, block, lds, s>>>(p);                                            \
+        const int el = x6_launch_dyn_lds<sgemm_x6d_kernel<0, TB_, false, NS_, true>>(grid, block, lds, s, p);              \
+        if (el) return el;                                                                                                 \
     } while (0)
     if (anti) {
         if (bf16_operands == 1) M3T_CONVD_GO(0, 1); else if (bf16_operands == 2) M3T_CONVD_GO(0, 2); else M3T_CONVD_GO(0, 3);

@@ -8,39 +8,25 @@
 // A-operand staging per flop -- LDS traffic per MFMA falls by a quarter ((128 + 256) instead of 2 x (128 + 128) rows per 128 x 256 x 16 step:
 // the 128-tile kernel needs the LDS pipe as long as the matrix pipe), the in-kernel operand split by the same quarter.
 //
-// Same arithmetic as gemm_x6d.hip (same exact split, same products smallest first, same k order, same split-K slabs): results are
+// Same arithmetic as gemm_x6d.hip (the split, stores and product order of x6_tile.h, same k order, same split-K slabs): results are
 // bit-identical to the 128-tile kernels'.  4 waves as 2 (M) x 2 (N), each 64 x 128 = 2 x 4 v_mfma_f32_32x32x16 tiles; 16-k stages,
 // double-buffered LDS, one barrier per stage.  The planner (gemm.hip, plan_gemm) takes it where it fills the chip better.
-#include "common.h"
-#include <atomic>
+#include "x6_tile.h"
 #include <cstdlib>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int WM = 128, WN = 256, WKS = 16, WTH = 256;
+constexpr int WM = 128, WN = 256, WKS = X6_STAGE_K, WTH = 256;
 constexpr int PLA = WM * 16 + 128;                 // one k-octet plane of A: 128 rows x 16 B (+128 B: the stage's two planes hit distinct banks)
 constexpr int PLB = WN * 16 + 128;                 // ... of B: 256 rows
-constexpr int planes_of(int NS) { return NS == 4 ? 2 : NS; }
 constexpr int opera(int NS) { return planes_of(NS) * 2 * PLA; }
 constexpr int operb(int NS) { return planes_of(NS) * 2 * PLB; }
 constexpr int stageb(int NS) { return opera(NS) + operb(NS); }
-// TR (NS = 4): a row-contiguous operand lies in LDS as it lies in memory -- per term [k 16][rows] halves, a k-row every 2 x rows + 64 B (the
-// four k-rows of one transposed read, and the two 16-row blocks of a 32-lane half, cover the 64 banks once) -- and a fragment is two
-// ds_read_b64_tr_b16 (four k each): gemm_x6d.hip's image, B's k-rows 256 wide
+// TR (NS = 4): the transposed-read image of a row-contiguous operand (x6_tile.h), B's k-rows 256 wide
 constexpr int TRROWA = WM * 2 + 64, TRROWB = WN * 2 + 64;
 constexpr int opera_of(int NS, bool tr) { return tr ? 2 * WKS * TRROWA : opera(NS); }
 constexpr int operb_of(int NS, bool tr) { return tr ? 2 * WKS * TRROWB : operb(NS); }
 constexpr int stageb_of(int NS, int TA, int TB, bool tr) { return opera_of(NS, tr && TA == 1) + operb_of(NS, tr && TB == 0); }
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 struct X6WParams {
     const float* A; const float* B; float* C; const float* bias; float* ws;
@@ -51,93 +37,7 @@ struct X6WParams {
     const unsigned long long* amax_b;
 };
 
-// (the exact splits of gemm_x6d.hip)
-template <int NS>
-__device__ __forceinline__ void split3_pair(f32x2 v, unsigned (&o)[3], float scale = 1.f) {
-    if (NS == 4) {
-        const f32x2 vs = v * scale;
-        const f16x2 h = __builtin_convertvector(vs, f16x2);
-        o[0] = __builtin_bit_cast(unsigned, h);
-        const f32x2 r1 = vs - __builtin_convertvector(h, f32x2);
-        const f16x2 l = __builtin_convertvector(r1, f16x2);
-        o[1] = __builtin_bit_cast(unsigned, l);
-        return;
-    }
-    const bf16x2 h = __builtin_convertvector(v, bf16x2);
-    o[0] = __builtin_bit_cast(unsigned, h);
-    f32x2 hf;
-    hf.x = __uint_as_float(o[0] << 16); hf.y = __uint_as_float(o[0] & 0xffff0000u);
-    const f32x2 r1 = v - hf;
-    const bf16x2 m = __builtin_convertvector(r1, bf16x2);
-    o[1] = __builtin_bit_cast(unsigned, m);
-    f32x2 mf;
-    mf.x = __uint_as_float(o[1] << 16); mf.y = __uint_as_float(o[1] & 0xffff0000u);
-    const f32x2 r2 = r1 - mf;
-    const bf16x2 l = __builtin_convertvector(r2, bf16x2);
-    o[2] = __builtin_bit_cast(unsigned, l);
-}
-
-// K-contiguous operand of NR x 64 rows: thread = (k-quad tid & 3, rows (tid >> 2) + 64 i); r[i] = 4 k of row i; PL = the plane's bytes
-template <int NS, int NR, int PL>
-__device__ __forceinline__ void kc_store_w(unsigned char* __restrict__ S, const f32x4 (&r)[NR], float scale) {
-    const int tid = threadIdx.x;
-    unsigned char* q = S + ((tid >> 1) & 1) * PL + (tid >> 2) * 16 + (tid & 1) * 8;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        unsigned lo[3], hi2[3];
-        split3_pair<NS>((f32x2){r[i].x, r[i].y}, lo, scale);
-        split3_pair<NS>((f32x2){r[i].z, r[i].w}, hi2, scale);
-#pragma unroll
-        for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * 2 * PL + i * 1024) = (u32x2){lo[s], hi2[s]};
-    }
-}
-// row-contiguous operand, one 128-row half: wave w holds k-octet w >> 1 of rows 64 (w & 1) ..+63 of the half; lane = (k-pair g = lane >> 4,
-// rows 4 (lane & 15) ..+3); r[e] = those 4 rows at k = 8 (w >> 1) + 2 g + e.  4 x 4 transpose across the four lanes 16 apart (gemm_x6d.hip)
-template <int NS, int PL>
-__device__ __forceinline__ void mc_store_w(unsigned char* __restrict__ S, const f32x4& r0, const f32x4& r1, float scale, int half) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned o[4][3];
-    split3_pair<NS>((f32x2){r0.x, r1.x}, o[0], scale);
-    split3_pair<NS>((f32x2){r0.y, r1.y}, o[1], scale);
-    split3_pair<NS>((f32x2){r0.z, r1.z}, o[2], scale);
-    split3_pair<NS>((f32x2){r0.w, r1.w}, o[3], scale);
-    unsigned char* q = S + (w >> 1) * PL + (half * 128 + (w & 1) * 64 + (lane & 15) * 4 + (lane >> 4)) * 16;
-#pragma unroll
-    for (int s = 0; s < planes_of(NS); ++s) {
-        const u32x2 p01 = __builtin_amdgcn_permlane16_swap(o[0][s], o[1][s], false, false);
-        const u32x2 p23 = __builtin_amdgcn_permlane16_swap(o[2][s], o[3][s], false, false);
-        const u32x2 c02 = __builtin_amdgcn_permlane32_swap(p01.x, p23.x, false, false);
-        const u32x2 c13 = __builtin_amdgcn_permlane32_swap(p01.y, p23.y, false, false);
-        *reinterpret_cast<u32x4*>(q + s * 2 * PL) = (u32x4){c02.x, c13.x, c02.y, c13.y};
-    }
-}
-
-// TR form of mc_store_w (same thread map): the four rows' terms at one k are one 8-byte store per term, no cross-lane traffic; ROW = the
-// image's k-row stride
-template <int NS, int ROW>
-__device__ __forceinline__ void mc_store_wtr(unsigned char* __restrict__ S, const f32x4& r0, const f32x4& r1, float scale, int half) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned char* q = S + (8 * (w >> 1) + 2 * (lane >> 4)) * ROW + (half * 128 + (w & 1) * 64 + (lane & 15) * 4) * 2;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const f32x4& r = e ? r1 : r0;
-        unsigned a[3], b[3];
-        split3_pair<NS>((f32x2){r.x, r.y}, a, scale);
-        split3_pair<NS>((f32x2){r.z, r.w}, b, scale);
-#pragma unroll
-        for (int s = 0; s < planes_of(NS); ++s) *reinterpret_cast<u32x2*>(q + s * WKS * ROW + e * ROW) = (u32x2){a[s], b[s]};
-    }
-}
-// the 32x32x16 operand (lane: row lane & 31, k 8 (lane >> 5) ..+7) from a TR image: per 16-lane group a 4 k x 16 row block, lane 4 q + p of the
-// group addressing k-row q, rows 4 p ..+3; `at` = this lane's address for the first four k, the next four lie 4 k-rows on.  (EXEC is all ones
-// at every call: the callers sit in uniform control flow.)  The same eight halves in the same order as the 16-B record of the permlane path.
-template <int ROW>
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* at) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(at + 4 * ROW));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
+// the split, the LDS stores (kc_store_w, mc_store_w, mc_store_wtr), tr_frag and the product order: x6_tile.h
 
 // BD (TA = 0, TB = 1, NS = 4): the B operand is a STAGED IMAGE of the weights (m3t_f16x3_image_b: [N / 64][K / 8][term][64 rows][16 B] -- one
 // 1-KiB piece per (64-row block, k-octet, term)) and reaches LDS by LDS-DMA (global_load_lds_dwordx4: one piece per wave instruction, no
@@ -156,9 +56,7 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
     const int l31 = lane & 31, hi = lane >> 5;
 
     const int tn_ = gridDim.x, nt_ = gridDim.x * gridDim.y;
-    const int lin = blockIdx.y * tn_ + blockIdx.x;
-    const int xq = nt_ >> 3, xr = nt_ & 7, xcd = lin & 7, slot = lin >> 3;
-    const int til = xcd * xq + min(xcd, xr) + slot;           // XCD-contiguous tile order (see gemm.hip)
+    const int til = m3t_xcd_tile(blockIdx.y * tn_ + blockIdx.x, nt_);      // XCD-contiguous tile order (x6_tile.h)
     const int bm = (til / tn_) * WM, bn = (til % tn_) * WN;
     const int k_begin = blockIdx.z * p.kchunk;
     const int k_end = min(p.K, k_begin + p.kchunk);
@@ -271,9 +169,6 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
         else { mc_store_w<NS, PLB>(st + OPA, rb[0], rb[1], sc_b, 0); mc_store_w<NS, PLB>(st + OPA, rb[2], rb[3], sc_b, 1); }
     };
 
-    // the products, smallest first (NS = 3: (a3,b1) (a2,b2) (a1,b3) (a2,b1) (a1,b2) (a1,b1); NS = 4: lo hi, hi lo, hi hi)
-    constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-    constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
     const int trk = 8 * hi + ((lane >> 2) & 3), trc = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;      // TR: this lane's k-row and column bytes of a block
     const int fro_a = TRA ? trk * TRROWA + trc + wm * 128 : hi * PLA + (wm * 64 + l31) * 16;
     const int fro_b = OPA + (TRB ? trk * TRROWB + trc + wn * 256 : hi * PLB + (wn * 128 + l31) * 16);
@@ -283,12 +178,12 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
         for (int s = 0; s < NP; ++s) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                if (TRA) fa[s][i] = tr_frag<TRROWA>(cur + fro_a + s * WKS * TRROWA + i * 64);
+                if (TRA) fa[s][i] = tr_frag<TRROWA>(cur + fro_a + s * X6_STAGE_K * TRROWA + i * 64);
                 else fa[s][i] = *reinterpret_cast<const bf16x8*>(cur + fro_a + s * 2 * PLA + i * 512);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (TRB) fb[s][j] = tr_frag<TRROWB>(cur + fro_b + s * WKS * TRROWB + j * 64);
+                if (TRB) fb[s][j] = tr_frag<TRROWB>(cur + fro_b + s * X6_STAGE_K * TRROWB + j * 64);
                 else fb[s][j] = *reinterpret_cast<const bf16x8*>(cur + fro_b + s * 2 * PLB + j * 512);
             }
         }
@@ -296,19 +191,8 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                f32x16 c = acc[i][j];
-                if (NS == 4) {
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[1][i]), __builtin_bit_cast(f16x8, fb[0][j]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0][i]), __builtin_bit_cast(f16x8, fb[1][j]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[0][i]), __builtin_bit_cast(f16x8, fb[0][j]), c, 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 6; ++q)
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[q] < NP ? PA[q] : 0][i], fb[PB[q] < NP ? PB[q] : 0][j], c, 0, 0, 0);
-                }
-                acc[i][j] = c;
-            }
+            for (int j = 0; j < 4; ++j)
+                acc[i][j] = x6_mac<NS>(acc[i][j], fa, i, fb, j);
     };
 
     unsigned char* buf0 = ldsb;
@@ -360,7 +244,7 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
     }
 
     const bool direct = p.splits == 1;
-    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;
+    float* dst = direct ? p.C : p.ws + (size_t)blockIdx.z * p.M * p.N;      // one K pass: C itself; else this split's slab, [M][N] dense
     const int ldd = direct ? p.ldc : p.N;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -373,13 +257,7 @@ __global__ __launch_bounds__(WTH, 2) void sgemm_x6w_kernel(X6WParams p) {
                 const int row = bm + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 float v = acc[i][j][r];
                 if (NS == 4) v = v * sc_ia * sc_ib;              // (exact: powers of two)
-                float* q = dst + (size_t)row * ldd + col;
-                if (direct) {
-                    v += bv;
-                    if (p.act == 1) v = m3t_relu(v);
-                    if (p.accumulate) v += *q;
-                }
-                *q = v;
+                x6_plain_out(v, dst + (size_t)row * ldd + col, bv, direct, p.act, p.accumulate);
             }
         }
 }
@@ -401,19 +279,11 @@ int m3t_sgemm_x6w_launch(int transA, int transB, int M, int N, int K, const floa
     p.act = act; p.accumulate = accumulate; p.splits = splits; p.kchunk = kchunk;
     p.seg_len = seg_len; p.seg_stride = seg_stride; p.a_off = a_off; p.b_off = b_off;
     dim3 grid(N / WN, M / WM, splits), block(WTH);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return M3T_EINVAL;
 #define M3T_X6W_GO(TA_, TB_, SEG_, NS_, TR_)                                                                          \
     do {                                                                                                               \
         const size_t lds = 2 * (size_t)stageb_of(NS_, TA_, TB_, TR_);                                                  \
-        static std::atomic<unsigned> attr_set{0};           /* one bit per device (was one flag per process) */           \
-        if (!(attr_set.load(std::memory_order_relaxed) & (1u << dev))) {                                               \
-            hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6w_kernel<TA_, TB_, SEG_, NS_, 0, TR_>,            \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-            if (ea != hipSuccess) return (int)ea;                                                                      \
-            attr_set.fetch_or(1u << dev, std::memory_order_relaxed);                                                   \
-        }                                                                                                              \
-        sgemm_x6w_kernel<TA_, TB_, SEG_, NS_, 0, TR_><<<grid, block, lds, s>>>(p);                                     \
+        const int el = x6_launch_dyn_lds<sgemm_x6w_kernel<TA_, TB_, SEG_, NS_, 0, TR_>>(grid, block, lds, s, p);       \
+        if (el) return el;                                                                                             \
     } while (0)
 #define M3T_X6W_DISPATCH(NS_, TR_)                                                                                   \
     do {                                                                                                               \
@@ -445,14 +315,6 @@ int m3t_sgemm_x6w_bimg_launch(int M, int N, int K, const float* A, int lda, cons
     p.seg_len = p.seg_stride = p.a_off = p.b_off = 0;
     dim3 grid(N / WN, M / WM, splits), block(WTH);
     const size_t lds = 2 * (size_t)stageb(4);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return M3T_EINVAL;
-    static std::atomic<unsigned> attr_set{0};
-    if (!(attr_set.load(std::memory_order_relaxed) & (1u << dev))) {
-        hipError_t ea = hipFuncSetAttribute((const void*)sgemm_x6w_kernel<0, 1, false, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return (int)ea;
-        attr_set.fetch_or(1u << dev, std::memory_order_relaxed);
-    }
-    sgemm_x6w_kernel<0, 1, false, 4, 1><<<grid, block, lds, s>>>(p);
-    return (int)hipGetLastError();
+    const int el = x6_launch_dyn_lds<sgemm_x6w_kernel<0, 1, false, 4, 1>>(grid, block, lds, s, p);
+    return el ? el : (int)hipGetLastError();
 }

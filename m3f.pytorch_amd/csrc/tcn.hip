@@ -9,7 +9,7 @@
 //     bias, ReLU and the residual add + ReLU of the block are fused in the epilogue;
 //   * the same kernel run anti-causally with the [co][ci] weight read as [K][N] is the
 //     data gradient; the weight gradient is K segment-mapped TN GEMMs (m3t_sgemm).
-#include "common.h"
+#include "x6_tile.h"
 #include <cstdlib>
 
 namespace {
@@ -273,8 +273,6 @@ __global__ __launch_bounds__(256) void batched_transpose_kernel(const float* __r
 // [R][C] -> the m3t_f16x3_split IMAGE of [C][R] (round 6): the transpose above with the split of its result folded in -- for a source whose
 // magnitude slot its PRODUCER raised (BatchNorm's apply / dx kernels), so the scale is known before the first store.  R % 4 == 0 (R = the
 // channels: four consecutive ones share a 16-byte record {hi 0|1, hi 2|3, lo 0|1, lo 2|3}); a thread packs the record of (column, channel quad).
-typedef _Float16 tr_f16x2 __attribute__((ext_vector_type(2)));
-typedef float tr_f32x2 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void batched_transpose_img_kernel(const float* __restrict__ src, float* __restrict__ dst, int R, int C,
                                                                     const unsigned long long* __restrict__ slot, float* __restrict__ rowsum) {
     __shared__ float tile[32][33];
@@ -298,14 +296,8 @@ __global__ __launch_bounds__(256) void batched_transpose_img_kernel(const float*
     const int q = threadIdx.x & 7, ci = threadIdx.x >> 3;       // channel quad (rows r0 + 4 q ..+3 of the source), column c0 + ci
     const int c = c0 + ci, r = r0 + 4 * q;
     if (c < C && r < R) {
-        const tr_f32x2 a = (tr_f32x2){tile[4 * q][ci], tile[4 * q + 1][ci]} * sc, b = (tr_f32x2){tile[4 * q + 2][ci], tile[4 * q + 3][ci]} * sc;
-        const tr_f16x2 ha = __builtin_convertvector(a, tr_f16x2), hb = __builtin_convertvector(b, tr_f16x2);
-        const tr_f16x2 la = __builtin_convertvector(a - __builtin_convertvector(ha, tr_f32x2), tr_f16x2);
-        const tr_f16x2 lb = __builtin_convertvector(b - __builtin_convertvector(hb, tr_f32x2), tr_f16x2);
-        float4 o;
-        o.x = __uint_as_float(__builtin_bit_cast(unsigned, ha)); o.y = __uint_as_float(__builtin_bit_cast(unsigned, hb));
-        o.z = __uint_as_float(__builtin_bit_cast(unsigned, la)); o.w = __uint_as_float(__builtin_bit_cast(unsigned, lb));
-        *reinterpret_cast<float4*>(dst + boff + (size_t)c * R + r) = o;
+        *reinterpret_cast<float4*>(dst + boff + (size_t)c * R + r) =
+            f16x3_record((f32x2){tile[4 * q][ci], tile[4 * q + 1][ci]}, (f32x2){tile[4 * q + 2][ci], tile[4 * q + 3][ci]}, sc);
     }
 }
 
