@@ -15,7 +15,9 @@ An item is (video, start, track_len) -- or (video, start), track_len = window, t
 `batch['video']` stays the caller's (decode, then `m3t.video.ingest`): for a store given `has_image`, collate adds the `video_frame_idx`
 rows that go with the frames start .. start + track_len - 1 of each item.  The frames themselves have a resident store of their own,
 `m3t.jpeg.FrameStore` (the files' scan bytes on the device, a batch of windows decoded from them; its `has_image(video)` is the array this
-store takes).  Out of scope: the file-system scan, prefetch threads and DDP sharding.
+store takes).  The file-system scan, the epoch's order of items and draws and the sharding are m3t/feed.py, which drives both stores
+(`train_items` draws an epoch's choices in one run; the reference interleaves them with each clip's mirror, crop and cutout draws, which
+is the feed's plan).  Out of scope: prefetch threads.
 """
 import numpy as np
 import torch

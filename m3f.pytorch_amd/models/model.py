@@ -18,7 +18,9 @@ decoder kernels of csrc/attdec.hip.  Validation/test window stitching (SURVEY 8(
 `batch['video']` may also be the frames as decoded -- uint8 [N, Ts, Hs, Ws, 3], with the loader's draws in `batch['video_aug']` and the frame
 indices in `batch['video_frame_idx']` (m3t/video.py): crop, mirror, cutout and the normalisation then run as one kernel in front of the first
 convolution; a float32 `video` takes the reference's route.
-Out of scope: dataloaders (need the Aff-Wild2 dataset and cv2), the LR range finder.
+`train_dataloader` / `val_dataloader` / `test_dataloader` (model.py:409-446) return the epoch feed of m3t/feed.py: the dataset folder scanned
+by the reference's rules, the batches cut, decoded and augmented on the device in the reference's order of draws; nothing needs cv2.
+Out of scope: the LR range finder.
 """
 import os
 from argparse import ArgumentParser
@@ -253,6 +255,25 @@ class AffWild2VA(_Base):
     def on_batch_end(self):
         if getattr(self.hparams, 'scheduler', None) == 'cyclic' and hasattr(self, 'cyclic_scheduler'):
             self.cyclic_scheduler.step()
+
+    # ------------------------------------------------------------------ data (m3t/feed.py; the reference's model.py:409-446)
+    def _feed(self, split):
+        from m3t import feed
+        rank, world = 0, 1
+        if getattr(self.hparams, 'distributed', False) and torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+        return feed.feed_from_hparams(self.hparams, split, rank, world, visual=getattr(self, 'visual', None))
+
+    def train_dataloader(self):
+        return self._feed('train')
+
+    def val_dataloader(self):
+        return self._feed('val')
+
+    def test_dataloader(self):
+        if self.hparams.test_on_val:
+            return self.val_dataloader()
+        return self._feed('test')
 
     # ------------------------------------------------------------------ optimisation (host glue)
     def configure_optimizers(self):
