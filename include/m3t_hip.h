@@ -967,6 +967,17 @@ int m3t_stack_context_batch(const float* mels, long long total_rows, int n_mels,
                             int step, int width, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * The AudioSet label rows (csrc/audioset.hip; m3t.audioset.WaveStore): the reference's loader builds one float32 multi-hot vector per listed
+ * clip when it scans the folder and hands a batch a stack of them (models/audioset_dataset.py:116-118, :131).  Here the vectors of a split
+ * stay on the device as ONE uint8 matrix table [n_files][n_classes] (0 / 1), and one launch writes a batch's rows:
+ *     out[n][c] = (float) table[items[n]][c],   n < N, c < n_classes           (out: float32 [N][n_classes])
+ * items: device long long [N], the clips' indices into the table; a repeat is allowed.  A flat grid-stride over N * n_classes cells, byte
+ * loads and float stores, no atomics, no order.  An item outside [0, n_files) leaves its row of `out` untouched and reads nothing; the host
+ * refuses such an item before the launch (m3t.audioset).  M3T_EINVAL: null pointers, items not 8-byte or out not 4-byte aligned, n_files or
+ * n_classes <= 0, N < 0; N == 0 returns 0. */
+int m3t_label_rows(const uint8_t* table, long long n_files, int n_classes, const long long* items, int N, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Video ingest: what the reference's two loaders do to pixels between the decoder and the first convolution (models/dataset.py:16-31,46-80
  * and :312, models/vox2_dataset.py:14-50, models/cv_augment.py:6-37) and the normalisation of models/model.py:106, in one pass over the
  * uint8 frames as decoded, frames [N][Ts][Hs][Ws][3] (channel order as stored).  For clip n, output frame t, pixel (y, x), channel c:

@@ -26,7 +26,8 @@ temporal crop with np.pad 'wrap', the spectrogram above, the context stack) in t
   load_audio_batch(mels, starts, ...)    the AffWild2 loader's collate step (`models/dataset.py:83-95, :276-306`): N pre-extracted tracks
                                          -> [N, window, 200] in one launch, edge padding and the "fps < 15 -> zeros" rule included
 
-Out of scope: wav decoding and resampling (`librosa.load`), which stay on the host.
+Wav reading is m3t/wav.py (16-bit mono PCM, on the host) and the resident store of a split's clips m3t/audioset.py.  Out of scope:
+resampling and the other sample formats `librosa.load` takes.
 """
 import ctypes as C
 import math
@@ -150,14 +151,32 @@ def draw_audioset(tot_samples, length, training):
     return {"fps": fps, "hop": hop_length(fps), "start": start, "nsamples": nsamples}
 
 
-def plan_waves(waves, aug=None, length=32, lengths=None):
+def plan_waves(waves, aug=None, length=32, lengths=None, offsets=None):
     """Host validation of an ingest call, before anything touches a device: returns (wave, table, R) -- the flat sample buffer (a 1-D int16 or
     float32 tensor on the device `waves` lives on), the per-clip table int64 [N, 8] = off, len, start, nsamples, hop, nf, row_off, 0
     (include/m3t_hip.h) and the number of spectrogram rows of the batch.  ValueError for a wrong dtype or rank, a draw count different from
-    N, hop <= 0, nsamples <= 0, length <= 0, a start outside [0, max(len, nsamples + 5)), an empty clip."""
+    N, hop <= 0, nsamples <= 0, length <= 0, a start outside [0, max(len, nsamples + 5)), an empty clip.
+    The store form, `offsets` given: `waves` is a flat 1-D tensor that is read in place (a resident store, m3t.audioset.WaveStore) and clip n
+    is waves[offsets[n] : offsets[n] + lengths[n]]; clips may repeat or overlap.  No sample is copied or looked at; ValueError for an
+    offset or a length that leaves the buffer.  The table is the list form's but for the offsets."""
     if int(length) <= 0:
         raise ValueError("ingest: length must be positive, got %r" % (length,))
-    if isinstance(waves, (list, tuple)):
+    if offsets is not None:
+        if not isinstance(waves, torch.Tensor) or waves.dim() != 1 or not waves.is_contiguous():
+            raise ValueError("ingest: with offsets, waves must be one flat contiguous 1-D tensor")
+        if lengths is None:
+            raise ValueError("ingest: offsets go with the clips' lengths")
+        offs = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets)
+        lens = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths)
+        if offs.ndim != 1 or lens.shape != offs.shape or not (np.issubdtype(offs.dtype, np.integer) and np.issubdtype(lens.dtype, np.integer)):
+            raise ValueError("ingest: offsets and lengths must be integers [N]")
+        offs, lens = offs.astype(np.int64), lens.astype(np.int64)
+        total = int(waves.numel())
+        for n in np.flatnonzero((offs < 0) | (lens <= 0) | (offs > total - lens)):
+            raise ValueError("ingest: clip %d: samples %d .. %d lie outside the buffer's %d (or the clip is empty)"
+                             % (n, offs[n], int(offs[n]) + int(lens[n]), total))
+        wave = waves.detach()
+    elif isinstance(waves, (list, tuple)):
         clips = [np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w) for w in waves]
         if not clips:
             raise ValueError("ingest: no clips")
@@ -228,21 +247,32 @@ def _mel_sparse(device):
     return c
 
 
-def ingest(waves, aug=None, length=32, lengths=None, pad_mode="constant", top_db=80.0):
-    """waves: decoded 16 kHz PCM, int16 or float32: [N, S] (tensor or array; `lengths` int [N] for ragged clips stored in rows of S) or a
-    list of 1-D arrays.  A host tensor is copied to the device with non_blocking=True -- pin it to overlap the copy.  aug: one draw per
-    clip (draw_audioset) or None = the evaluation draws (30 fps, centred crop).  -> float32 device tensor [N, length, 200]: per clip what
-    load_audio(melspec_db(crop, fps), 0, length) gives (audioset_dataset.py:58-87), the dB floor taken from the clip's own maximum.
+def ingest(waves, aug=None, length=32, lengths=None, pad_mode="constant", top_db=80.0, offsets=None):
+    """waves: decoded 16 kHz PCM, int16 or float32: [N, S] (tensor or array; `lengths` int [N] for ragged clips stored in rows of S), a
+    list of 1-D arrays, or -- with `offsets` and `lengths`, int [N] -- one flat buffer read in place (plan_waves' store form: nothing is
+    copied when it lives on the device).  A host tensor is copied to the device with non_blocking=True -- pin it to overlap the copy.
+    aug: one draw per clip (draw_audioset) or None = the evaluation draws (30 fps, centred crop).  -> float32 device tensor
+    [N, length, 200]: per clip what load_audio(melspec_db(crop, fps), 0, length) gives (audioset_dataset.py:58-87), the dB floor taken from the clip's own maximum.
     Everything is validated on the host first (ValueError); the per-clip table reaches the device in one copy; three kernels and one GEMM."""
     if pad_mode not in ("constant", "reflect"):
         raise ValueError("pad_mode must be 'constant' or 'reflect'")
-    wave, table, R = plan_waves(waves, aug, length, lengths)
+    wave, table, R = plan_waves(waves, aug, length, lengths, offsets)
     if not torch.cuda.is_available():
         raise M3THipError("m3t.audio needs the GPU: the M3T path has no CPU fallback")
     dev = wave.device if wave.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    N, T, bins = table.shape[0], int(length), 1 + N_FFT // 2
     tab = torch.from_numpy(table.reshape(-1)).to(dev, non_blocking=True)
-    wave = wave.to(dev, non_blocking=True)
+    return ingest_planned(wave.to(dev, non_blocking=True), tab, table.shape[0], R, length, pad_mode, top_db)
+
+
+def ingest_planned(wave, tab, N, R, length=32, pad_mode="constant", top_db=80.0):
+    """ingest's launches for a batch that is planned and on the device: wave, the flat sample buffer; tab, plan_waves' table as a device
+    int64 tensor (N * 8 values, 8-byte aligned -- it may be a slice of a larger upload); R, the table's row count."""
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError("pad_mode must be 'constant' or 'reflect'")
+    if not (wave.is_cuda and tab.is_cuda and tab.dtype == torch.int64 and tab.is_contiguous() and tab.numel() == 8 * N and wave.dim() == 1):
+        raise ValueError("ingest_planned: a flat device buffer and a device int64 table of %d x 8 values are needed" % N)
+    dev = wave.device
+    N, T, R, bins = int(N), int(length), int(R), 1 + N_FFT // 2
     win, dft, _ = _constants(dev)
     weights, bands, nnz = _mel_sparse(dev)
     L, st = lib(), _stream()

@@ -1,0 +1,352 @@
+"""The AudioSet epoch feed: from a dataset folder to the batch dicts `models.audioset_model.AudioSet` pre-trains on (stage 2 of the
+reference's workflow).  The reference's loader (`models/audioset_dataset.py`, `AudioSetDataset` behind a `DataLoader`) scans the folder,
+and per item decodes a whole 10 s clip with librosa, crops it, and computes the log-Mel rows on the host.  Here:
+
+  scan_audioset   the reference's `__init__` (`audioset_dataset.py:99-121`), rule for rule -> Scan (files, uint8 label matrix).  Host only.
+  WaveStore       every clip of a split read once (m3t/wav.py) into ONE flat int16 device buffer, the label matrix beside it as uint8
+  AudioSetFeed    plan_epoch(epoch) -> [BatchPlan], host only; iterating it yields {'audio': float32 [N, window, 200], 'label': float32
+                  [N, 527]} on the current stream -- what the reference's loader yields, so AudioSet.training_step / validation_step take it
+                  unchanged; set_epoch / state_dict / load_state_dict
+  BatchPlan       one batch: the clips' indices, their draws (m3t.audio.draw_audioset), the batch's index in the epoch
+
+The order of an epoch (`num_workers=0`, which is what the reference's draws are reproducible for) is the reference's by construction: the
+plan runs torch's own `DataLoader` over a small data set whose item i is (i, draw), drawn when it is read -- `shuffle=True` for training,
+sequential otherwise (`audioset_model.py:129-145`), torch's default `DistributedSampler` in BOTH splits when world > 1 (the reference's
+`--distributed`).  Per item `random.choice(FPS_VALUES)` then `random.randint(0, tot - nsamples)` (training; `audioset_dataset.py:60, :69`);
+an evaluation item draws nothing.
+
+A batch is one small table upload (the ingest's per-clip table and the clips' indices in one copy), ONE launch for the labels
+(m3t_label_rows, csrc/audioset.hip) and the ingest's launches (m3t.audio.ingest_planned), which read the crops out of the store in place:
+no sample crosses the bus after the store is built, and nothing is read back.
+
+Everything down to "which clips, which draws" runs without a GPU and without initialising one (the clips' lengths come from the files'
+headers); the store is built when the first batch is asked for (or by build_store()).
+
+Out of scope: resampling and other sample formats (a clip that is not 16 kHz, 16-bit, mono is refused with its name), stereo down-mix, a
+disk cache or a host arena for the store (balanced train is about 7 GB of int16: it fits), prefetch threads, `spec_augment` (defined by the
+reference, never called by it), the VoxCeleb2 loader, multi-GPU measurements (the sharding rule is tested on the host).
+"""
+import os
+import random
+
+import numpy as np
+import torch
+from torch.utils.data import DataLoader, Dataset
+from torch.utils.data.distributed import DistributedSampler
+
+from . import _lib
+from . import audio as _audio
+from . import wav as _wav
+from .ops import lib, _stream, M3THipError
+
+FOLD_MAP = {"train": "balanced_train_segments", "val": "eval_segments"}       # audioset_dataset.py:104
+N_CLASSES = 527
+SR = 16000
+CHUNK_BYTES = 64 << 20
+
+
+# ---- the folder scan ------------------------------------------------------------------------------------------------------------------
+class Scan:
+    """What scan_audioset found.  files: the clips' paths in the reference's order; labels: uint8 [F, 527], 1 where the reference's float
+    vector is 1.0; split, path.  lengths() reads the files' headers (once) -> int64 [F] samples; a rate other than 16 kHz or an empty clip is
+    refused there, with the file named."""
+    __slots__ = ("files", "labels", "split", "path", "_lengths")
+
+    def __len__(self):
+        return len(self.files)
+
+    def lengths(self):
+        if self._lengths is None:
+            self._lengths = np.array([_clip_samples(f) for f in self.files], np.int64)
+        return self._lengths
+
+
+def _clip_samples(path):
+    n, rate = _wav.probe_pcm16(path)
+    _check_clip(path, n, rate)
+    return n
+
+
+def _check_clip(path, n, rate):
+    if rate != SR:
+        raise ValueError("%s: sampled at %d Hz; the store takes %d Hz only (resampling is out of scope: convert the folder first)" % (path, rate, SR))
+    if n <= 0:
+        raise ValueError("%s: an empty clip (no whole sample in its 'data' chunk)" % (path,))
+
+
+def _lines(path, what):
+    try:
+        with open(path, "r") as f:
+            return f.read().splitlines()
+    except OSError as e:
+        raise ValueError("scan_audioset: no %s: %s (%s)" % (what, path, e.strerror or e)) from None
+
+
+def scan_audioset(path, split):
+    """The reference's `AudioSetDataset.__init__` (`audioset_dataset.py:99-121`), rule for rule -> Scan.  Host only.
+      * `path`/class_labels_indices.csv without its first line: the mid of class i is `l.split(',')[1]` of line i (display names may hold
+        commas and quotes: they come third);
+      * `path`/{balanced_train_segments | eval_segments}.csv without its first THREE lines: `name, start, end, "mid,mid,..."` split at
+        ', ' into four; the mids are `ontology[1:-1].split(',')`;
+      * the clip is `path`/<fold>/<name>.wav; a listed clip without a file is skipped silently, before its labels are looked at.
+    Where the reference dies with a bare ValueError (a line that does not split into four) or KeyError (a mid that is not in the class
+    list), this refuses with the file and the line named."""
+    if split not in FOLD_MAP:
+        raise ValueError("scan_audioset: split must be one of %s, got %r" % (tuple(FOLD_MAP), split))
+    fold = FOLD_MAP[split]
+    class_file, annot_file = os.path.join(path, "class_labels_indices.csv"), os.path.join(path, "%s.csv" % fold)
+    mid_map = {}
+    for i, l in enumerate(_lines(class_file, "class list")[1:]):
+        parts = l.split(",")
+        if len(parts) < 2:
+            raise ValueError("scan_audioset: %s, line %d: expected index,mid,display_name, got %r" % (class_file, i + 2, l))
+        mid_map[parts[1]] = i
+    if any(i >= N_CLASSES for i in mid_map.values()):
+        raise ValueError("scan_audioset: %s lists more than %d classes" % (class_file, N_CLASSES))
+    files, rows = [], []
+    for n, l in enumerate(_lines(annot_file, "segment list")[3:]):
+        parts = l.split(", ")
+        if len(parts) != 4:
+            raise ValueError("scan_audioset: %s, line %d: expected 'name, start, end, \"mids\"' (four parts at ', '), got %r" % (annot_file, n + 4, l))
+        name, _, _, ontology = parts
+        wav_path = os.path.join(path, fold, name + ".wav")
+        if not os.path.exists(wav_path):
+            continue
+        row = np.zeros(N_CLASSES, np.uint8)
+        for mid in ontology[1:-1].split(","):
+            if mid not in mid_map:
+                raise ValueError("scan_audioset: %s, line %d: label %r of clip %r is not in %s" % (annot_file, n + 4, mid, name, class_file))
+            row[mid_map[mid]] = 1
+        files.append(wav_path)
+        rows.append(row)
+    s = Scan()
+    s.files, s.split, s.path, s._lengths = files, split, path, None
+    s.labels = np.stack(rows) if rows else np.zeros((0, N_CLASSES), np.uint8)
+    return s
+
+
+# ---- the resident store ---------------------------------------------------------------------------------------------------------------
+def plan_batch(wave, offsets, lengths, items, draws, window):
+    """Host validation of one batch out of a store, before anything touches a device: wave, the store's flat buffer (only its size and dtype
+    are looked at); offsets, lengths int64 [F]; items, the clips' indices; draws, one m3t.audio.draw_audioset dict per item or None.
+    -> (items int64 [N], table int64 [N, 8], R) -- m3t.audio.plan_waves' store form.  ValueError for an item outside the store."""
+    items = np.asarray(items)
+    if items.ndim != 1 or items.size == 0 or not np.issubdtype(items.dtype, np.integer):
+        raise ValueError("WaveStore: a batch needs a non-empty 1-D list of clip indices")
+    items = items.astype(np.int64)
+    F = int(np.asarray(offsets).shape[0])
+    for n in np.flatnonzero((items < 0) | (items >= F)):
+        raise ValueError("WaveStore: item %d of the batch is clip %d; the store holds %d" % (n, items[n], F))
+    _, table, R = _audio.plan_waves(wave, draws, window, lengths=np.asarray(lengths)[items], offsets=np.asarray(offsets)[items])
+    return items, table, R
+
+
+class WaveStore:
+    """The clips of a split on the device.  files: paths read once with m3t.wav.read_pcm16 (a rate other than 16 kHz or an empty clip is
+    refused with the file named); labels: uint8 [F, n_classes] or None.  The samples go to ONE flat int16 device buffer `wave`, staged
+    through a host buffer of at most `chunk_bytes` (a longer clip goes on its own): the host never holds the corpus.  offsets, lengths:
+    int64 [F] on the host, clip i = wave[offsets[i] : offsets[i] + lengths[i]]; label_table: the uint8 matrix on the device.
+    lengths (optional): what the files' headers said; the store refuses a file that now reads differently."""
+
+    def __init__(self, files, labels=None, lengths=None, chunk_bytes=CHUNK_BYTES, device=None):
+        files = list(files)
+        if not files:
+            raise ValueError("WaveStore: no files")
+        if labels is not None:
+            labels = np.ascontiguousarray(labels)
+            if labels.dtype != np.uint8 or labels.ndim != 2 or labels.shape[0] != len(files):
+                raise ValueError("WaveStore: labels must be uint8 [%d, classes]" % len(files))
+        if not torch.cuda.is_available():
+            raise M3THipError("m3t.audioset.WaveStore needs the GPU: the M3T path has no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.files = files
+        if lengths is None:
+            lengths = [_clip_samples(f) for f in files]
+        self.lengths = np.asarray(lengths, np.int64).copy()
+        if self.lengths.shape != (len(files),) or self.lengths.min() <= 0:
+            raise ValueError("WaveStore: one positive length per file is needed")
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        total = int(self.lengths.sum())
+        self.wave = torch.empty(total, dtype=torch.int16, device=self.device)
+        cap = max(int(chunk_bytes) // 2, 1)
+        stage, fill, base = np.empty(min(cap, total), np.int16), 0, 0
+
+        def flush():
+            nonlocal fill, base
+            if fill:
+                self.wave[base:base + fill].copy_(torch.from_numpy(stage[:fill]))      # (pageable memory: the copy has ended when this returns)
+                base, fill = base + fill, 0
+
+        for i, f in enumerate(files):
+            y, rate = _wav.read_pcm16(f)
+            _check_clip(f, y.shape[0], rate)
+            if y.shape[0] != self.lengths[i]:
+                raise ValueError("%s: %d samples read, %d expected from its header when the epoch was planned" % (f, y.shape[0], self.lengths[i]))
+            if y.shape[0] > stage.shape[0] - fill:
+                flush()
+            if y.shape[0] > stage.shape[0]:
+                self.wave[base:base + y.shape[0]].copy_(torch.from_numpy(y))
+                base += y.shape[0]
+            else:
+                stage[fill:fill + y.shape[0]] = y
+                fill += y.shape[0]
+        flush()
+        assert base == total
+        self.label_table = None if labels is None else torch.from_numpy(labels).to(self.device)
+        self.n_classes = 0 if labels is None else int(labels.shape[1])
+
+    def __len__(self):
+        return len(self.files)
+
+    @property
+    def nbytes(self):
+        return int(self.wave.numel()) * 2 + (0 if self.label_table is None else int(self.label_table.numel()))
+
+    def plan(self, items, draws, window):
+        return plan_batch(self.wave, self.offsets, self.lengths, items, draws, window)
+
+    def label_rows(self, items_dev, N):
+        """float32 [N, n_classes]: the rows of the clips `items_dev` (device int64 [N], validated by the caller) -- one launch"""
+        if self.label_table is None:
+            raise ValueError("WaveStore: built without labels")
+        out = torch.empty(N, self.n_classes, dtype=torch.float32, device=self.device)
+        _lib.check(lib().m3t_label_rows(self.label_table.data_ptr(), len(self.files), self.n_classes, items_dev.data_ptr(), N,
+                                      out.data_ptr(), _stream()), "m3t_label_rows")
+        return out
+
+    def batch(self, items, draws=None, window=32, pad_mode="constant"):
+        """{'audio': float32 [N, window, 200], 'label': float32 [N, n_classes]} of the clips `items` with `draws` (None: the evaluation
+        draws), queued on the current stream.  Host validation, ONE table upload, the label launch, the ingest's launches."""
+        if pad_mode not in ("constant", "reflect"):
+            raise ValueError("pad_mode must be 'constant' or 'reflect'")
+        items, table, R = self.plan(items, draws, window)
+        N = int(items.shape[0])
+        tab = torch.from_numpy(np.concatenate([table.reshape(-1), items])).to(self.device, non_blocking=True)
+        out = {"audio": _audio.ingest_planned(self.wave, tab[:8 * N], N, R, window, pad_mode)}
+        if self.label_table is not None:
+            out["label"] = self.label_rows(tab[8 * N:], N)
+        return out
+
+
+# ---- the epoch plan -------------------------------------------------------------------------------------------------------------------
+class BatchPlan:
+    """One batch of an epoch.  items: the clips' indices into the scan's files, as the sampler gave them; aug: one m3t.audio.draw_audioset
+    dict per item; index: the batch's position in the epoch."""
+    __slots__ = ("items", "aug", "index")
+
+    def __init__(self, items, aug, index):
+        self.items, self.aug, self.index = items, aug, index
+
+    def __eq__(self, other):
+        return isinstance(other, BatchPlan) and self.items == other.items and self.index == other.index and self.aug == other.aug
+
+    def __repr__(self):
+        return "BatchPlan(index=%d, items=%r, aug=%r)" % (self.index, self.items, self.aug)
+
+
+class _Draws(Dataset):
+    """the data set the plan's DataLoader reads: item i is (i, draw), drawn when it is read"""
+
+    def __init__(self, lengths, window, training):
+        self.lengths, self.window, self.training = lengths, window, training
+
+    def __len__(self):
+        return len(self.lengths)
+
+    def __getitem__(self, i):
+        return int(i), _audio.draw_audioset(int(self.lengths[i]), self.window, self.training)
+
+
+class AudioSetFeed:
+    """An epoch of AudioSet batches from a Scan (scan_audioset), as the reference's DataLoader over its AudioSetDataset gives them.
+
+    window, batch_size, split: the reference's (`audioset_dataset.py:99`, `audioset_model.py:129-145`); split must be the scan's.  rank /
+    world: world > 1 shards the indices with torch's DistributedSampler in both splits (the reference's default one: shuffled, seed 0,
+    set_epoch(epoch)).  sampler: overrides the index order -- any iterable of indices, or a callable that makes one from the data set.
+    pad_mode: the STFT's padding, m3t.audio's ('constant' is librosa >= 0.10's).
+
+    Construction reads the clips' headers (Scan.lengths) and touches no device.  plan_epoch(epoch) is host only.  Iterating builds the
+    WaveStore on the current device at the first batch and yields, per BatchPlan, WaveStore.batch(items, draws): validated for the whole
+    batch before its first launch, queued on the current stream, nothing read back."""
+
+    def __init__(self, scan, window, batch_size, split, rank=0, world=1, sampler=None, pad_mode="constant"):
+        if scan.split != split:
+            raise ValueError("AudioSetFeed: split is %r, the folder was scanned for %r" % (split, scan.split))
+        self.scan, self.window, self.batch_size, self.split = scan, int(window), int(batch_size), split
+        self.rank, self.world, self.pad_mode = int(rank), int(world), pad_mode
+        if self.batch_size <= 0 or self.window <= 0:
+            raise ValueError("AudioSetFeed: batch_size and window must be positive")
+        if self.world <= 0 or not 0 <= self.rank < self.world:
+            raise ValueError("AudioSetFeed: rank %d outside a world of %d" % (self.rank, self.world))
+        if pad_mode not in ("constant", "reflect"):
+            raise ValueError("pad_mode must be 'constant' or 'reflect'")
+        if len(scan) == 0:
+            raise ValueError("AudioSetFeed: the scan of %s found no clip of split %r" % (scan.path, split))
+        self.training = split == "train"
+        self.files = list(scan.files)
+        self.lengths = scan.lengths()
+        self._draws = _Draws(self.lengths, self.window, self.training)
+        self._sampler = sampler(self._draws) if callable(sampler) else sampler
+        self._dist = None
+        if self._sampler is None and self.world > 1:
+            self._sampler = self._dist = DistributedSampler(self._draws, num_replicas=self.world, rank=self.rank)
+        self._loader = DataLoader(self._draws, batch_size=self.batch_size, shuffle=self.training and self._sampler is None,
+                                  sampler=self._sampler, num_workers=0, collate_fn=list)
+        self.epoch = 0
+        self.store = None
+
+    # ---- host ----
+    def __len__(self):
+        return len(self._loader)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def plans(self, epoch=None):
+        """the epoch's BatchPlans one at a time, each drawn when it is asked for (the reference's order with num_workers=0)"""
+        if epoch is not None:
+            self.set_epoch(epoch)
+        if self._dist is not None:
+            self._dist.set_epoch(self.epoch)
+        elif hasattr(self._sampler, "set_epoch"):
+            self._sampler.set_epoch(self.epoch)
+        for b, rows in enumerate(self._loader):
+            yield BatchPlan([i for i, _ in rows], [d for _, d in rows], b)
+
+    def plan_epoch(self, epoch=None):
+        """-> [BatchPlan] of one epoch (default: the current one); host only, no device is touched.  Consumes the epoch's random numbers."""
+        return list(self.plans(epoch))
+
+    def state_dict(self):
+        """what a resume between two epochs needs: the epoch and the states of `random`, `np.random` and torch's default generator"""
+        kind, keys, pos, has_gauss, gauss = np.random.get_state()
+        return {"epoch": self.epoch, "random": random.getstate(),
+                "numpy": (kind, np.array(keys, copy=True), int(pos), int(has_gauss), float(gauss)), "torch": torch.get_rng_state().clone()}
+
+    def load_state_dict(self, state):
+        self.epoch = int(state["epoch"])
+        random.setstate(state["random"])
+        np.random.set_state(tuple(state["numpy"]))
+        torch.set_rng_state(state["torch"])
+
+    # ---- device ----
+    def build_store(self):
+        """the WaveStore of the scan on the current device (once)"""
+        if self.store is None:
+            self.store = WaveStore(self.files, self.scan.labels, self.lengths)
+        return self
+
+    def batch(self, plan):
+        """one BatchPlan -> the batch dict, queued on the current stream"""
+        self.build_store()
+        return self.store.batch(plan.items, plan.aug, self.window, self.pad_mode)
+
+    def __iter__(self):
+        self.build_store()
+        for plan in self.plans():
+            yield self.batch(plan)
+
+
+def feed_from_hparams(hparams, split, rank=0, world=1):
+    """the feed of one split with the reference's arguments (`audioset_model.py:129-145`): dataset_path, window, batch_size"""
+    return AudioSetFeed(scan_audioset(hparams.dataset_path, split), hparams.window, hparams.batch_size, split, rank, world)

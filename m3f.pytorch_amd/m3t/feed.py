@@ -30,8 +30,8 @@ scans the windows (`dataset.py:202`) -- and forgets to when it reads the windows
 are the zeroed track whether or not a cache was read.
 
 Out of scope: prefetch threads and a second stream for the next batch (the persistent scans own the CUs: a concurrent decode stream is not
-added here), a host arena for a corpus larger than the device, a disk cache of the parsed frame store, the VoxCeleb2 (mp4) and AudioSet
-(wav) loaders, multi-GPU measurements (the sharding rule is tested on the host).
+added here), a host arena for a corpus larger than the device, a disk cache of the parsed frame store, the VoxCeleb2 (mp4) loader (the
+AudioSet one is m3t/audioset.py), multi-GPU measurements (the sharding rule is tested on the host).
 """
 import os
 import pickle

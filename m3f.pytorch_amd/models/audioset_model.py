@@ -10,8 +10,9 @@ pass); `train_acc` stays on the device (M3T_STEP_SYNC=1: a Python float).  The h
 m3t/checkpoints.py carries a trained checkpoint into AffWild2VA.  `batch['audio']` may be the audio as decoded -- 16 kHz PCM, int16 [N, S] or
 float32 [N, S], with the loader's draws in `batch['audio_aug']` (m3t.audio.draw_audioset) and the clips' lengths in `batch['audio_len']`:
 crop, spectrogram, power_to_db and the context stack of the reference's loader (audioset_dataset.py:58-87) then run on the device
-(m3t.audio.ingest) in front of the BiGRU; a float32 [N, T, 200] batch takes the reference's route.  Out of scope: decoding and the LR range
-finder.
+(m3t.audio.ingest) in front of the BiGRU; a float32 [N, T, 200] batch takes the reference's route.  train_dataloader / val_dataloader
+return the epoch feed of m3t/audioset.py (the clips of `--dataset_path` resident on the device, batches of {'audio', 'label'} as the
+reference's loader yields them); pretrain_audioset.py drives it.  Out of scope: the LR range finder.
 """
 from argparse import ArgumentParser
 
@@ -70,6 +71,20 @@ class AudioSet(_Base):
 
     def configure_optimizers(self):
         return _configure_optimizers(self, step_size_up=480)
+
+    # ------------------------------------------------------------------ data (audioset_model.py:129-145; m3t/audioset.py)
+    def _feed(self, split):
+        from m3t import audioset
+        rank, world = 0, 1
+        if getattr(self.hparams, 'distributed', False) and torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+        return audioset.feed_from_hparams(self.hparams, split, rank, world)
+
+    def train_dataloader(self):
+        return self._feed('train')
+
+    def val_dataloader(self):
+        return self._feed('val')
 
     @staticmethod
     def add_model_specific_args(parent_parser):
