@@ -8,11 +8,11 @@
 //   * apply / dx raise the magnitude slot of what they write (m3t_amax_out); the dx pass also leaves the column sums of dx -- under GroupNorm
 //     the bias gradient of the convolution in front is not zero by construction
 //   * GroupNorm + ReLU + k x k / stride k pooling as ONE operator (k = 2, 3): relu(gn(x)) at full resolution is neither written nor read
-#include "common.h"
+#include "cl_rows.h"
 
 namespace {
 
-constexpr int GN_TH = 256;
+constexpr int GN_TH = CL_TH;
 
 // the per-element map, shared by the plain and the fused kernels: the same bits in both
 __device__ __forceinline__ float gn_map(float x, float mu, float w, float b, int relu) {
@@ -38,6 +38,41 @@ __device__ __forceinline__ GNStat gn_load_stats(const float* __restrict__ mean, 
     return s;
 }
 
+// GroupNorm's per-thread channel constants (w = gamma rstd, b = beta, k1 = s1 / M, k2 = s2 / M of each element's group) with its formulas and
+// its clip: what the fused pooling bodies of csrc/cl_rows.h take as their norm, and what gncl_map_kernel sweeps with
+struct GNQuad {
+    typedef double acc_t;
+    GNStat st;
+    float w[4], b[4], k1[4], k2[4];
+    int n, T;                                               // the clip (the grid's y) and its frames
+    __device__ __forceinline__ void load_stats(const float* mean, const float* rstd, int clip, int G, int cpg, int q) {
+        n = clip;
+        st = gn_load_stats(mean, rstd, n, G, cpg, q);
+    }
+    __device__ __forceinline__ void load_fwd(const float* gamma, const float* beta, const float* mean, const float* rstd, int clip, int G, int cpg, int q) {
+        load_stats(mean, rstd, clip, G, cpg, q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * q + e;
+            w[e] = (gamma ? gamma[c] : 1.f) * st.is[e];
+            b[e] = beta ? beta[c] : 0.f;
+        }
+    }
+    __device__ __forceinline__ void load_bwd(const float* gamma, const float* mean, const float* rstd, const float* sums, int clip, int G, int cpg, int q) {
+        load_stats(mean, rstd, clip, G, cpg, q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * q + e, g = c / cpg;
+            w[e] = (gamma ? gamma[c] : 1.f) * st.is[e];
+            k1[e] = sums[((size_t)n * 2 + 0) * G + g];
+            k2[e] = sums[((size_t)n * 2 + 1) * G + g];
+        }
+    }
+    __device__ __forceinline__ float mask(float dP, float P) const { return gn_mask(dP, P); }
+    __device__ __forceinline__ float xhat(float x, int e) const { return (x - st.mu[e]) * st.is[e]; }
+    __device__ __forceinline__ float dx(float g, float x, int e) const { return gn_dx(g, x, st.mu[e], st.is[e], w[e], k1[e], k2[e]); }
+};
+
 // ---- statistics: partial[clip][chunk][2][C] doubles.  MODE 0: sum x, sum x^2 (both in fp64: a mean that is large against the spread must not
 // cost the variance its digits);  MODE 1 (backward): sum g, sum g xhat with g = dy (masked by y if relu)
 template <int MODE>
@@ -52,10 +87,8 @@ __global__ __launch_bounds__(GN_TH) void gncl_partial_kernel(const float* __rest
     const size_t r0 = (size_t)blockIdx.x * rows_per_chunk;
     const size_t r1 = r0 + rows_per_chunk < R ? r0 + rows_per_chunk : R;
     double s[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {0.0, 0.0, 0.0, 0.0};
-    GNStat st;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { st.mu[e] = 0.f; st.is[e] = 0.f; }
-    if (MODE == 1) st = gn_load_stats(mean, rstd, n, G, C / G, q);
+    GNQuad gn;
+    if (MODE == 1) gn.load_stats(mean, rstd, n, G, C / G, q);
     if (g < groups) {
         for (size_t rb = r0 + g; rb < r1; rb += (size_t)4 * groups) {      // four rows in flight per thread
             float4 av[4], xv4[4], yv4[4];
@@ -85,21 +118,13 @@ __global__ __launch_bounds__(GN_TH) void gncl_partial_kernel(const float* __rest
                         for (int e = 0; e < 4; ++e) ve[e] = gn_mask(ve[e], ye[e]);
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { s[e] += (double)ve[e]; t[e] += (double)(ve[e] * ((xe[e] - st.mu[e]) * st.is[e])); }
+                    for (int e = 0; e < 4; ++e) { s[e] += (double)ve[e]; t[e] += (double)(ve[e] * gn.xhat(xe[e], e)); }
                 }
             }
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { red[(size_t)g * C + 4 * q + e] = s[e]; red[(size_t)(groups + g) * C + 4 * q + e] = t[e]; }
+        cl_put_groups(red, g, q, groups, C, s, t);
     }
-    __syncthreads();
-    const size_t pb = ((size_t)n * gridDim.x + blockIdx.x) * 2;
-    for (int c = threadIdx.x; c < C; c += GN_TH) {
-        double a0 = 0.0, b0 = 0.0;
-        for (int k = 0; k < groups; ++k) { a0 += red[(size_t)k * C + c]; b0 += red[(size_t)(groups + k) * C + c]; }      // fixed order
-        partial[(pb + 0) * C + c] = a0;
-        partial[(pb + 1) * C + c] = b0;
-    }
+    cl_fold_groups(red, groups, C, partial, (size_t)n * gridDim.x + blockIdx.x);
 }
 
 // Fold a clip's chunks for the CB channels [c0, c0 + CB) of this block into ch[2][CB]: 64 channels at a time, the chunks in four interleaved
@@ -189,20 +214,6 @@ __global__ __launch_bounds__(GN_TH) void gncl_dparam_kernel(const double* __rest
     if (dgamma) dgamma[c] = (float)t;
 }
 
-// the dx pass's column sums: a thread's four channels are fixed, its sums run in fp64; block partial [C] in thread order
-__device__ __forceinline__ void gncl_block_colsum(const double (&cs)[4], double* csum, int C, double* __restrict__ colpart_row) {
-    const int c4n = C >> 2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) csum[threadIdx.x * 4 + e] = cs[e];
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += GN_TH) {
-        double t = 0.0;
-        for (int th = c >> 2; th < GN_TH; th += c4n) t += csum[th * 4 + (c & 3)];      // (a block starts at quad 0: C / 4 divides 256)
-        colpart_row[c] = t;
-    }
-    __syncthreads();
-}
-
 // out[c] = sum over the blocks' partials, in block order
 __global__ __launch_bounds__(256) void gncl_colsum_final_kernel(const double* __restrict__ colpart, int nblocks, int C, float* __restrict__ out) {
     __shared__ double red[4][64];
@@ -236,16 +247,9 @@ __global__ __launch_bounds__(GN_TH) void gncl_map_kernel(const float* __restrict
     const size_t i0 = (size_t)blockIdx.x * GN_TH + threadIdx.x;
     const int q = (int)(i0 % (size_t)c4n);
     const size_t base = (size_t)n * total4;
-    const GNStat st = gn_load_stats(mean, rstd, n, G, cpg, q);
-    float w[4], b[4], k1[4], k2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e, g = c / cpg;
-        w[e] = (gamma ? gamma[c] : 1.f) * st.is[e];
-        b[e] = (MODE == 0 && beta) ? beta[c] : 0.f;
-        k1[e] = MODE == 1 ? sums[((size_t)n * 2 + 0) * G + g] : 0.f;
-        k2[e] = MODE == 1 ? sums[((size_t)n * 2 + 1) * G + g] : 0.f;
-    }
+    GNQuad gn;
+    if (MODE == 0) gn.load_fwd(gamma, beta, mean, rstd, n, G, cpg, q);
+    else gn.load_bwd(gamma, mean, rstd, sums, n, G, cpg, q);
     float mx = 0.f;
     double cs[4] = {0.0, 0.0, 0.0, 0.0};
     for (size_t i = i0; i < total4; i += (size_t)gridDim.x * GN_TH) {
@@ -254,26 +258,33 @@ __global__ __launch_bounds__(GN_TH) void gncl_map_kernel(const float* __restrict
         float o[4];
         if (MODE == 0) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = gn_map(ve[e], st.mu[e], w[e], b[e], relu);
+            for (int e = 0; e < 4; ++e) o[e] = gn_map(ve[e], gn.st.mu[e], gn.w[e], gn.b[e], relu);
         } else {
             const float4 xv = reinterpret_cast<const float4*>(x)[base + i];
             const float xe[4] = {xv.x, xv.y, xv.z, xv.w};
             float ye[4] = {1.f, 1.f, 1.f, 1.f};
             if (relu) { const float4 yv = reinterpret_cast<const float4*>(y)[base + i]; ye[0] = yv.x; ye[1] = yv.y; ye[2] = yv.z; ye[3] = yv.w; }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = gn_dx(relu ? gn_mask(ve[e], ye[e]) : ve[e], xe[e], st.mu[e], st.is[e], w[e], k1[e], k2[e]);
+            for (int e = 0; e < 4; ++e) o[e] = gn.dx(relu ? gn_mask(ve[e], ye[e]) : ve[e], xe[e], e);
         }
         reinterpret_cast<float4*>(out)[base + i] = make_float4(o[0], o[1], o[2], o[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (slot) mx = cl_max4(mx, o);
         if (MODE == 1 && colpart) { cs[0] += (double)o[0]; cs[1] += (double)o[1]; cs[2] += (double)o[2]; cs[3] += (double)o[3]; }
     }
-    if (MODE == 1 && colpart) gncl_block_colsum(cs, csum, C, colpart + ((size_t)n * gridDim.x + blockIdx.x) * C);
+    if (MODE == 1 && colpart) cl_block_colsum(cs, csum, C, colpart + ((size_t)n * gridDim.x + blockIdx.x) * C);
     if (slot) m3t_block_raise_slot(slot, mx, red4);         // (uniform: every thread of the block gets here)
 }
 
-// ---- GroupNorm + ReLU + max pooling (k x k, stride k, no padding) as one operator over a clip's T frames [T][H][W][C]
+// ---- GroupNorm + ReLU + max pooling (k x k, stride k, no padding) as one operator over a clip's T frames [T][H][W][C]: the bodies of
+// csrc/cl_rows.h under GNQuad, the clip on the grid's y
 struct GNPool { int T, H, W, Ho, Wo, He, We, C, G; };      // He x We = ceil(H / k) x ceil(W / k): edge positions no window covers (odd H, W)
+static bool gnpool_geom(int T, int H, int W, int C, int G, int k, GNPool& g) {
+    if (T < 1 || H < 1 || W < 1 || (k != 2 && k != 3) || H < k || W < k) return false;
+    g.T = T; g.H = H; g.W = W; g.C = C; g.G = G; g.Ho = H / k; g.Wo = W / k; g.He = (H + k - 1) / k; g.We = (W + k - 1) / k;
+    return true;
+}
 
+// (own text beside bnpool_fwd_kernel's: shared through a function the K = 3 kernel runs 8-10 % longer, NOTEBOOK section 27)
 template <int K>
 __global__ __launch_bounds__(GN_TH) void gnpool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ yp,
@@ -317,7 +328,7 @@ __global__ __launch_bounds__(GN_TH) void gnpool_fwd_kernel(const float* __restri
         }
         reinterpret_cast<float4*>(yp)[obase + i] = make_float4(best[0], best[1], best[2], best[3]);
         reinterpret_cast<uchar4*>(win)[obase + i] = make_uchar4((unsigned char)bi[0], (unsigned char)bi[1], (unsigned char)bi[2], (unsigned char)bi[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(best[0]), m3t_fin_abs(best[1]))), fmaxf(m3t_fin_abs(best[2]), m3t_fin_abs(best[3])));
+        if (slot) mx = cl_max4(mx, best);
     }
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
@@ -328,47 +339,11 @@ __global__ __launch_bounds__(GN_TH) void gnpool_bwd_partial_kernel(const float* 
                                                                    const unsigned char* __restrict__ win, const float* __restrict__ mean,
                                                                    const float* __restrict__ rstd, size_t nwin, GNPool g, size_t win_per_chunk,
                                                                    double* __restrict__ partial) {
-    extern __shared__ double red[];
-    const int C = g.C, c4n = C >> 2, groups = GN_TH / c4n, n = blockIdx.y;
-    const int q = threadIdx.x % c4n, gi = threadIdx.x / c4n;
-    const size_t r0 = (size_t)blockIdx.x * win_per_chunk;
-    const size_t r1 = r0 + win_per_chunk < nwin ? r0 + win_per_chunk : nwin;
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {0.0, 0.0, 0.0, 0.0};
-    const GNStat st = gn_load_stats(mean, rstd, n, g.G, C / g.G, q);
-    const size_t p0 = (size_t)n * g.T;
-    if (gi < groups) {
-        for (size_t r = r0 + gi; r < r1; r += groups) {
-            size_t rr = r;
-            const int wo = (int)(rr % (size_t)g.Wo); rr /= (size_t)g.Wo;
-            const int ho = (int)(rr % (size_t)g.Ho);
-            const size_t p = p0 + rr / (size_t)g.Ho;
-            const size_t o = ((size_t)n * nwin + r) * (size_t)c4n + q;
-            const float4 d = reinterpret_cast<const float4*>(dyp)[o];
-            const float4 pv = reinterpret_cast<const float4*>(yp)[o];
-            const uchar4 wb = reinterpret_cast<const uchar4*>(win)[o];
-            const float de[4] = {d.x, d.y, d.z, d.w}, pe[4] = {pv.x, pv.y, pv.z, pv.w};
-            const int we[4] = {wb.x, wb.y, wb.z, wb.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float gq = gn_mask(de[e], pe[e]);
-                const int wi = we[e] < K * K ? we[e] : 0;                      // (a byte this library did not write must not index outside the window)
-                const int dh = wi / K, dw = wi - dh * K;
-                const float xv = x[((p * g.H + (size_t)(ho * K + dh)) * g.W + (size_t)(wo * K + dw)) * (size_t)C + 4 * q + e];
-                s[e] += (double)gq;
-                t[e] += (double)(gq * ((xv - st.mu[e]) * st.is[e]));
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { red[(size_t)gi * C + 4 * q + e] = s[e]; red[(size_t)(groups + gi) * C + 4 * q + e] = t[e]; }
-    }
-    __syncthreads();
-    const size_t pb = ((size_t)n * gridDim.x + blockIdx.x) * 2;
-    for (int c = threadIdx.x; c < C; c += GN_TH) {
-        double a0 = 0.0, b0 = 0.0;
-        for (int k = 0; k < groups; ++k) { a0 += red[(size_t)k * C + c]; b0 += red[(size_t)(groups + k) * C + c]; }
-        partial[(pb + 0) * C + c] = a0;
-        partial[(pb + 1) * C + c] = b0;
-    }
+    const int c4n = g.C >> 2, q = threadIdx.x % c4n, gi = threadIdx.x / c4n;
+    GNQuad gn;
+    gn.load_stats(mean, rstd, blockIdx.y, g.G, g.C / g.G, q);
+    gn.T = g.T;
+    cl_normpool_bwd_partial<K>(dyp, x, yp, win, nwin, g, win_per_chunk, partial, gn, q, gi);
 }
 
 // dx at full resolution: a thread = one (extended) window x four channels; positions outside the pooled grid (odd H / W) have g = 0
@@ -378,61 +353,11 @@ __global__ __launch_bounds__(GN_TH) void gnpool_bwd_dx_kernel(const float* __res
                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
                                                               const float* __restrict__ sums, float* __restrict__ dx, size_t total4, GNPool g,
                                                               unsigned long long* __restrict__ slot, double* __restrict__ colpart) {
-    __shared__ float red4[4];
-    __shared__ double csum[GN_TH * 4];
-    const int C = g.C, c4n = C >> 2, cpg = C / g.G, n = blockIdx.y;
-    const size_t i0 = (size_t)blockIdx.x * GN_TH + threadIdx.x;
-    const int q = (int)(i0 % (size_t)c4n);
-    const GNStat st = gn_load_stats(mean, rstd, n, g.G, cpg, q);
-    float w[4], k1[4], k2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e, gr = c / cpg;
-        w[e] = (gamma ? gamma[c] : 1.f) * st.is[e];
-        k1[e] = sums[((size_t)n * 2 + 0) * g.G + gr];
-        k2[e] = sums[((size_t)n * 2 + 1) * g.G + gr];
-    }
-    const size_t p0 = (size_t)n * g.T;
-    float mx = 0.f;
-    double cs[4] = {0.0, 0.0, 0.0, 0.0};
-    for (size_t i = i0; i < total4; i += (size_t)gridDim.x * GN_TH) {
-        size_t r = i / (size_t)c4n;
-        const int we_ = (int)(r % (size_t)g.We); r /= (size_t)g.We;
-        const int he = (int)(r % (size_t)g.He);
-        const size_t p = p0 + r / (size_t)g.He;
-        const bool pooled = he < g.Ho && we_ < g.Wo;
-        float de[4] = {0.f, 0.f, 0.f, 0.f};
-        int wi[4] = {-1, -1, -1, -1};
-        if (pooled) {
-            const size_t o = ((p * g.Ho + he) * g.Wo + we_) * (size_t)c4n + q;
-            const float4 d = reinterpret_cast<const float4*>(dyp)[o];
-            const float4 pv = reinterpret_cast<const float4*>(yp)[o];
-            const uchar4 wb = reinterpret_cast<const uchar4*>(win)[o];
-            de[0] = gn_mask(d.x, pv.x); de[1] = gn_mask(d.y, pv.y); de[2] = gn_mask(d.z, pv.z); de[3] = gn_mask(d.w, pv.w);
-            wi[0] = wb.x; wi[1] = wb.y; wi[2] = wb.z; wi[3] = wb.w;
-        }
-#pragma unroll
-        for (int dh = 0; dh < K; ++dh) {
-            const int h = he * K + dh;
-            if (h >= g.H) continue;
-#pragma unroll
-            for (int dw = 0; dw < K; ++dw) {
-                const int ww = we_ * K + dw;
-                if (ww >= g.W) continue;
-                const size_t xo = ((p * g.H + h) * g.W + ww) * (size_t)C + 4 * q;
-                const float4 xv = *reinterpret_cast<const float4*>(x + xo);
-                const float xe[4] = {xv.x, xv.y, xv.z, xv.w};
-                float o[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = gn_dx((wi[e] == dh * K + dw) ? de[e] : 0.f, xe[e], st.mu[e], st.is[e], w[e], k1[e], k2[e]);
-                *reinterpret_cast<float4*>(dx + xo) = make_float4(o[0], o[1], o[2], o[3]);
-                if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
-                if (colpart) { cs[0] += (double)o[0]; cs[1] += (double)o[1]; cs[2] += (double)o[2]; cs[3] += (double)o[3]; }
-            }
-        }
-    }
-    if (colpart) gncl_block_colsum(cs, csum, C, colpart + ((size_t)n * gridDim.x + blockIdx.x) * C);
-    if (slot) m3t_block_raise_slot(slot, mx, red4);
+    const int q = (int)(((size_t)blockIdx.x * GN_TH + threadIdx.x) % (size_t)(g.C >> 2));
+    GNQuad gn;
+    gn.load_bwd(gamma, mean, rstd, sums, blockIdx.y, g.G, g.C / g.G, q);
+    gn.T = g.T;
+    cl_normpool_bwd_dx<K>(dyp, x, yp, win, dx, total4, g, slot, colpart, gn, q);
 }
 
 // chunks / blocks per clip: about 256 rows a chunk and 16 float4 a thread, at most ~1024 chunks and ~2048 blocks over all clips
@@ -449,7 +374,6 @@ static int gn_cb(int C, int G) { const int cpg = C / G; return C < 64 ? C : (cpg
 static bool gncl_shape_ok(int N, size_t R, int C, int G) {
     return C > 0 && C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && G > 0 && C % G == 0 && N >= 1 && N <= 65535 && R >= 1;
 }
-static bool al16(const void* p) { return p && ((uintptr_t)p % 16) == 0; }
 
 // workspace: fp64 chunk partials [N][chunks][2][C] | chansum [N][2][C] fp64 | sums [N][2][G <= C] | the dx pass's block partials [N][blocks][C] fp64
 struct GNWs { double* partial; double* chansum; float* sums; double* colpart; size_t bytes; };
@@ -501,7 +425,7 @@ extern "C" int m3t_gn_cl_fwd(const float* x, int N, size_t R, int C, int G, cons
     unsigned long long* slot = m3t_take_amax_out();
     if (!gncl_shape_ok(N, R, C, G) || !al16(x) || !al16(y) || !save_mean || !save_rstd) return M3T_EINVAL;
     const GNWs w = gn_ws(ws, N, R, C);
-    if (!ws || ws_bytes < w.bytes || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    if (!cl_ws_ok(ws, ws_bytes, w.bytes)) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int rc = gn_stats(x, N, R, C, G, eps, save_mean, save_rstd, w, s);
     if (rc) return rc;
@@ -519,7 +443,7 @@ extern "C" int m3t_gn_cl_bwd(const float* dy, const float* x, const float* y, co
     if (!gncl_shape_ok(N, R, C, G) || !al16(dy) || !al16(x) || !al16(dx) || !save_mean || !save_rstd) return M3T_EINVAL;
     if (relu && !al16(y)) return M3T_EINVAL;
     const GNWs w = gn_ws(ws, N, R, C);
-    if (!ws || ws_bytes < w.bytes || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    if (!cl_ws_ok(ws, ws_bytes, w.bytes)) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int cpc = gn_chunks_per_clip(N, R), groups = GN_TH / (C / 4), CB = gn_cb(C, G);
     const size_t rpc = (R + cpc - 1) / cpc;
@@ -542,16 +466,15 @@ extern "C" int m3t_gn_cl_bwd(const float* dy, const float* x, const float* y, co
 extern "C" int m3t_gn_pool_cl_fwd(const float* x, int N, int T, int H, int W, int C, int G, int k, const float* gamma, const float* beta, float eps,
                                   float* yp, unsigned char* win, float* save_mean, float* save_rstd, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (T < 1 || H < 1 || W < 1 || (k != 2 && k != 3) || H < k || W < k) return M3T_EINVAL;
+    GNPool g;
+    if (!gnpool_geom(T, H, W, C, G, k, g)) return M3T_EINVAL;
     const size_t R = (size_t)T * H * W;
-    if (!gncl_shape_ok(N, R, C, G) || !al16(x) || !al16(yp) || !win || ((uintptr_t)win % 4) != 0 || !save_mean || !save_rstd) return M3T_EINVAL;
+    if (!gncl_shape_ok(N, R, C, G) || !al16(x) || !al16(yp) || !al4(win) || !save_mean || !save_rstd) return M3T_EINVAL;
     const GNWs w = gn_ws(ws, N, R, C);
-    if (!ws || ws_bytes < w.bytes || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    if (!cl_ws_ok(ws, ws_bytes, w.bytes)) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int rc = gn_stats(x, N, R, C, G, eps, save_mean, save_rstd, w, s);
     if (rc) return rc;
-    GNPool g;
-    g.T = T; g.H = H; g.W = W; g.C = C; g.G = G; g.Ho = H / k; g.Wo = W / k; g.He = (H + k - 1) / k; g.We = (W + k - 1) / k;
     const size_t total4 = (size_t)T * g.Ho * g.Wo * (size_t)(C / 4);
     const dim3 grid(gn_blocks_per_clip(N, total4), N);
     if (k == 2) gnpool_fwd_kernel<2><<<grid, GN_TH, 0, s>>>(x, gamma, beta, save_mean, save_rstd, yp, win, total4, g, slot);
@@ -564,15 +487,14 @@ extern "C" int m3t_gn_pool_cl_bwd(const float* dyp, const float* x, const float*
                                   const float* save_mean, const float* save_rstd, int N, int T, int H, int W, int C, int G, int k, float* dx,
                                   float* dgamma, float* dbeta, float* dx_colsum, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (T < 1 || H < 1 || W < 1 || (k != 2 && k != 3) || H < k || W < k) return M3T_EINVAL;
+    GNPool g;
+    if (!gnpool_geom(T, H, W, C, G, k, g)) return M3T_EINVAL;
     const size_t R = (size_t)T * H * W;
-    if (!gncl_shape_ok(N, R, C, G) || !al16(dyp) || !al16(x) || !al16(yp) || !al16(dx) || !win || ((uintptr_t)win % 4) != 0 || !save_mean || !save_rstd)
+    if (!gncl_shape_ok(N, R, C, G) || !al16(dyp) || !al16(x) || !al16(yp) || !al16(dx) || !al4(win) || !save_mean || !save_rstd)
         return M3T_EINVAL;
     const GNWs w = gn_ws(ws, N, R, C);
-    if (!ws || ws_bytes < w.bytes || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    if (!cl_ws_ok(ws, ws_bytes, w.bytes)) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    GNPool g;
-    g.T = T; g.H = H; g.W = W; g.C = C; g.G = G; g.Ho = H / k; g.Wo = W / k; g.He = (H + k - 1) / k; g.We = (W + k - 1) / k;
     const size_t nwin = (size_t)T * g.Ho * g.Wo;
     const int cpc = gn_chunks_per_clip(N, nwin), groups = GN_TH / (C / 4), CB = gn_cb(C, G);      // (<= the chunks of R rows: ws covers them)
     const size_t wpc = (nwin + cpc - 1) / cpc;

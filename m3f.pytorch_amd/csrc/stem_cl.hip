@@ -9,11 +9,12 @@
 //   * max pooling of frames [P][H][W][C] with a (kh, kw) window: a thread = one output position x four channels; the winner's place inside its
 //     window is kept as a byte per element, backward is a gather over the windows that cover an input position (no atomics), as the plane
 //     kernels; ties / NaN as torch (first maximum in window order, NaN wins)
-#include "common.h"
+#include "cl_rows.h"
 
 namespace {
 
-constexpr int CL_TH = 256;
+// the ReLU's gradient mask under BatchNorm: dy where y > 0 (a NaN y stops it; gn_cl.hip's gn_mask lets it through)
+__device__ __forceinline__ float bn_mask(float dy, float y) { return y > 0.f ? dy : 0.f; }
 
 // ---- statistics: partial[chunk][2][C] doubles.  MODE 0: sum x, sum x^2;  MODE 1 (backward): sum g, sum g xhat with g = dy (y > 0 if relu)
 template <int MODE>
@@ -26,11 +27,8 @@ __global__ __launch_bounds__(CL_TH) void bncl_partial_kernel(const float* __rest
     const size_t r0 = (size_t)blockIdx.x * rows_per_chunk;
     const size_t r1 = r0 + rows_per_chunk < M ? r0 + rows_per_chunk : M;
     double s[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {0.0, 0.0, 0.0, 0.0};
-    float mu[4] = {0.f, 0.f, 0.f, 0.f}, is[4] = {0.f, 0.f, 0.f, 0.f};
-    if (MODE == 1) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { mu[e] = mean[4 * q + e]; is[e] = invstd[4 * q + e]; }
-    }
+    BNQuad bn;
+    if (MODE == 1) bn.load_stats(mean, invstd, q);
     if (g < groups) {
         // four rows in flight per thread (the loads of all four issued before the first is used); their sum in fp32, the running sums in fp64
         for (size_t rb = r0 + g; rb < r1; rb += (size_t)4 * groups) {
@@ -62,22 +60,15 @@ __global__ __launch_bounds__(CL_TH) void bncl_partial_kernel(const float* __rest
                         for (int e = 0; e < 4; ++e) if (!(ye[e] > 0.f)) ve[e] = 0.f;
                     }
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { fs[e] += ve[e]; ft[e] = fmaf(ve[e], (xe[e] - mu[e]) * is[e], ft[e]); }
+                    for (int e = 0; e < 4; ++e) { fs[e] += ve[e]; ft[e] = fmaf(ve[e], bn.xhat(xe[e], e), ft[e]); }
                 }
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) { s[e] += (double)fs[e]; t[e] += (double)ft[e]; }
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { red[(size_t)g * C + 4 * q + e] = s[e]; red[(size_t)(groups + g) * C + 4 * q + e] = t[e]; }
+        cl_put_groups(red, g, q, groups, C, s, t);
     }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += CL_TH) {
-        double a0 = 0.0, b0 = 0.0;
-        for (int k = 0; k < groups; ++k) { a0 += red[(size_t)k * C + c]; b0 += red[(size_t)(groups + k) * C + c]; }      // fixed order
-        partial[((size_t)blockIdx.x * 2 + 0) * C + c] = a0;
-        partial[((size_t)blockIdx.x * 2 + 1) * C + c] = b0;
-    }
+    cl_fold_groups(red, groups, C, partial, blockIdx.x);
 }
 
 // mean / biased variance -> invstd; running statistics as torch (unbiased variance)
@@ -157,16 +148,9 @@ __global__ __launch_bounds__(CL_TH) void bncl_map_kernel(const float* __restrict
     const int c4n = C >> 2;
     const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
     const int q = (int)(i0 % (size_t)c4n);
-    float w[4], b[4], mu[4], is[4], k1[4], k2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        mu[e] = mean[c]; is[e] = invstd[c];
-        w[e] = (gamma ? gamma[c] : 1.f) * is[e];
-        b[e] = (MODE == 0 && beta) ? beta[c] : 0.f;
-        k1[e] = (MODE == 1 && training) ? sums[c] * inv_count : 0.f;
-        k2[e] = (MODE == 1 && training) ? sums[C + c] * inv_count : 0.f;
-    }
+    BNQuad bn;
+    if (MODE == 0) bn.load_fwd(gamma, beta, mean, invstd, q);
+    else bn.load_bwd(gamma, mean, invstd, sums, C, inv_count, training, q);
     float mx = 0.f;
     float cs[4] = {0.f, 0.f, 0.f, 0.f};                      // MODE 1 + colpart: this thread's sums of dx over its rows (its four channels are fixed)
     for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
@@ -176,7 +160,7 @@ __global__ __launch_bounds__(CL_TH) void bncl_map_kernel(const float* __restrict
         if (MODE == 0) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float r = (ve[e] - mu[e]) * w[e] + b[e];
+                const float r = bn.map(ve[e], e);
                 o[e] = relu ? m3t_relu(r) : r;
             }
         } else {
@@ -187,27 +171,14 @@ __global__ __launch_bounds__(CL_TH) void bncl_map_kernel(const float* __restrict
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float g = (relu && !(ye[e] > 0.f)) ? 0.f : ve[e];
-                o[e] = training ? w[e] * (g - k1[e] - ((xe[e] - mu[e]) * is[e]) * k2[e]) : g * w[e];
+                o[e] = bn.dx(g, xe[e], e, training);
             }
         }
         reinterpret_cast<float4*>(out)[i] = make_float4(o[0], o[1], o[2], o[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (slot) mx = cl_max4(mx, o);
         if (MODE == 1 && colpart) { cs[0] += o[0]; cs[1] += o[1]; cs[2] += o[2]; cs[3] += o[3]; }
     }
-    if (MODE == 1 && colpart) {
-        // block partial [C]: the 256 / (C / 4) threads that share a channel quad, in thread order (deterministic); colpart [blocks][C]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) csum[threadIdx.x * 4 + e] = cs[e];
-        __syncthreads();
-        for (int c = threadIdx.x; c < C; c += CL_TH) {
-            float t = 0.f;
-            const int base = (int)((size_t)blockIdx.x * CL_TH % (size_t)c4n);      // quad of this block's thread 0
-            const int first = ((c >> 2) - base + c4n) % c4n;                        // first thread of the block that holds quad c / 4
-            for (int th = first; th < CL_TH; th += c4n) t += csum[th * 4 + (c & 3)];
-            colpart[(size_t)blockIdx.x * C + c] = t;
-        }
-        __syncthreads();
-    }
+    if (MODE == 1 && colpart) cl_block_colsum(cs, csum, C, colpart + (size_t)blockIdx.x * C);      // colpart [blocks][C]
     if (slot) m3t_block_raise_slot(slot, mx, red4);         // (uniform: every thread of the block gets here)
 }
 
@@ -246,10 +217,9 @@ __global__ __launch_bounds__(CL_TH) void poolcl_fwd_kernel(const float* __restri
     float mx = 0.f;
     for (size_t i = (size_t)blockIdx.x * CL_TH + threadIdx.x; i < total4; i += (size_t)gridDim.x * CL_TH) {
         const int q = (int)(i % (size_t)c4n);
-        size_t r = i / (size_t)c4n;
-        const int wo = (int)(r % (size_t)g.Wo); r /= (size_t)g.Wo;
-        const int ho = (int)(r % (size_t)g.Ho);
-        const size_t p = r / (size_t)g.Ho;
+        int ho, wo;
+        size_t p;
+        cl_decode(i / (size_t)c4n, g.Ho, g.Wo, p, ho, wo);
         float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         int bi[4] = {0, 0, 0, 0};
         bool first = true;
@@ -269,7 +239,7 @@ __global__ __launch_bounds__(CL_TH) void poolcl_fwd_kernel(const float* __restri
         }
         reinterpret_cast<float4*>(y)[i] = make_float4(best[0], best[1], best[2], best[3]);
         reinterpret_cast<uchar4*>(win)[i] = make_uchar4((unsigned char)bi[0], (unsigned char)bi[1], (unsigned char)bi[2], (unsigned char)bi[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(best[0]), m3t_fin_abs(best[1]))), fmaxf(m3t_fin_abs(best[2]), m3t_fin_abs(best[3])));
+        if (slot) mx = cl_max4(mx, best);
     }
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
@@ -280,10 +250,9 @@ __global__ __launch_bounds__(CL_TH) void poolcl_bwd_kernel(const float* __restri
     const int c4n = g.C >> 2;
     for (size_t i = (size_t)blockIdx.x * CL_TH + threadIdx.x; i < total4; i += (size_t)gridDim.x * CL_TH) {
         const int q = (int)(i % (size_t)c4n);
-        size_t r = i / (size_t)c4n;
-        const int w = (int)(r % (size_t)g.W); r /= (size_t)g.W;
-        const int h = (int)(r % (size_t)g.H);
-        const size_t p = r / (size_t)g.H;
+        int h, w;
+        size_t p;
+        cl_decode(i / (size_t)c4n, g.H, g.W, p, h, w);
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         // windows with ho sh - ph <= h < ho sh - ph + kh
         const int ho_hi = min((h + g.ph) / g.sh, g.Ho - 1), wo_hi = min((w + g.pw) / g.sw, g.Wo - 1);
@@ -312,8 +281,21 @@ __global__ __launch_bounds__(CL_TH) void poolcl_bwd_kernel(const float* __restri
 // the pooled value and the winner byte; in backward an input position's gradient through the pooling is dP of its window if it won, else 0 --
 // computed in the BatchNorm backward's two sweeps, no scatter pass, and the ReLU mask is P > 0 of the window (the winner's y IS P).  Per pooled
 // group: 2.3 instead of 4.9 passes over the convolution's output.
+// The three kernels are the bodies of csrc/cl_rows.h under BatchNorm's quad.
 struct PoolF { int H, W, Ho, Wo, He, We, k, C; };           // He x We = ceil(H / k) x ceil(W / k): edge positions no window covers (odd H, W)
 
+struct BNPoolQuad {
+    typedef float acc_t;
+    static constexpr int n = 0, T = 0;                      // no clips under BatchNorm: one run of P frames
+    BNQuad bn;
+    int training;
+    __device__ __forceinline__ float mask(float dP, float P) const { return bn_mask(dP, P); }
+    __device__ __forceinline__ float xhat(float x, int e) const { return bn.xhat(x, e); }
+    __device__ __forceinline__ float dx(float g, float x, int e) const { return bn.dx(g, x, e, training); }
+};
+
+// (own text, not a body of cl_rows.h shared with gnpool_fwd_kernel: through any function around the window loop the K = 3 kernel takes 71
+// VGPRs for 57 and its forward runs 8-10 % longer, NOTEBOOK section 27)
 template <int K>
 __global__ __launch_bounds__(CL_TH) void bnpool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ yp,
@@ -323,20 +305,13 @@ __global__ __launch_bounds__(CL_TH) void bnpool_fwd_kernel(const float* __restri
     const int c4n = g.C >> 2;
     const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
     const int q = (int)(i0 % (size_t)c4n);
-    float w[4], b[4], mu[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        mu[e] = mean[c];
-        w[e] = (gamma ? gamma[c] : 1.f) * invstd[c];
-        b[e] = beta ? beta[c] : 0.f;
-    }
+    BNQuad bn;
+    bn.load_fwd(gamma, beta, mean, invstd, q);
     float mx = 0.f;
     for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
-        size_t r = i / (size_t)c4n;
-        const int wo = (int)(r % (size_t)g.Wo); r /= (size_t)g.Wo;
-        const int ho = (int)(r % (size_t)g.Ho);
-        const size_t p = r / (size_t)g.Ho;
+        int ho, wo;
+        size_t p;
+        cl_decode(i / (size_t)c4n, g.Ho, g.Wo, p, ho, wo);
         float4 v[K * K];
 #pragma unroll
         for (int dh = 0; dh < K; ++dh)
@@ -350,13 +325,13 @@ __global__ __launch_bounds__(CL_TH) void bnpool_fwd_kernel(const float* __restri
             const float ve[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float y = m3t_relu((ve[e] - mu[e]) * w[e] + b[e]);          // (NaN stays NaN, as torch.relu; the pooling lets it win)
+                const float y = m3t_relu(bn.map(ve[e], e));                     // (NaN stays NaN, as torch.relu; the pooling lets it win)
                 if (t == 0 || m3t_nan_gt(y, best[e])) { best[e] = y; bi[e] = t; }
             }
         }
         reinterpret_cast<float4*>(yp)[i] = make_float4(best[0], best[1], best[2], best[3]);
         reinterpret_cast<uchar4*>(win)[i] = make_uchar4((unsigned char)bi[0], (unsigned char)bi[1], (unsigned char)bi[2], (unsigned char)bi[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(best[0]), m3t_fin_abs(best[1]))), fmaxf(m3t_fin_abs(best[2]), m3t_fin_abs(best[3])));
+        if (slot) mx = cl_max4(mx, best);
     }
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
@@ -367,46 +342,10 @@ __global__ __launch_bounds__(CL_TH) void bnpool_bwd_partial_kernel(const float* 
                                                                    const unsigned char* __restrict__ win, const float* __restrict__ mean,
                                                                    const float* __restrict__ invstd, size_t nwin, PoolF g, size_t win_per_chunk,
                                                                    double* __restrict__ partial) {
-    extern __shared__ double red[];
-    const int C = g.C, c4n = C >> 2, groups = CL_TH / c4n;
-    const int q = threadIdx.x % c4n, gi = threadIdx.x / c4n;
-    const size_t r0 = (size_t)blockIdx.x * win_per_chunk;
-    const size_t r1 = r0 + win_per_chunk < nwin ? r0 + win_per_chunk : nwin;
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {0.0, 0.0, 0.0, 0.0};
-    float mu[4], is[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { mu[e] = mean[4 * q + e]; is[e] = invstd[4 * q + e]; }
-    if (gi < groups) {
-        for (size_t r = r0 + gi; r < r1; r += groups) {
-            size_t rr = r;
-            const int wo = (int)(rr % (size_t)g.Wo); rr /= (size_t)g.Wo;
-            const int ho = (int)(rr % (size_t)g.Ho);
-            const size_t p = rr / (size_t)g.Ho;
-            const size_t o = r * (size_t)c4n + q;
-            const float4 d = reinterpret_cast<const float4*>(dyp)[o];
-            const float4 pv = reinterpret_cast<const float4*>(yp)[o];
-            const uchar4 wb = reinterpret_cast<const uchar4*>(win)[o];
-            const float de[4] = {d.x, d.y, d.z, d.w}, pe[4] = {pv.x, pv.y, pv.z, pv.w};
-            const int we[4] = {wb.x, wb.y, wb.z, wb.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float gq = pe[e] > 0.f ? de[e] : 0.f;
-                const int dh = we[e] / K, dw = we[e] - dh * K;
-                const float xv = x[((p * g.H + (size_t)(ho * K + dh)) * g.W + (size_t)(wo * K + dw)) * (size_t)C + 4 * q + e];
-                s[e] += (double)gq;
-                t[e] += (double)(gq * ((xv - mu[e]) * is[e]));
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { red[(size_t)gi * C + 4 * q + e] = s[e]; red[(size_t)(groups + gi) * C + 4 * q + e] = t[e]; }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += CL_TH) {
-        double a0 = 0.0, b0 = 0.0;
-        for (int k = 0; k < groups; ++k) { a0 += red[(size_t)k * C + c]; b0 += red[(size_t)(groups + k) * C + c]; }
-        partial[((size_t)blockIdx.x * 2 + 0) * C + c] = a0;
-        partial[((size_t)blockIdx.x * 2 + 1) * C + c] = b0;
-    }
+    const int c4n = g.C >> 2, q = threadIdx.x % c4n, gi = threadIdx.x / c4n;
+    BNPoolQuad nm;
+    nm.bn.load_stats(mean, invstd, q);
+    cl_normpool_bwd_partial<K>(dyp, x, yp, win, nwin, g, win_per_chunk, partial, nm, q, gi);
 }
 
 // dx at full resolution: a thread = one (extended) window x four channels; positions outside the pooled grid (odd H / W) have g = 0
@@ -417,72 +356,11 @@ __global__ __launch_bounds__(CL_TH) void bnpool_bwd_dx_kernel(const float* __res
                                                               const float* __restrict__ sums, float* __restrict__ dx, size_t total4, PoolF g,
                                                               float inv_count, int training, unsigned long long* __restrict__ slot,
                                                               float* __restrict__ colpart) {
-    __shared__ float red4[4];
-    __shared__ float csum[CL_TH * 4];
-    const int C = g.C, c4n = C >> 2;
-    const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
-    const int q = (int)(i0 % (size_t)c4n);
-    float w[4], mu[4], is[4], k1[4], k2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        mu[e] = mean[c]; is[e] = invstd[c];
-        w[e] = (gamma ? gamma[c] : 1.f) * is[e];
-        k1[e] = training ? sums[c] * inv_count : 0.f;
-        k2[e] = training ? sums[C + c] * inv_count : 0.f;
-    }
-    float mx = 0.f, cs[4] = {0.f, 0.f, 0.f, 0.f};
-    for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
-        size_t r = i / (size_t)c4n;
-        const int we_ = (int)(r % (size_t)g.We); r /= (size_t)g.We;
-        const int he = (int)(r % (size_t)g.He);
-        const size_t p = r / (size_t)g.He;
-        const bool pooled = he < g.Ho && we_ < g.Wo;
-        float de[4] = {0.f, 0.f, 0.f, 0.f};
-        int wi[4] = {-1, -1, -1, -1};
-        if (pooled) {
-            const size_t o = ((p * g.Ho + he) * g.Wo + we_) * (size_t)c4n + q;
-            const float4 d = reinterpret_cast<const float4*>(dyp)[o];
-            const float4 pv = reinterpret_cast<const float4*>(yp)[o];
-            const uchar4 wb = reinterpret_cast<const uchar4*>(win)[o];
-            de[0] = pv.x > 0.f ? d.x : 0.f; de[1] = pv.y > 0.f ? d.y : 0.f; de[2] = pv.z > 0.f ? d.z : 0.f; de[3] = pv.w > 0.f ? d.w : 0.f;
-            wi[0] = wb.x; wi[1] = wb.y; wi[2] = wb.z; wi[3] = wb.w;
-        }
-#pragma unroll
-        for (int dh = 0; dh < K; ++dh) {
-            const int h = he * K + dh;
-            if (h >= g.H) continue;
-#pragma unroll
-            for (int dw = 0; dw < K; ++dw) {
-                const int ww = we_ * K + dw;
-                if (ww >= g.W) continue;
-                const size_t xo = ((p * g.H + h) * g.W + ww) * (size_t)C + 4 * q;
-                const float4 xv = *reinterpret_cast<const float4*>(x + xo);
-                const float xe[4] = {xv.x, xv.y, xv.z, xv.w};
-                float o[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float gq = (wi[e] == dh * K + dw) ? de[e] : 0.f;
-                    o[e] = training ? w[e] * (gq - k1[e] - ((xe[e] - mu[e]) * is[e]) * k2[e]) : gq * w[e];
-                }
-                *reinterpret_cast<float4*>(dx + xo) = make_float4(o[0], o[1], o[2], o[3]);
-                if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
-                if (colpart) { cs[0] += o[0]; cs[1] += o[1]; cs[2] += o[2]; cs[3] += o[3]; }
-            }
-        }
-    }
-    if (colpart) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) csum[threadIdx.x * 4 + e] = cs[e];
-        __syncthreads();
-        for (int c = threadIdx.x; c < C; c += CL_TH) {
-            float t = 0.f;
-            for (int th = c >> 2; th < CL_TH; th += c4n) t += csum[th * 4 + (c & 3)];
-            colpart[(size_t)blockIdx.x * C + c] = t;
-        }
-        __syncthreads();
-    }
-    if (slot) m3t_block_raise_slot(slot, mx, red4);
+    const int q = (int)(((size_t)blockIdx.x * CL_TH + threadIdx.x) % (size_t)(g.C >> 2));
+    BNPoolQuad nm;
+    nm.bn.load_bwd(gamma, mean, invstd, sums, g.C, inv_count, training, q);
+    nm.training = training;
+    cl_normpool_bwd_dx<K>(dyp, x, yp, win, dx, total4, g, slot, colpart, nm, q);
 }
 
 static int grid_for(size_t total4, int c4n) {
@@ -493,6 +371,10 @@ static int grid_for(size_t total4, int c4n) {
     (void)c4n;
     return (int)b;
 }
+
+// (the v2 seam's statistics pass, defined with its operator below: bn_stats launches it)
+__global__ __launch_bounds__(CL_TH) void abr_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ sum,
+                                                            size_t M, int C, size_t rows_per_chunk, double* __restrict__ partial);
 
 }  // namespace
 
@@ -506,28 +388,78 @@ extern "C" size_t m3t_bn_cl_ws_bytes(size_t M, int C) {
 
 static bool bncl_shape_ok(size_t M, int C) { return C > 0 && C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && M > 0; }
 
+// ---- what the BatchNorm entry points share on the host
+static size_t bn_fold_lds(int C) { return (size_t)2 * (CL_TH / (C / 4)) * C * sizeof(double); }      // red [2][groups][C] of a partial kernel
+
+// The statistics of a forward entry point into save_mean / save_invstd.  Training: chunk partials of x [M][C] (b given: of the sum x + b, which
+// the pass writes to `sum` -- the v2 seam) -> mean, inv-std and the running update; eval: from the running statistics.
+static int bn_stats(const float* x, const float* b, float* sum, size_t M, int C, float* run_mean, float* run_var, float momentum, float eps,
+                    int training, float* save_mean, float* save_invstd, float* ws, size_t ws_bytes, hipStream_t s) {
+    if (!training) {
+        if (!run_mean || !run_var) return M3T_EINVAL;
+        bncl_eval_stats_kernel<<<cdiv(C, 256), 256, 0, s>>>(run_mean, run_var, C, eps, save_mean, save_invstd);
+        M3T_LAUNCH_CHECK();
+        return 0;
+    }
+    if (M < 2 || !cl_ws_ok(ws, ws_bytes, m3t_bn_cl_ws_bytes(M, C))) return M3T_EINVAL;
+    const int nch = cl_chunks(M);
+    const size_t rpc = (M + nch - 1) / nch;
+    double* partial = reinterpret_cast<double*>(ws);
+    if (b) abr_partial_kernel<<<nch, CL_TH, bn_fold_lds(C), s>>>(x, b, sum, M, C, rpc, partial);
+    else bncl_partial_kernel<0><<<nch, CL_TH, bn_fold_lds(C), s>>>(x, nullptr, nullptr, nullptr, nullptr, M, C, rpc, 0, partial);
+    M3T_LAUNCH_CHECK();
+    bncl_stats_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, (double)M, C, eps, momentum, run_mean, run_var, save_mean, save_invstd);
+    M3T_LAUNCH_CHECK();
+    return 0;
+}
+
+// The backward chain over ws = fp64 chunk partials | sums [2 C] | block partials of the dx pass: the caller's partial launch over `nrows` rows
+// (or pooled windows) in chunks -> bncl_bwd_final_kernel (sums, dgamma, dbeta) -> the caller's dx launch over total4 quads -> dx_colsum
+// (optional: the column sums of dx = the bias gradient of the convolution in front, block partials summed in block order).
+//   partial_pass(nch, rows_per_chunk, partial)     dx_pass(nblk, sums, colpart)
+template <class PARTIAL, class DX>
+static int bn_bwd_chain(size_t nrows, size_t M, int C, size_t total4, float* dgamma, float* dbeta, float* dx_colsum, float* ws, size_t ws_bytes,
+                        hipStream_t s, PARTIAL partial_pass, DX dx_pass) {
+    if (!cl_ws_ok(ws, ws_bytes, m3t_bn_cl_ws_bytes(M, C))) return M3T_EINVAL;
+    const int nch = cl_chunks(nrows);
+    double* partial = reinterpret_cast<double*>(ws);
+    float* sums = reinterpret_cast<float*>(partial + (size_t)cl_chunks(M) * 2 * C);
+    partial_pass(nch, (nrows + nch - 1) / nch, partial);
+    M3T_LAUNCH_CHECK();
+    bncl_bwd_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, C, sums, dgamma, dbeta);
+    M3T_LAUNCH_CHECK();
+    const int nblk = grid_for(total4, C / 4);
+    float* colpart = dx_colsum ? sums + 2 * (size_t)C + 64 : nullptr;
+    dx_pass(nblk, sums, colpart);
+    M3T_LAUNCH_CHECK();
+    if (dx_colsum) {
+        bncl_colsum_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(colpart, nblk, C, dx_colsum);
+        M3T_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+static bool poolcl_geom(int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw, PoolCL& g) {
+    if (H <= 0 || W <= 0 || C <= 0 || C % 4 != 0 || kh <= 0 || kw <= 0 || kh * kw > 255 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0 || ph >= kh || pw >= kw)
+        return false;
+    g.H = H; g.W = W; g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.ph = ph; g.pw = pw; g.C = C;
+    g.Ho = (H + 2 * ph - kh) / sh + 1; g.Wo = (W + 2 * pw - kw) / sw + 1;
+    return g.Ho >= 1 && g.Wo >= 1;
+}
+static bool poolf_geom(int H, int W, int C, int k, PoolF& g) {
+    if ((k != 2 && k != 3) || H < k || W < k) return false;
+    g.H = H; g.W = W; g.k = k; g.C = C; g.Ho = H / k; g.Wo = W / k; g.He = (H + k - 1) / k; g.We = (W + k - 1) / k;
+    return true;
+}
+
 extern "C" int m3t_bn_cl_fwd(const float* x, size_t M, int C, const float* gamma, const float* beta, float* run_mean, float* run_var,
                              float momentum, float eps, int training, int relu, float* y, float* save_mean, float* save_invstd, float* ws,
                              size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!bncl_shape_ok(M, C) || !x || !y || !save_mean || !save_invstd || ((uintptr_t)x % 16) != 0 || ((uintptr_t)y % 16) != 0) return M3T_EINVAL;
-    if (!training && (!run_mean || !run_var)) return M3T_EINVAL;
+    if (!bncl_shape_ok(M, C) || !al16(x) || !al16(y) || !save_mean || !save_invstd) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (training) {
-        if (M < 2) return M3T_EINVAL;
-        if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
-        const int nch = cl_chunks(M);
-        const size_t rpc = (M + nch - 1) / nch;
-        double* partial = reinterpret_cast<double*>(ws);
-        const int groups = CL_TH / (C / 4);
-        bncl_partial_kernel<0><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(x, nullptr, nullptr, nullptr, nullptr, M, C, rpc, 0, partial);
-        M3T_LAUNCH_CHECK();
-        bncl_stats_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, (double)M, C, eps, momentum, run_mean, run_var, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
-    } else {
-        bncl_eval_stats_kernel<<<cdiv(C, 256), 256, 0, s>>>(run_mean, run_var, C, eps, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
-    }
+    const int rc = bn_stats(x, nullptr, nullptr, M, C, run_mean, run_var, momentum, eps, training, save_mean, save_invstd, ws, ws_bytes, s);
+    if (rc) return rc;
     const size_t total4 = M * (size_t)(C / 4);
     bncl_map_kernel<0><<<grid_for(total4, C / 4), CL_TH, 0, s>>>(x, nullptr, nullptr, gamma, beta, save_mean, save_invstd, nullptr, y, total4, C, 0.f,
                                                                 training, relu, slot, nullptr);
@@ -539,34 +471,19 @@ extern "C" int m3t_bn_cl_bwd(const float* dy, const float* x, const float* y, co
                              size_t M, int C, int training, int relu, float* dx, float* dgamma, float* dbeta, float* dx_colsum, float* ws,
                              size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!bncl_shape_ok(M, C) || !dy || !x || !dx || !save_mean || !save_invstd || ((uintptr_t)dy % 16) != 0 || ((uintptr_t)x % 16) != 0 ||
-        ((uintptr_t)dx % 16) != 0)
-        return M3T_EINVAL;
-    if (relu && (!y || ((uintptr_t)y % 16) != 0)) return M3T_EINVAL;
-    if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    if (!bncl_shape_ok(M, C) || !al16(dy) || !al16(x) || !al16(dx) || !save_mean || !save_invstd) return M3T_EINVAL;
+    if (relu && !al16(y)) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int nch = cl_chunks(M);
-    const size_t rpc = (M + nch - 1) / nch;
-    double* partial = reinterpret_cast<double*>(ws);
-    float* sums = reinterpret_cast<float*>(partial + (size_t)nch * 2 * C);
-    const int groups = CL_TH / (C / 4);
-    bncl_partial_kernel<1><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(dy, x, y, save_mean, save_invstd, M, C, rpc, relu, partial);
-    M3T_LAUNCH_CHECK();
-    bncl_bwd_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, C, sums, dgamma, dbeta);
-    M3T_LAUNCH_CHECK();
     const size_t total4 = M * (size_t)(C / 4);
-    // dx_colsum [C] (optional): the column sums of dx = the bias gradient of the convolution in front of this BatchNorm, from the same pass
-    // (block partials behind the fp64 partials in ws, summed in block order)
-    const int nblk = grid_for(total4, C / 4);
-    float* colpart = dx_colsum ? sums + 2 * (size_t)C + 64 : nullptr;
-    bncl_map_kernel<1><<<nblk, CL_TH, 0, s>>>(dy, x, y, gamma, nullptr, save_mean, save_invstd, sums, dx, total4, C, (float)(1.0 / (double)M),
-                                             training, relu, slot, colpart);
-    M3T_LAUNCH_CHECK();
-    if (dx_colsum) {
-        bncl_colsum_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(colpart, nblk, C, dx_colsum);
-        M3T_LAUNCH_CHECK();
-    }
-    return 0;
+    return bn_bwd_chain(
+        M, M, C, total4, dgamma, dbeta, dx_colsum, ws, ws_bytes, s,
+        [&](int nch, size_t rpc, double* partial) {
+            bncl_partial_kernel<1><<<nch, CL_TH, bn_fold_lds(C), s>>>(dy, x, y, save_mean, save_invstd, M, C, rpc, relu, partial);
+        },
+        [&](int nblk, const float* sums, float* colpart) {
+            bncl_map_kernel<1><<<nblk, CL_TH, 0, s>>>(dy, x, y, gamma, nullptr, save_mean, save_invstd, sums, dx, total4, C, (float)(1.0 / (double)M),
+                                                     training, relu, slot, colpart);
+        });
 }
 
 // Max pooling of P channels-last frames x [P][H][W][C] -> y [P][Ho][Wo][C] (nn.MaxPool3d((1, kh, kw)) of the stems on channels-last rows);
@@ -575,13 +492,8 @@ extern "C" int m3t_pool_cl_fwd(const float* x, size_t P, int H, int W, int C, in
                                unsigned char* win, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
     if (P == 0) return 0;
-    if (!x || !y || !win || H <= 0 || W <= 0 || C <= 0 || C % 4 != 0 || kh <= 0 || kw <= 0 || kh * kw > 255 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0 ||
-        ph >= kh || pw >= kw || ((uintptr_t)x % 16) != 0 || ((uintptr_t)y % 16) != 0 || ((uintptr_t)win % 4) != 0)
-        return M3T_EINVAL;
     PoolCL g;
-    g.H = H; g.W = W; g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.ph = ph; g.pw = pw; g.C = C;
-    g.Ho = (H + 2 * ph - kh) / sh + 1; g.Wo = (W + 2 * pw - kw) / sw + 1;
-    if (g.Ho < 1 || g.Wo < 1) return M3T_EINVAL;
+    if (!al16(x) || !al16(y) || !al4(win) || !poolcl_geom(H, W, C, kh, kw, sh, sw, ph, pw, g)) return M3T_EINVAL;
     const size_t total4 = P * (size_t)g.Ho * g.Wo * (size_t)(C / 4);
     poolcl_fwd_kernel<<<grid_for(total4, C / 4), CL_TH, 0, (hipStream_t)stream>>>(x, y, win, total4, g, slot);
     M3T_LAUNCH_CHECK();
@@ -591,13 +503,8 @@ extern "C" int m3t_pool_cl_fwd(const float* x, size_t P, int H, int W, int C, in
 extern "C" int m3t_pool_cl_bwd(const float* dy, const unsigned char* win, size_t P, int H, int W, int C, int kh, int kw, int sh, int sw, int ph,
                                int pw, float* dx, void* stream) {
     if (P == 0) return 0;
-    if (!dy || !dx || !win || H <= 0 || W <= 0 || C <= 0 || C % 4 != 0 || kh <= 0 || kw <= 0 || kh * kw > 255 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0 ||
-        ph >= kh || pw >= kw || ((uintptr_t)dy % 16) != 0 || ((uintptr_t)dx % 16) != 0 || ((uintptr_t)win % 4) != 0)
-        return M3T_EINVAL;
     PoolCL g;
-    g.H = H; g.W = W; g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.ph = ph; g.pw = pw; g.C = C;
-    g.Ho = (H + 2 * ph - kh) / sh + 1; g.Wo = (W + 2 * pw - kw) / sw + 1;
-    if (g.Ho < 1 || g.Wo < 1) return M3T_EINVAL;
+    if (!al16(dy) || !al16(dx) || !al4(win) || !poolcl_geom(H, W, C, kh, kw, sh, sw, ph, pw, g)) return M3T_EINVAL;
     const size_t total4 = P * (size_t)H * W * (size_t)(C / 4);
     poolcl_bwd_kernel<<<grid_for(total4, C / 4), CL_TH, 0, (hipStream_t)stream>>>(dy, win, dx, total4, g);
     M3T_LAUNCH_CHECK();
@@ -612,28 +519,11 @@ extern "C" int m3t_bn_pool_cl_fwd(const float* x, size_t P, int H, int W, int C,
                                   float* save_invstd, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
     const size_t M = P * (size_t)H * W;
-    if (!bncl_shape_ok(M, C) || (k != 2 && k != 3) || H < k || W < k || !x || !yp || !win || !save_mean || !save_invstd || ((uintptr_t)x % 16) != 0 ||
-        ((uintptr_t)yp % 16) != 0 || ((uintptr_t)win % 4) != 0)
-        return M3T_EINVAL;
-    if (!training && (!run_mean || !run_var)) return M3T_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (training) {
-        if (M < 2) return M3T_EINVAL;
-        if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
-        const int nch = cl_chunks(M);
-        const size_t rpc = (M + nch - 1) / nch;
-        double* partial = reinterpret_cast<double*>(ws);
-        const int groups = CL_TH / (C / 4);
-        bncl_partial_kernel<0><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(x, nullptr, nullptr, nullptr, nullptr, M, C, rpc, 0, partial);
-        M3T_LAUNCH_CHECK();
-        bncl_stats_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, (double)M, C, eps, momentum, run_mean, run_var, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
-    } else {
-        bncl_eval_stats_kernel<<<cdiv(C, 256), 256, 0, s>>>(run_mean, run_var, C, eps, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
-    }
     PoolF g;
-    g.H = H; g.W = W; g.k = k; g.C = C; g.Ho = H / k; g.Wo = W / k; g.He = (H + k - 1) / k; g.We = (W + k - 1) / k;
+    if (!bncl_shape_ok(M, C) || !poolf_geom(H, W, C, k, g) || !al16(x) || !al16(yp) || !al4(win) || !save_mean || !save_invstd) return M3T_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = bn_stats(x, nullptr, nullptr, M, C, run_mean, run_var, momentum, eps, training, save_mean, save_invstd, ws, ws_bytes, s);
+    if (rc) return rc;
     const size_t total4 = P * (size_t)g.Ho * g.Wo * (size_t)(C / 4);
     if (k == 2) bnpool_fwd_kernel<2><<<grid_for(total4, C / 4), CL_TH, 0, s>>>(x, gamma, beta, save_mean, save_invstd, yp, win, total4, g, slot);
     else bnpool_fwd_kernel<3><<<grid_for(total4, C / 4), CL_TH, 0, s>>>(x, gamma, beta, save_mean, save_invstd, yp, win, total4, g, slot);
@@ -646,35 +536,22 @@ extern "C" int m3t_bn_pool_cl_bwd(const float* dyp, const float* x, const float*
                                   float* dgamma, float* dbeta, float* dx_colsum, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
     const size_t M = P * (size_t)H * W;
-    if (!bncl_shape_ok(M, C) || (k != 2 && k != 3) || H < k || W < k || !dyp || !x || !yp || !win || !dx || !save_mean || !save_invstd ||
-        ((uintptr_t)dyp % 16) != 0 || ((uintptr_t)x % 16) != 0 || ((uintptr_t)yp % 16) != 0 || ((uintptr_t)dx % 16) != 0 || ((uintptr_t)win % 4) != 0)
-        return M3T_EINVAL;
-    if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
     PoolF g;
-    g.H = H; g.W = W; g.k = k; g.C = C; g.Ho = H / k; g.Wo = W / k; g.He = (H + k - 1) / k; g.We = (W + k - 1) / k;
-    const size_t nwin = P * (size_t)g.Ho * g.Wo;
-    const int nch = cl_chunks(nwin);
-    const size_t wpc = (nwin + nch - 1) / nch;
-    double* partial = reinterpret_cast<double*>(ws);
-    float* sums = reinterpret_cast<float*>(partial + (size_t)cl_chunks(M) * 2 * C);
-    const int groups = CL_TH / (C / 4);
-    if (k == 2) bnpool_bwd_partial_kernel<2><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(dyp, x, yp, win, save_mean, save_invstd, nwin, g, wpc, partial);
-    else bnpool_bwd_partial_kernel<3><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(dyp, x, yp, win, save_mean, save_invstd, nwin, g, wpc, partial);
-    M3T_LAUNCH_CHECK();
-    bncl_bwd_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, C, sums, dgamma, dbeta);
-    M3T_LAUNCH_CHECK();
-    const size_t total4 = P * (size_t)g.He * g.We * (size_t)(C / 4);
-    const int nblk = grid_for(total4, C / 4);
-    float* colpart = dx_colsum ? sums + 2 * (size_t)C + 64 : nullptr;
-    if (k == 2) bnpool_bwd_dx_kernel<2><<<nblk, CL_TH, 0, s>>>(dyp, x, yp, win, gamma, save_mean, save_invstd, sums, dx, total4, g, (float)(1.0 / (double)M), training, slot, colpart);
-    else bnpool_bwd_dx_kernel<3><<<nblk, CL_TH, 0, s>>>(dyp, x, yp, win, gamma, save_mean, save_invstd, sums, dx, total4, g, (float)(1.0 / (double)M), training, slot, colpart);
-    M3T_LAUNCH_CHECK();
-    if (dx_colsum) {
-        bncl_colsum_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(colpart, nblk, C, dx_colsum);
-        M3T_LAUNCH_CHECK();
-    }
-    return 0;
+    if (!bncl_shape_ok(M, C) || !poolf_geom(H, W, C, k, g) || !al16(dyp) || !al16(x) || !al16(yp) || !al16(dx) || !al4(win) || !save_mean || !save_invstd)
+        return M3T_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nwin = P * (size_t)g.Ho * g.Wo, total4 = P * (size_t)g.He * g.We * (size_t)(C / 4);
+    const float inv_count = (float)(1.0 / (double)M);
+    return bn_bwd_chain(
+        nwin, M, C, total4, dgamma, dbeta, dx_colsum, ws, ws_bytes, s,
+        [&](int nch, size_t wpc, double* partial) {
+            if (k == 2) bnpool_bwd_partial_kernel<2><<<nch, CL_TH, bn_fold_lds(C), s>>>(dyp, x, yp, win, save_mean, save_invstd, nwin, g, wpc, partial);
+            else bnpool_bwd_partial_kernel<3><<<nch, CL_TH, bn_fold_lds(C), s>>>(dyp, x, yp, win, save_mean, save_invstd, nwin, g, wpc, partial);
+        },
+        [&](int nblk, const float* sums, float* colpart) {
+            if (k == 2) bnpool_bwd_dx_kernel<2><<<nblk, CL_TH, 0, s>>>(dyp, x, yp, win, gamma, save_mean, save_invstd, sums, dx, total4, g, inv_count, training, slot, colpart);
+            else bnpool_bwd_dx_kernel<3><<<nblk, CL_TH, 0, s>>>(dyp, x, yp, win, gamma, save_mean, save_invstd, sums, dx, total4, g, inv_count, training, slot, colpart);
+        });
 }
 
 // ---- the per-frame ResNet (v1) on the chain: the two operators that close a residual block and close the trunk.  Reference models/resnet.py
@@ -690,14 +567,8 @@ __global__ __launch_bounds__(CL_TH) void bnar_fwd_kernel(const float* __restrict
     const int c4n = C >> 2;
     const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
     const int q = (int)(i0 % (size_t)c4n);
-    float w[4], b[4], mu[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        mu[e] = mean[c];
-        w[e] = (gamma ? gamma[c] : 1.f) * invstd[c];
-        b[e] = beta ? beta[c] : 0.f;
-    }
+    BNQuad bn;
+    bn.load_fwd(gamma, beta, mean, invstd, q);
     float mx = 0.f;
     for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
         const float4 v = reinterpret_cast<const float4*>(x)[i];
@@ -705,9 +576,9 @@ __global__ __launch_bounds__(CL_TH) void bnar_fwd_kernel(const float* __restrict
         const float ve[4] = {v.x, v.y, v.z, v.w}, se[4] = {s.x, s.y, s.z, s.w};
         float o[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = m3t_relu(((ve[e] - mu[e]) * w[e] + b[e]) + se[e]);      // (gamma = 0, beta = 0: relu(shortcut), bit for bit)
+        for (int e = 0; e < 4; ++e) o[e] = m3t_relu(bn.map(ve[e], e) + se[e]);      // (gamma = 0, beta = 0: relu(shortcut), bit for bit)
         reinterpret_cast<float4*>(y)[i] = make_float4(o[0], o[1], o[2], o[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (slot) mx = cl_max4(mx, o);
     }
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
@@ -723,15 +594,8 @@ __global__ __launch_bounds__(CL_TH) void bnar_bwd_kernel(const float* __restrict
     const int c4n = C >> 2;
     const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
     const int q = (int)(i0 % (size_t)c4n);
-    float w[4], mu[4], is[4], k1[4], k2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        mu[e] = mean[c]; is[e] = invstd[c];
-        w[e] = (gamma ? gamma[c] : 1.f) * is[e];
-        k1[e] = training ? sums[c] * inv_count : 0.f;
-        k2[e] = training ? sums[C + c] * inv_count : 0.f;
-    }
+    BNQuad bn;
+    bn.load_bwd(gamma, mean, invstd, sums, C, inv_count, training, q);
     float mx = 0.f;
     float cs[4] = {0.f, 0.f, 0.f, 0.f};
     for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
@@ -742,28 +606,15 @@ __global__ __launch_bounds__(CL_TH) void bnar_bwd_kernel(const float* __restrict
         float o[4], g[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            g[e] = (ye[e] > 0.f) ? de[e] : 0.f;
-            o[e] = training ? w[e] * (g[e] - k1[e] - ((xe[e] - mu[e]) * is[e]) * k2[e]) : g[e] * w[e];
+            g[e] = bn_mask(de[e], ye[e]);
+            o[e] = bn.dx(g[e], xe[e], e, training);
         }
         reinterpret_cast<float4*>(dx)[i] = make_float4(o[0], o[1], o[2], o[3]);
         reinterpret_cast<float4*>(ds)[i] = make_float4(g[0], g[1], g[2], g[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (slot) mx = cl_max4(mx, o);
         if (colpart) { cs[0] += o[0]; cs[1] += o[1]; cs[2] += o[2]; cs[3] += o[3]; }
     }
-    if (colpart) {
-        // block partial [C]: the 256 / (C / 4) threads that share a channel quad, in thread order (deterministic); colpart [blocks][C]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) csum[threadIdx.x * 4 + e] = cs[e];
-        __syncthreads();
-        for (int c = threadIdx.x; c < C; c += CL_TH) {
-            float t = 0.f;
-            const int base = (int)((size_t)blockIdx.x * CL_TH % (size_t)c4n);
-            const int first = ((c >> 2) - base + c4n) % c4n;
-            for (int th = first; th < CL_TH; th += c4n) t += csum[th * 4 + (c & 3)];
-            colpart[(size_t)blockIdx.x * C + c] = t;
-        }
-        __syncthreads();
-    }
+    if (colpart) cl_block_colsum(cs, csum, C, colpart + (size_t)blockIdx.x * C);
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
 
@@ -805,26 +656,10 @@ extern "C" int m3t_bn_add_relu_cl_fwd(const float* x, const float* shortcut, siz
                                       float* run_var, float momentum, float eps, int training, float* y, float* save_mean, float* save_invstd,
                                       float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!bncl_shape_ok(M, C) || !x || !shortcut || !y || !save_mean || !save_invstd || ((uintptr_t)x % 16) != 0 || ((uintptr_t)shortcut % 16) != 0 ||
-        ((uintptr_t)y % 16) != 0)
-        return M3T_EINVAL;
-    if (!training && (!run_mean || !run_var)) return M3T_EINVAL;
+    if (!bncl_shape_ok(M, C) || !al16(x) || !al16(shortcut) || !al16(y) || !save_mean || !save_invstd) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (training) {
-        if (M < 2) return M3T_EINVAL;
-        if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
-        const int nch = cl_chunks(M);
-        const size_t rpc = (M + nch - 1) / nch;
-        double* partial = reinterpret_cast<double*>(ws);
-        const int groups = CL_TH / (C / 4);
-        bncl_partial_kernel<0><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(x, nullptr, nullptr, nullptr, nullptr, M, C, rpc, 0, partial);
-        M3T_LAUNCH_CHECK();
-        bncl_stats_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, (double)M, C, eps, momentum, run_mean, run_var, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
-    } else {
-        bncl_eval_stats_kernel<<<cdiv(C, 256), 256, 0, s>>>(run_mean, run_var, C, eps, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
-    }
+    const int rc = bn_stats(x, nullptr, nullptr, M, C, run_mean, run_var, momentum, eps, training, save_mean, save_invstd, ws, ws_bytes, s);
+    if (rc) return rc;
     const size_t total4 = M * (size_t)(C / 4);
     bnar_fwd_kernel<<<grid_for(total4, C / 4), CL_TH, 0, s>>>(x, shortcut, gamma, beta, save_mean, save_invstd, y, total4, C, slot);
     M3T_LAUNCH_CHECK();
@@ -837,36 +672,23 @@ extern "C" int m3t_bn_add_relu_cl_bwd(const float* dy, const float* x, const flo
                                       const float* save_invstd, size_t M, int C, int training, float* dx, float* ds, float* dgamma, float* dbeta,
                                       float* dx_colsum, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!bncl_shape_ok(M, C) || !dy || !x || !y || !dx || !ds || !save_mean || !save_invstd || ((uintptr_t)dy % 16) != 0 || ((uintptr_t)x % 16) != 0 ||
-        ((uintptr_t)y % 16) != 0 || ((uintptr_t)dx % 16) != 0 || ((uintptr_t)ds % 16) != 0)
-        return M3T_EINVAL;
-    if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    if (!bncl_shape_ok(M, C) || !al16(dy) || !al16(x) || !al16(y) || !al16(dx) || !al16(ds) || !save_mean || !save_invstd) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int nch = cl_chunks(M);
-    const size_t rpc = (M + nch - 1) / nch;
-    double* partial = reinterpret_cast<double*>(ws);
-    float* sums = reinterpret_cast<float*>(partial + (size_t)nch * 2 * C);
-    const int groups = CL_TH / (C / 4);
-    bncl_partial_kernel<1><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), s>>>(dy, x, y, save_mean, save_invstd, M, C, rpc, 1, partial);
-    M3T_LAUNCH_CHECK();
-    bncl_bwd_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(partial, nch, C, sums, dgamma, dbeta);
-    M3T_LAUNCH_CHECK();
     const size_t total4 = M * (size_t)(C / 4);
-    const int nblk = grid_for(total4, C / 4);
-    float* colpart = dx_colsum ? sums + 2 * (size_t)C + 64 : nullptr;
-    bnar_bwd_kernel<<<nblk, CL_TH, 0, s>>>(dy, x, y, gamma, save_mean, save_invstd, sums, dx, ds, total4, C, (float)(1.0 / (double)M), training, slot,
-                                           colpart);
-    M3T_LAUNCH_CHECK();
-    if (dx_colsum) {
-        bncl_colsum_final_kernel<<<cdiv(C, 64), 256, 0, s>>>(colpart, nblk, C, dx_colsum);
-        M3T_LAUNCH_CHECK();
-    }
-    return 0;
+    return bn_bwd_chain(
+        M, M, C, total4, dgamma, dbeta, dx_colsum, ws, ws_bytes, s,
+        [&](int nch, size_t rpc, double* partial) {
+            bncl_partial_kernel<1><<<nch, CL_TH, bn_fold_lds(C), s>>>(dy, x, y, save_mean, save_invstd, M, C, rpc, 1, partial);
+        },
+        [&](int nblk, const float* sums, float* colpart) {
+            bnar_bwd_kernel<<<nblk, CL_TH, 0, s>>>(dy, x, y, gamma, save_mean, save_invstd, sums, dx, ds, total4, C, (float)(1.0 / (double)M), training,
+                                                   slot, colpart);
+        });
 }
 
 // AdaptiveAvgPool2d(1) + flatten over P channels-last frames x [P][HW][C] -> y [P][C]; C % 4 == 0, 16-B aligned tensors.
 extern "C" int m3t_mean_cl_fwd(const float* x, size_t P, int HW, int C, float* y, void* stream) {
-    if (!x || !y || P == 0 || HW <= 0 || C <= 0 || C % 4 != 0 || ((uintptr_t)x % 16) != 0 || ((uintptr_t)y % 16) != 0) return M3T_EINVAL;
+    if (!al16(x) || !al16(y) || P == 0 || HW <= 0 || C <= 0 || C % 4 != 0) return M3T_EINVAL;
     const size_t total4 = P * (size_t)(C / 4);
     size_t b = (total4 + CL_TH - 1) / CL_TH;
     if (b > 2048) b = 2048;
@@ -876,7 +698,7 @@ extern "C" int m3t_mean_cl_fwd(const float* x, size_t P, int HW, int C, float* y
 }
 
 extern "C" int m3t_mean_cl_bwd(const float* dy, size_t P, int HW, int C, float* dx, void* stream) {
-    if (!dy || !dx || P == 0 || HW <= 0 || C <= 0 || C % 4 != 0 || ((uintptr_t)dy % 16) != 0 || ((uintptr_t)dx % 16) != 0) return M3T_EINVAL;
+    if (!al16(dy) || !al16(dx) || P == 0 || HW <= 0 || C <= 0 || C % 4 != 0) return M3T_EINVAL;
     const size_t total4 = P * (size_t)HW * (size_t)(C / 4);
     meancl_bwd_kernel<<<grid_for(total4, C / 4), CL_TH, 0, (hipStream_t)stream>>>(dy, dx, total4, HW, C);
     M3T_LAUNCH_CHECK();
@@ -922,16 +744,9 @@ __global__ __launch_bounds__(CL_TH) void abr_partial_kernel(const float* __restr
 #pragma unroll
             for (int e = 0; e < 4; ++e) { s[e] += (double)fs[e]; t[e] += (double)ft[e]; }
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { red[(size_t)g * C + 4 * q + e] = s[e]; red[(size_t)(groups + g) * C + 4 * q + e] = t[e]; }
+        cl_put_groups(red, g, q, groups, C, s, t);
     }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += CL_TH) {
-        double a0 = 0.0, b0 = 0.0;
-        for (int k = 0; k < groups; ++k) { a0 += red[(size_t)k * C + c]; b0 += red[(size_t)(groups + k) * C + c]; }      // fixed order
-        partial[((size_t)blockIdx.x * 2 + 0) * C + c] = a0;
-        partial[((size_t)blockIdx.x * 2 + 1) * C + c] = b0;
-    }
+    cl_fold_groups(red, groups, C, partial, blockIdx.x);
 }
 
 // eval mode: s = a + b (written unless sum is null), z = relu(bn(s)) with bncl_map_kernel<0>'s formula: one sweep
@@ -943,14 +758,8 @@ __global__ __launch_bounds__(CL_TH) void abr_eval_kernel(const float* __restrict
     const int c4n = C >> 2;
     const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
     const int q = (int)(i0 % (size_t)c4n);
-    float w[4], b[4], mu[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        mu[e] = mean[c];
-        w[e] = (gamma ? gamma[c] : 1.f) * invstd[c];
-        b[e] = beta ? beta[c] : 0.f;
-    }
+    BNQuad bn;
+    bn.load_fwd(gamma, beta, mean, invstd, q);
     float mx = 0.f;
     for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
         const float4 v = reinterpret_cast<const float4*>(a)[i];
@@ -958,10 +767,10 @@ __global__ __launch_bounds__(CL_TH) void abr_eval_kernel(const float* __restrict
         const float ve[4] = {v.x + u.x, v.y + u.y, v.z + u.z, v.w + u.w};
         float o[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = m3t_relu((ve[e] - mu[e]) * w[e] + b[e]);
+        for (int e = 0; e < 4; ++e) o[e] = m3t_relu(bn.map(ve[e], e));
         if (sum) reinterpret_cast<float4*>(sum)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
         reinterpret_cast<float4*>(z)[i] = make_float4(o[0], o[1], o[2], o[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (slot) mx = cl_max4(mx, o);
     }
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
@@ -978,15 +787,8 @@ __global__ __launch_bounds__(CL_TH) void abr_bwd_kernel(const float* __restrict_
     const int c4n = C >> 2;
     const size_t i0 = (size_t)blockIdx.x * CL_TH + threadIdx.x;
     const int q = (int)(i0 % (size_t)c4n);
-    float w[4], mu[4], is[4], k1[4], k2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        mu[e] = mean[c]; is[e] = invstd[c];
-        w[e] = (gamma ? gamma[c] : 1.f) * is[e];
-        k1[e] = training ? sums[c] * inv_count : 0.f;
-        k2[e] = training ? sums[C + c] * inv_count : 0.f;
-    }
+    BNQuad bn;
+    bn.load_bwd(gamma, mean, invstd, sums, C, inv_count, training, q);
     float mx = 0.f;
     float cs[4] = {0.f, 0.f, 0.f, 0.f};
     for (size_t i = i0; i < total4; i += (size_t)gridDim.x * CL_TH) {
@@ -996,32 +798,16 @@ __global__ __launch_bounds__(CL_TH) void abr_bwd_kernel(const float* __restrict_
         const float de[4] = {dv.x, dv.y, dv.z, dv.w}, xe[4] = {xv.x, xv.y, xv.z, xv.w}, ze[4] = {zv.x, zv.y, zv.z, zv.w};
         float o[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float g = (ze[e] > 0.f) ? de[e] : 0.f;
-            o[e] = training ? w[e] * (g - k1[e] - ((xe[e] - mu[e]) * is[e]) * k2[e]) : g * w[e];
-        }
+        for (int e = 0; e < 4; ++e) o[e] = bn.dx(bn_mask(de[e], ze[e]), xe[e], e, training);
         if (ds_out) {
             const float4 pv = reinterpret_cast<const float4*>(ds_out)[i];
             o[0] += pv.x; o[1] += pv.y; o[2] += pv.z; o[3] += pv.w;
         }
         reinterpret_cast<float4*>(ds)[i] = make_float4(o[0], o[1], o[2], o[3]);
-        if (slot) mx = fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
+        if (slot) mx = cl_max4(mx, o);
         if (colpart) { cs[0] += o[0]; cs[1] += o[1]; cs[2] += o[2]; cs[3] += o[3]; }
     }
-    if (colpart) {
-        // block partial [C]: the 256 / (C / 4) threads that share a channel quad, in thread order (deterministic); colpart [blocks][C]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) csum[threadIdx.x * 4 + e] = cs[e];
-        __syncthreads();
-        for (int c = threadIdx.x; c < C; c += CL_TH) {
-            float t = 0.f;
-            const int base = (int)((size_t)blockIdx.x * CL_TH % (size_t)c4n);
-            const int first = ((c >> 2) - base + c4n) % c4n;
-            for (int th = first; th < CL_TH; th += c4n) t += csum[th * 4 + (c & 3)];
-            colpart[(size_t)blockIdx.x * C + c] = t;
-        }
-        __syncthreads();
-    }
+    if (colpart) cl_block_colsum(cs, csum, C, colpart + (size_t)blockIdx.x * C);
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
 
@@ -1034,33 +820,17 @@ extern "C" int m3t_add_bn_relu_cl_fwd(const float* a, const float* b, size_t M, 
                                       float* run_var, float momentum, float eps, int training, float* s_out, float* z, float* save_mean,
                                       float* save_invstd, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!bncl_shape_ok(M, C) || !a || !b || !z || !save_mean || !save_invstd || ((uintptr_t)a % 16) != 0 || ((uintptr_t)b % 16) != 0 ||
-        ((uintptr_t)z % 16) != 0 || ((uintptr_t)s_out % 16) != 0)
-        return M3T_EINVAL;
+    if (!bncl_shape_ok(M, C) || !al16(a) || !al16(b) || !al16(z) || !al16_opt(s_out) || !save_mean || !save_invstd) return M3T_EINVAL;
     if (training && !s_out) return M3T_EINVAL;
-    if (!training && (!run_mean || !run_var)) return M3T_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    const int rc = bn_stats(a, b, s_out, M, C, run_mean, run_var, momentum, eps, training, save_mean, save_invstd, ws, ws_bytes, st);
+    if (rc) return rc;
     const size_t total4 = M * (size_t)(C / 4);
-    if (training) {
-        if (M < 2) return M3T_EINVAL;
-        if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
-        const int nch = cl_chunks(M);
-        const size_t rpc = (M + nch - 1) / nch;
-        double* partial = reinterpret_cast<double*>(ws);
-        const int groups = CL_TH / (C / 4);
-        abr_partial_kernel<<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), st>>>(a, b, s_out, M, C, rpc, partial);
-        M3T_LAUNCH_CHECK();
-        bncl_stats_final_kernel<<<cdiv(C, 64), 256, 0, st>>>(partial, nch, (double)M, C, eps, momentum, run_mean, run_var, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
+    if (training)
         bncl_map_kernel<0><<<grid_for(total4, C / 4), CL_TH, 0, st>>>(s_out, nullptr, nullptr, gamma, beta, save_mean, save_invstd, nullptr, z, total4, C,
                                                                      0.f, 1, 1, slot, nullptr);
-        M3T_LAUNCH_CHECK();
-    } else {
-        bncl_eval_stats_kernel<<<cdiv(C, 256), 256, 0, st>>>(run_mean, run_var, C, eps, save_mean, save_invstd);
-        M3T_LAUNCH_CHECK();
-        abr_eval_kernel<<<grid_for(total4, C / 4), CL_TH, 0, st>>>(a, b, gamma, beta, save_mean, save_invstd, s_out, z, total4, C, slot);
-        M3T_LAUNCH_CHECK();
-    }
+    else abr_eval_kernel<<<grid_for(total4, C / 4), CL_TH, 0, st>>>(a, b, gamma, beta, save_mean, save_invstd, s_out, z, total4, C, slot);
+    M3T_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1071,29 +841,16 @@ extern "C" int m3t_add_bn_relu_cl_bwd(const float* dz, const float* ds_out, cons
                                       const float* save_mean, const float* save_invstd, size_t M, int C, int training, float* ds, float* dgamma,
                                       float* dbeta, float* ds_colsum, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!bncl_shape_ok(M, C) || !dz || !s || !z || !ds || !save_mean || !save_invstd || ((uintptr_t)dz % 16) != 0 || ((uintptr_t)s % 16) != 0 ||
-        ((uintptr_t)z % 16) != 0 || ((uintptr_t)ds % 16) != 0 || ((uintptr_t)ds_out % 16) != 0)
-        return M3T_EINVAL;
-    if (!ws || ws_bytes < m3t_bn_cl_ws_bytes(M, C) || ((uintptr_t)ws % 8) != 0) return M3T_EINVAL;
+    if (!bncl_shape_ok(M, C) || !al16(dz) || !al16(s) || !al16(z) || !al16(ds) || !al16_opt(ds_out) || !save_mean || !save_invstd) return M3T_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int nch = cl_chunks(M);
-    const size_t rpc = (M + nch - 1) / nch;
-    double* partial = reinterpret_cast<double*>(ws);
-    float* sums = reinterpret_cast<float*>(partial + (size_t)nch * 2 * C);
-    const int groups = CL_TH / (C / 4);
-    bncl_partial_kernel<1><<<nch, CL_TH, (size_t)2 * groups * C * sizeof(double), st>>>(dz, s, z, save_mean, save_invstd, M, C, rpc, 1, partial);
-    M3T_LAUNCH_CHECK();
-    bncl_bwd_final_kernel<<<cdiv(C, 64), 256, 0, st>>>(partial, nch, C, sums, dgamma, dbeta);
-    M3T_LAUNCH_CHECK();
     const size_t total4 = M * (size_t)(C / 4);
-    const int nblk = grid_for(total4, C / 4);
-    float* colpart = ds_colsum ? sums + 2 * (size_t)C + 64 : nullptr;
-    abr_bwd_kernel<<<nblk, CL_TH, 0, st>>>(dz, ds_out, s, z, gamma, save_mean, save_invstd, sums, ds, total4, C, (float)(1.0 / (double)M), training,
-                                           slot, colpart);
-    M3T_LAUNCH_CHECK();
-    if (ds_colsum) {
-        bncl_colsum_final_kernel<<<cdiv(C, 64), 256, 0, st>>>(colpart, nblk, C, ds_colsum);
-        M3T_LAUNCH_CHECK();
-    }
-    return 0;
+    return bn_bwd_chain(
+        M, M, C, total4, dgamma, dbeta, ds_colsum, ws, ws_bytes, st,
+        [&](int nch, size_t rpc, double* partial) {
+            bncl_partial_kernel<1><<<nch, CL_TH, bn_fold_lds(C), st>>>(dz, s, z, save_mean, save_invstd, M, C, rpc, 1, partial);
+        },
+        [&](int nblk, const float* sums, float* colpart) {
+            abr_bwd_kernel<<<nblk, CL_TH, 0, st>>>(dz, ds_out, s, z, gamma, save_mean, save_invstd, sums, ds, total4, C, (float)(1.0 / (double)M), training,
+                                                   slot, colpart);
+        });
 }

@@ -10,21 +10,17 @@
 // threads (row group g, quad q) keep their four channels for the whole chunk, column sums are fp64 from the first add to the last (thread ->
 // LDS in group order -> block partial -> the blocks' partials in a fixed order): deterministic, no float atomics.  NaN as torch: relu(NaN) = NaN, a NaN wins
 // its window, and the ReLU's backward lets dy through where y is NaN (threshold_backward: y <= 0 ? 0 : dy).
-#include "common.h"
+#include "cl_rows.h"
 
 namespace {
 
-constexpr int VG_TH = 256;
+constexpr int VG_TH = CL_TH;
 constexpr int VG_MAX_CHUNKS = 2048;
 
 // torch.relu: v > 0 ? v : (v != v ? v : 0)
 __device__ __forceinline__ float vg_relu(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 // the ReLU's gradient mask as torch's threshold_backward: 0 where y <= 0, dy elsewhere (a NaN y lets dy through)
 __device__ __forceinline__ float vg_mask(float dy, float y) { return y <= 0.f ? 0.f : dy; }
-
-__device__ __forceinline__ float vg_max4(float mx, const float (&o)[4]) {
-    return fmaxf(fmaxf(mx, fmaxf(m3t_fin_abs(o[0]), m3t_fin_abs(o[1]))), fmaxf(m3t_fin_abs(o[2]), m3t_fin_abs(o[3])));
-}
 
 static int vg_chunks(size_t M, int C) {
     // ~16 quads per thread and chunk, at most VG_MAX_CHUNKS chunks, at least one row per chunk
@@ -50,7 +46,7 @@ __global__ __launch_bounds__(VG_TH) void vg_relu_fwd_kernel(const float* x, floa
         const float4 v = reinterpret_cast<const float4*>(x)[i];
         const float o[4] = {vg_relu(v.x), vg_relu(v.y), vg_relu(v.z), vg_relu(v.w)};
         reinterpret_cast<float4*>(y)[i] = make_float4(o[0], o[1], o[2], o[3]);
-        if (slot) mx = vg_max4(mx, o);
+        if (slot) mx = cl_max4(mx, o);
     }
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
@@ -88,7 +84,7 @@ __global__ __launch_bounds__(VG_TH) void vg_relu_bwd_kernel(const float* dy, con
             const float4 v = reinterpret_cast<const float4*>(y)[i];
             const float o[4] = {vg_mask(d.x, v.x), vg_mask(d.y, v.y), vg_mask(d.z, v.z), vg_mask(d.w, v.w)};
             reinterpret_cast<float4*>(dx)[i] = make_float4(o[0], o[1], o[2], o[3]);
-            if (slot) mx = vg_max4(mx, o);
+            if (slot) mx = cl_max4(mx, o);
 #pragma unroll
             for (int e = 0; e < 4; ++e) cs[e] += (double)o[e];
         }
@@ -134,9 +130,7 @@ __device__ __forceinline__ void vg_decode(size_t r, int A, int B, size_t& p, int
         a = (int)(rr % (unsigned)A);
         p = rr / (unsigned)A;
     } else {
-        b = (int)(r % (size_t)B); r /= (size_t)B;
-        a = (int)(r % (size_t)A);
-        p = r / (size_t)A;
+        cl_decode(r, A, B, p, a, b);
     }
 }
 
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(VG_TH) void vg_relu_pool_fwd_kernel(const float* __
         }
         reinterpret_cast<float4*>(yp)[i] = make_float4(best[0], best[1], best[2], best[3]);
         reinterpret_cast<uchar4*>(win)[i] = make_uchar4((unsigned char)bi[0], (unsigned char)bi[1], (unsigned char)bi[2], (unsigned char)bi[3]);
-        if (slot) mx = vg_max4(mx, best);
+        if (slot) mx = cl_max4(mx, best);
     }
     if (slot) m3t_block_raise_slot(slot, mx, red4);
 }
@@ -212,7 +206,7 @@ __global__ __launch_bounds__(VG_TH) void vg_relu_pool_bwd_kernel(const float* __
                 if (b.w == me) o[3] = vg_mask(d.w, v.w);
             }
             reinterpret_cast<float4*>(dx)[r * (size_t)c4n + q] = make_float4(o[0], o[1], o[2], o[3]);
-            if (slot) mx = vg_max4(mx, o);
+            if (slot) mx = cl_max4(mx, o);
 #pragma unroll
             for (int e = 0; e < 4; ++e) cs[e] += (double)o[e];
         }
@@ -222,19 +216,40 @@ __global__ __launch_bounds__(VG_TH) void vg_relu_pool_bwd_kernel(const float* __
 }
 
 static bool vg_shape_ok(size_t M, int C) { return M > 0 && C > 0 && C % 4 == 0 && C <= 1024; }
-static bool vg_al16(const void* p) { return p && ((uintptr_t)p % 16) == 0; }
+static size_t vg_ws_bytes(size_t M, int C) { return (size_t)vg_chunks(M, C) * (size_t)C * sizeof(double); }      // fp64 chunk partials [chunks][C]
+static bool vgpool_geom(int H, int W, int C, int ceil_mode, VGPool& g) {
+    if (H < 1 || W < 1) return false;
+    g.H = H; g.W = W; g.C = C;
+    g.Ho = ceil_mode ? (H + 1) / 2 : H / 2; g.Wo = ceil_mode ? (W + 1) / 2 : W / 2;
+    return g.Ho >= 1 && g.Wo >= 1;
+}
+
+// A backward pass over M rows in chunks: the caller's launch(nch, lds_bytes, rows_per_chunk, partial) writes dx and, when dx_colsum is asked
+// for, the chunks' fp64 column sums into ws; then the chunks are folded into dx_colsum.
+template <class LAUNCH>
+int vg_bwd(size_t M, int C, float* dx_colsum, float* ws, size_t ws_bytes, hipStream_t s, LAUNCH launch) {
+    if (dx_colsum && !cl_ws_ok(ws, ws_bytes, vg_ws_bytes(M, C))) return M3T_EINVAL;
+    const int nch = vg_chunks(M, C), groups = VG_TH / (C / 4);
+    double* partial = dx_colsum ? reinterpret_cast<double*>(ws) : nullptr;
+    launch(nch, (size_t)groups * C * sizeof(double), (M + nch - 1) / nch, partial);
+    M3T_LAUNCH_CHECK();
+    if (dx_colsum) {
+        vg_colsum_final_kernel<<<cdiv(C, VG_FC), VG_TH, 0, s>>>(partial, nch, C, dx_colsum);
+        M3T_LAUNCH_CHECK();
+    }
+    return 0;
+}
 
 }  // namespace
 
-// fp64 chunk partials [chunks][C] of the backward passes' column sums
+// the workspace of the backward passes' column sums
 extern "C" size_t m3t_relu_cl_ws_bytes(size_t M, int C) {
-    if (!vg_shape_ok(M, C)) return 0;
-    return (size_t)vg_chunks(M, C) * (size_t)C * sizeof(double);
+    return vg_shape_ok(M, C) ? vg_ws_bytes(M, C) : 0;
 }
 
 extern "C" int m3t_relu_cl_fwd(const float* x, size_t M, int C, float* y, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!vg_shape_ok(M, C) || !vg_al16(x) || !vg_al16(y)) return M3T_EINVAL;
+    if (!vg_shape_ok(M, C) || !al16(x) || !al16(y)) return M3T_EINVAL;
     const size_t total4 = M * (size_t)(C / 4);
     vg_relu_fwd_kernel<<<vg_grid(total4), VG_TH, 0, (hipStream_t)stream>>>(x, y, total4, slot);
     M3T_LAUNCH_CHECK();
@@ -244,29 +259,17 @@ extern "C" int m3t_relu_cl_fwd(const float* x, size_t M, int C, float* y, void* 
 extern "C" int m3t_relu_cl_bwd(const float* dy, const float* y, size_t M, int C, float* dx, float* dx_colsum, float* ws, size_t ws_bytes,
                                void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (!vg_shape_ok(M, C) || !vg_al16(dy) || !vg_al16(y) || !vg_al16(dx)) return M3T_EINVAL;
-    if (dx_colsum && (!ws || ((uintptr_t)ws % 8) != 0 || ws_bytes < m3t_relu_cl_ws_bytes(M, C))) return M3T_EINVAL;
+    if (!vg_shape_ok(M, C) || !al16(dy) || !al16(y) || !al16(dx)) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int nch = vg_chunks(M, C);
-    const size_t rpc = (M + nch - 1) / nch;
-    const int groups = VG_TH / (C / 4);
-    double* partial = dx_colsum ? reinterpret_cast<double*>(ws) : nullptr;
-    vg_relu_bwd_kernel<<<nch, VG_TH, (size_t)groups * C * sizeof(double), s>>>(dy, y, dx, M, C, rpc, slot, partial);
-    M3T_LAUNCH_CHECK();
-    if (dx_colsum) {
-        vg_colsum_final_kernel<<<cdiv(C, VG_FC), VG_TH, 0, s>>>(partial, nch, C, dx_colsum);
-        M3T_LAUNCH_CHECK();
-    }
-    return 0;
+    return vg_bwd(M, C, dx_colsum, ws, ws_bytes, s, [&](int nch, size_t lds, size_t rpc, double* partial) {
+        vg_relu_bwd_kernel<<<nch, VG_TH, lds, s>>>(dy, y, dx, M, C, rpc, slot, partial);
+    });
 }
 
 extern "C" int m3t_relu_pool_cl_fwd(const float* x, size_t P, int H, int W, int C, int ceil_mode, float* yp, unsigned char* win, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (H < 1 || W < 1 || !vg_shape_ok(P, C) || !vg_al16(x) || !vg_al16(yp) || !win || ((uintptr_t)win % 4) != 0) return M3T_EINVAL;
     VGPool g;
-    g.H = H; g.W = W; g.C = C;
-    g.Ho = ceil_mode ? (H + 1) / 2 : H / 2; g.Wo = ceil_mode ? (W + 1) / 2 : W / 2;
-    if (g.Ho < 1 || g.Wo < 1) return M3T_EINVAL;
+    if (!vgpool_geom(H, W, C, ceil_mode, g) || !vg_shape_ok(P, C) || !al16(x) || !al16(yp) || !al4(win)) return M3T_EINVAL;
     const size_t total4 = P * (size_t)g.Ho * g.Wo * (size_t)(C / 4);
     vg_relu_pool_fwd_kernel<<<vg_grid(total4), VG_TH, 0, (hipStream_t)stream>>>(x, yp, win, total4, g, slot);
     M3T_LAUNCH_CHECK();
@@ -276,23 +279,11 @@ extern "C" int m3t_relu_pool_cl_fwd(const float* x, size_t P, int H, int W, int 
 extern "C" int m3t_relu_pool_cl_bwd(const float* dyp, const float* yp, const unsigned char* win, size_t P, int H, int W, int C, int ceil_mode,
                                     float* dx, float* dx_colsum, float* ws, size_t ws_bytes, void* stream) {
     unsigned long long* slot = m3t_take_amax_out();
-    if (H < 1 || W < 1 || !vg_shape_ok(P, C) || !vg_al16(dyp) || !vg_al16(yp) || !vg_al16(dx) || !win || ((uintptr_t)win % 4) != 0) return M3T_EINVAL;
     VGPool g;
-    g.H = H; g.W = W; g.C = C;
-    g.Ho = ceil_mode ? (H + 1) / 2 : H / 2; g.Wo = ceil_mode ? (W + 1) / 2 : W / 2;
-    if (g.Ho < 1 || g.Wo < 1) return M3T_EINVAL;
+    if (!vgpool_geom(H, W, C, ceil_mode, g) || !vg_shape_ok(P, C) || !al16(dyp) || !al16(yp) || !al16(dx) || !al4(win)) return M3T_EINVAL;
     const size_t M = P * (size_t)H * W;
-    if (dx_colsum && (!ws || ((uintptr_t)ws % 8) != 0 || ws_bytes < m3t_relu_cl_ws_bytes(M, C))) return M3T_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int nch = vg_chunks(M, C);
-    const size_t rpc = (M + nch - 1) / nch;
-    const int groups = VG_TH / (C / 4);
-    double* partial = dx_colsum ? reinterpret_cast<double*>(ws) : nullptr;
-    vg_relu_pool_bwd_kernel<<<nch, VG_TH, (size_t)groups * C * sizeof(double), s>>>(dyp, yp, win, dx, M, g, rpc, slot, partial);
-    M3T_LAUNCH_CHECK();
-    if (dx_colsum) {
-        vg_colsum_final_kernel<<<cdiv(C, VG_FC), VG_TH, 0, s>>>(partial, nch, C, dx_colsum);
-        M3T_LAUNCH_CHECK();
-    }
-    return 0;
+    return vg_bwd(M, C, dx_colsum, ws, ws_bytes, s, [&](int nch, size_t lds, size_t rpc, double* partial) {
+        vg_relu_pool_bwd_kernel<<<nch, VG_TH, lds, s>>>(dyp, yp, win, dx, M, g, rpc, slot, partial);
+    });
 }
