@@ -22,6 +22,7 @@
 // Arithmetic: the same fp32 MFMA 16x16x4 chain, k order, LDS reduction order and gate math as the per-step kernels,
 // so results are bit-identical to them (tests assert equality).
 #include "gru_common.h"
+#include "gru_persist_step.h"      // the exchange state and everything the kernels below share
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,163 +38,6 @@ namespace m3t_gru {
 namespace {
 
 constexpr int SPIN_LIMIT_DEFAULT = 1 << 21;     // gather attempts (~1 us each) before a workgroup gives up; env M3T_SCAN_SPIN_LIMIT
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-struct ExPtrs {
-    void* gran[M3T_MAX_SCANS];       // exchange granules: [2 slots][row block][unit block][RT*256]
-    size_t slot[M3T_MAX_SCANS];      // granules per slot
-    int poll_fixed;                  // >= 0: fixed poll delay (x 64 cycles); < 0: adapted per workgroup
-    int poll_align;                  // 1: waves without cell math count the delay from the workgroup's publish
-    int spin_limit;                  // gather attempts before a workgroup gives up (raises the error word, finishes with garbage)
-    int fault_step;                  // fault injection (flag M3T_SCAN_FAULT): workgroup 0 does not publish this step; -1 = never
-    unsigned long long* prof;        // optional in-kernel stamps (M3T_SCAN_PROF=1): 6 phase sums of workgroup 0, wave 0 (M3T_SCAN_PROF=2: wave 4, a wave without cell math)
-    int prof_tid;
-    int slot_map;                    // 1: persist_map's XCD-slot mapping (grid = 8 * ceil(G/8) * H/16), 0: gid = b % G
-    unsigned long long* hs;          // placement-handshake table (arena), or nullptr: no L2-served exchange
-    unsigned hs_tag;
-    int inline_prep;                 // 1: the kernel builds its W_hh fragments itself from the parameter (no prep launch in front of it)
-    unsigned tag_base;               // tags of this launch are tag_base + step + 1 (launch-unique inside an exchange arena: no memset per launch)
-    // progress marks (m3t_gru_scan_progress, round 5): consumers of a scan's results need not wait for the launch to end.  prog[0] counts
-    // for the scans that walk time upwards, prog[1] for those that walk it downwards; when a workgroup's results of every step < marks[dir][k]
-    // are in memory and visible device-wide it adds 1 to its counter (gru_persist_fwd6_kernel / gru_persist_bwd3q_kernel only)
-    unsigned* prog;
-    int nmarks;
-    int marks[2][3];
-};
-
-// Progress marks, the two halves of a signal (see ExPtrs.prog).  Results of step k leave a workgroup during step k or k + 1 (the memory-order
-// hand-over stores one step late) and have been acknowledged once every wave has passed the gather's `s_waitcnt vmcnt(0)` of step k + 2 at the
-// latest -- so: after the BARRIER of step mark + 1 one wave starts the write-back of its XCD's L2 (plain stores stay there:
-// MI355X_MICROARCH.md, inter-workgroup visibility), which retires in order in front of that wave's next gather (its `s_waitcnt vmcnt(0)`);
-// at the TOP of step mark + 3 -- in front of the gather, where the kernels have registers to spare (behind it the wide forward kernel
-// spilled three VGPRs for the atomic's operands) -- the same wave raises the counter.  The write-back overlaps the poll delay and the
-// gather's round trip: nothing waits for it.
-#define M3T_MARK_STATE()                                                                                         \
-    const int mdir = MARK_ASC ? 0 : 1;                                                                           \
-    /* (three scalars and selects: a dynamically indexed copy of ex.marks would live in scratch) */               \
-    const int mark0 = MARK_ASC ? ex.marks[0][0] : ex.marks[1][0], mark1 = MARK_ASC ? ex.marks[0][1] : ex.marks[1][1],  \
-              mark2 = MARK_ASC ? ex.marks[0][2] : ex.marks[1][2];                                                \
-    const int nmarks = ex.prog != nullptr ? ex.nmarks : 0;                                                       \
-    /* the signalling wave as a SCALAR (the wide kernels sit at 256 VGPRs: a per-lane predicate inside the loop spilled three of them) */ \
-    const bool mark_wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == NW - 1;                           \
-    const int mark_off = __builtin_amdgcn_readfirstlane(mdir * 4);    /* byte offset of this scan's counter (an "s" operand that is a select of pointers lands in VGPRs) */ \
-    int mk = 0, sig_step = nmarks > 0 ? mark0 + 1 : -1
-#define M3T_MARK_AT(k_) ((k_) >= nmarks ? -2 : ((k_) == 0 ? mark0 : ((k_) == 1 ? mark1 : mark2)))
-// (one lane adds: exec is narrowed inside the asm; address from SGPRs, operands defined inside: nothing for hipcc to keep in loop-long VGPRs)
-#define M3T_MARK_STEP_TOP(step_)                                                                                 \
-    do {                                                                                                         \
-        if ((step_) == sig_step + 2 && sig_step >= 0) {                                                          \
-            if (mark_wave) {                                                                                     \
-                unsigned z_, o_;                                                                                 \
-                unsigned long long sv_;                                                                          \
-                asm volatile("s_mov_b64 %2, exec\n\ts_mov_b64 exec, 1\n\tv_mov_b32 %0, %4\n\tv_mov_b32 %1, 1\n\t" \
-                             "global_atomic_add %0, %1, %3\n\ts_mov_b64 exec, %2"                                \
-                             : "=&v"(z_), "=&v"(o_), "=&s"(sv_) : "s"(ex.prog), "s"(mark_off) : "memory");       \
-            }                                                                                                    \
-            ++mk;                                                                                                \
-            sig_step = M3T_MARK_AT(mk) + 1;                                                                      \
-        }                                                                                                        \
-    } while (0)
-// (buffer_wbl2 is one cache operation per WAVE instruction, whatever the lanes)
-#define M3T_MARK_AFTER_BARRIER(step_)                                                                            \
-    do {                                                                                                         \
-        if ((step_) == sig_step && mark_wave) asm volatile("buffer_wbl2 sc1" ::: "memory");                      \
-    } while (0)
-
-// phase stamps: s_memtime deltas accumulated by one lane; a uniform scalar branch when profiling is off
-// Polling for the peers' granules.  A gather attempt is a full round trip (~1 us) and the next attempt is only issued
-// when it has returned, so an attempt that leaves just before the data becomes visible costs a whole extra round trip --
-// and the attempt issued right after a workgroup's own publish is always that attempt (the peers are still in their cell
-// phase).  Every wave therefore sleeps `poll_delay` x 64 cycles before its first attempt.  Measured with fixed delays
-// (M3T_SCAN_POLL_FWD6 / _FWD / _BWD = n, tools/scan_bench.py, H=512, three boxes): bf16x6 forward 3.1 -> 2.3 us per step
-// at 16-24 units; backward 4.8-5.1 -> 3.9-4.7 at 12-18 (the gain varies from box to box, it was never negative); fp32
-// forward 4.9 -> 4.2-4.4 at 12-18, nothing at H=128; all worse again beyond ~24.  Policy:
-//   * bf16x6 forward: adaptive, one delay per workgroup (the step ends when the slowest of the 8 waves has its data, so
-//     per-wave controllers that each sit at their own edge fail somewhere almost every step): a wave whose first attempt
-//     failed sets a flag in LDS, after the step's barrier every wave reads it and moves the common delay +2 on a failure,
-//     -1 every eighth step otherwise.  It finds the best fixed value (2.3 / 2.6 / 1.76 us at 2x512 / 4x512 / 2x256).
-//   * backward and fp32 forward: fixed (12 units; 0 for the fp32 forward at H=128); in the backward scan the four waves
-//     that do no cell math arrive at the gather a cell phase early, and their first attempt then fails and their second
-//     returns after the cell-math waves' well-timed first one (in-kernel stamps: the cell-math waves waited 0.84 us at
-//     the step's barrier): they first wait in LDS for thread 0's "published" mark, so every wave counts the delay from
-//     the workgroup's own publish (M3T_SCAN_POLL_ALIGN; backward 4.7 -> 4.2 us per step on the boxes where it was not
-//     already there; no gain for the adaptive bf16x6 forward, which finds a delay that suits its early waves).  The same controller over-sleeps
-//     them (5.1 us), as do its variants (per-wave; waves without cell math aligned to the workgroup's publish first; a
-//     hill-climb on the s_memtime of 8-step windows is too noisy within 300 steps) -- the failure flag does not say
-//     what a failure cost there.
-constexpr int POLL_DELAY_INIT = 8, POLL_DELAY_MAX = 64;
-
-#define M3T_STAMP(i)                                                         \
-    do {                                                                     \
-        if (stamp) { const long long now = clock64(); psum[i] += now - last; last = now; } \
-    } while (0)
-
-// err[0]: step + 1 of the failing wait (for the message); err[1]: the STICKY flag the device-side guards read
-// (m3t_grad_norm_scale, m3t_grad_poison).  Nothing but m3t_gru_error_reset() -- which the host may only call after it has
-// synchronised the device -- ever clears either word, so work queued behind a dead scan sees the flag however far ahead
-// of the GPU the host runs.
-__device__ __forceinline__ void raise_spin(unsigned* err, int step) {
-    __hip_atomic_store(err, (unsigned)step + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(err + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// Block -> (group, unit block).  A group (one scan x one row block) is the set of workgroups that exchange h_t / dgh_t with each
-// other every step.  Blocks b and b + 8 share an XCD (observed dispatch rule: blocks are dealt round-robin over the 8 XCDs), so
-// slot = b % 8 names an XCD and a group lives entirely in one slot: group g sits in slot g % 8 (gpx = ceil(G / 8) groups per slot),
-// its members are the blocks of that slot.  The launch has 8 * gpx * (H / 16) blocks; blocks of slots that host no group exit at
-// once.  Placement is speed only -- persist_handshake() below checks it and falls back -- never correctness.
-__device__ __forceinline__ bool persist_map(int b, int G, int slot_map, int& gid, int& ub) {
-    if (!slot_map) { gid = b % G; ub = b / G; return true; }      // plain round-robin: a group spans XCDs unless G % 8 == 0
-    const int slot = b & 7, j = b >> 3, gpx = (G + 7) >> 3;
-    gid = slot + 8 * (j % gpx);
-    ub = j / gpx;
-    return gid < G;
-}
-
-// Placement handshake, once per launch (needs the exchange arena): every workgroup publishes the id of the XCD it runs on
-// (HW_REG_XCC_ID) as a tagged 8-byte granule with an agent-scope store, wave 0 gathers the ids of its group's members with
-// agent-scope loads (the one exchange of the launch that must not depend on placement) and all members reach the same verdict:
-// if they all share one XCD, the group's granules may travel through that XCD's L2 -- PLAIN stores (write-through, the line stays
-// in L2) read by the same `sc1` loads (which bypass only the reader's L1) -- instead of through the memory side.  Measured
-// (rocprofv3 FETCH_SIZE / WRITE_SIZE): the 4 x H=512 backward launch 2.0 -> 1.4 GB of HBM / fabric traffic (algorithmic 0.94), the
-// scorers' 0.45 -> 0.30 GB; step time -1 % (the steps no longer wait on the gather).  A group that spans XCDs keeps sc1 stores: a
-// reader's L2 could hold a stale copy of a line another XCD rewrote.  Stale or missing data can only ever delay a consumer (tags),
-// so a wrong verdict would end in the bounded-spin error, not in wrong numbers.
-constexpr int HS_STRIDE = 32;                          // granules per group in the handshake table (H / 16 <= 32 members)
-__device__ __forceinline__ int persist_handshake(const ExPtrs& ex, int gid, int ub, int members, int tid, unsigned* err) {
-    __shared__ int s_l2;
-    if (ex.hs == nullptr) return 0;
-    const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xfu;       // HW_REG_XCC_ID[3:0]
-    unsigned long long* hs = ex.hs + (size_t)gid * HS_STRIDE;
-    if (tid == 0) {
-        const unsigned long long g = ((unsigned long long)ex.hs_tag << 32) | xcc;
-        asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(hs + ub), "v"(g) : "memory");
-    }
-    if (tid < 64) {
-        const int lane = tid;
-        const unsigned long long* q = hs + (lane < members ? lane : 0);
-        bool same = true;
-        int spins = 0;
-        for (;;) {
-            unsigned long long v;
-            asm volatile("global_load_dwordx2 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(q) : "memory");
-            const bool ok = (unsigned)(v >> 32) == ex.hs_tag;
-            same = (unsigned)v == xcc;
-            if (__all(ok)) break;
-            if (++spins > ex.spin_limit) { same = false; if (lane == 0) raise_spin(err, 0); break; }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        const bool all_same = __all(same);
-        if (lane == 0) s_l2 = all_same ? 1 : 0;
-    }
-    __syncthreads();
-    return s_l2;
-}
-
-// Order of a step: gather (loads only, inline asm: all loads of the pass in flight, ONE explicit wait -- left to
-// hipcc the loads were issued and waited for in groups) -> MFMA -> LDS partials -> barrier -> reduce + cell math ->
-// publish -> [results to HBM, next step's inputs from HBM].  The HBM traffic is issued after the publish, so it is in
-// flight while the peers' granules travel and is never waited for on the chain.
 
 // ------------------------------------------------------------------------------------------------ forward
 template <int NC, int RT>      // NC = H / 128 = k-chunks per wave;  RT = 16-row tiles per workgroup
@@ -203,10 +47,7 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd_kernel(FwdGroup g, FragPtr
     constexpr int NB = RT == 1 ? 2 : 1;                // RT = 1: double-buffered by step parity, one barrier per step
     constexpr int H = 128 * NC, nch = H >> 4;
     __shared__ float red[NB][NW][3][ROWS][UB + 1];     // 51 KiB either way (static LDS limit 64 KiB); +1: conflict-free reads
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int gid, ub;
-    if (!persist_map((int)blockIdx.x, G, ex.slot_map, gid, ub)) return;      // a block of an XCD slot that hosts no group of this launch
-    const int s = gid / nrb, rb = gid % nrb;
+    M3T_PERSIST_WHO(ub);
     const m3t_gru_fwd_desc d = g.d[s];
     const int j0 = ub * UB, r0 = rb * ROWS;
 
@@ -235,61 +76,17 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd_kernel(FwdGroup g, FragPtr
     const size_t slot = ex.slot[s];
     const size_t grp = (size_t)rb * nch * TILE;
     const size_t pub = grp + (size_t)ub * TILE + tid;
-    bool dead = false;
-    int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
-    __shared__ unsigned poll_fail[2];                  // by step parity
-    __shared__ int pub_step;                           // steps this workgroup has published (thread 0)
-    const int l2mode = persist_handshake(ex, gid, ub, H >> 4, tid, err);     // 1: this group shares one XCD's L2 (publish with plain stores)
-    if (tid == 0) pub_step = 0;
-    if (tid < 2) poll_fail[tid] = 0;                   // first read after the first barrier
-    const bool stamp = ex.prof != nullptr && blockIdx.x == 0 && tid == ex.prof_tid;
-    long long psum[6] = {0, 0, 0, 0, 0, 0}, last = stamp ? clock64() : 0;
+    M3T_PERSIST_POLL_STATE(ub, H >> 4);
+    M3T_STAMP_STATE();
 
-    // x-projection of the step.  The next step's is requested right after this step's gather has completed (nothing else
-    // outstanding then) and has the rest of the step to arrive: requested after the publish it sat in front of the next
-    // gather's vmcnt(0) (vector-memory operations retire in order).  Inline asm, unconditional (lanes past the batch
-    // and the step past the end re-read a valid address), two register sets (A: even steps, B: odd; the loop body is
-    // included twice), defined by the next gather's vmcnt(0) and laundered there -- see gru_persist_bwd_kernel.
-    float xrA, xzA, xnA, xrB, xzB, xnB;
+    float xrA, xzA, xnA, xrB, xzB, xnB;                // the x-projection's two register sets (M3T_FWD_LOAD_X)
     const float* xq = d.xproj + (size_t)(pb < B ? pb : B - 1) * T * d.ldx + d.xoff + pj;
-#define M3T_FWD_LOAD_X(step_, XR, XZ, XN)                                                                             \
-    do {                                                                                                               \
-        const int ls_ = (step_) < T ? (step_) : T - 1;                                                                 \
-        const float* xa_ = xq + (size_t)(d.reverse ? T - 1 - ls_ : ls_) * d.ldx;                                       \
-        asm volatile("global_load_dword %0, %3, off\n\t"                                                               \
-                     "global_load_dword %1, %4, off\n\t"                                                               \
-                     "global_load_dword %2, %5, off"                                                                   \
-                     : "=&v"(XR), "=&v"(XZ), "=&v"(XN) : "v"(xa_), "v"(xa_ + H), "v"(xa_ + 2 * H) : "memory");         \
-    } while (0)
-    M3T_FWD_LOAD_X(0, xrA, xzA, xnA);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(xrA), "+v"(xzA), "+v"(xnA) :: "memory");
-    // everything loaded so far is in registers before the loop: hipcc then places no vmcnt wait for the weight
-    // fragments inside the step
-    __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
+    M3T_FWD_LOAD_X_FIRST();
 
-    for (int step2 = 0; step2 < T; step2 += 2) {
-#define STEPV step2
-#define CUR(x) x##A
-#define NXT(x) x##B
-#include "gru_persist_fwd_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-        if (step2 + 1 >= T) break;
-#define STEPV (step2 + 1)
-#define CUR(x) x##B
-#define NXT(x) x##A
-#include "gru_persist_fwd_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-    }
-#undef M3T_FWD_LOAD_X
-    // the last step's request for "the next step's inputs" is still in flight and invisible to hipcc (inline asm): a wave must
-    // not end with a load outstanding into registers that the next wave on this SIMD is about to own
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (stamp)
-        for (int i = 0; i < 6; ++i) ex.prof[i] = (unsigned long long)psum[i];
+#define M3T_STEP_FILE "gru_persist_fwd_step.inc"
+#include "gru_persist_ab.inc"
+    scan_drain();
+    M3T_STAMP_DUMP();
 }
 
 // ------------------------------------------------------------------------------------------------ forward, bf16x6
@@ -416,10 +213,7 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPt
     extern __shared__ __attribute__((aligned(16))) float red_d[];
     float* const red = UW == 1 ? red_s : red_d;
 #define M3T_RED(par_, w_, u_, ct_, r_, c_) red[(((((par_) * NW + (w_)) * UW + (u_)) * 3 + (ct_)) * ROWS + (r_)) * (UB + 1) + (c_)]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int gid, ubw;
-    if (!persist_map((int)blockIdx.x, G, ex.slot_map, gid, ubw)) return;      // a block of an XCD slot that hosts no group of this launch
-    const int s = gid / nrb, rb = gid % nrb;
+    M3T_PERSIST_WHO(ubw);
     const m3t_gru_fwd_desc d = g.d[s];
     const int tu = UW == 1 ? 0 : (tid >> 8);           // the unit tile this thread does cell math for
     const int ub = ubw * UW + tu;
@@ -514,24 +308,12 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPt
     // (RB = 8: row lane & 7, and lane bit 3 picks the odd unit pair jp, 64 granules on)
     const size_t lane_off = RB < ROWS ? (size_t)(wave + NW * (q >> 1)) * TILE + 2 * ((q & 1) * 16 + (lane & 7)) + 64 * ((lane >> 3) & 1)
                                       : (size_t)(wave + NW * (q >> 1)) * TILE + 2 * ((q & 1) * 16 + (lane & 15));
-    bool dead = false;
-    int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
-    __shared__ unsigned poll_fail[2];                  // by step parity
-    __shared__ int pub_step;                           // steps this workgroup has published (thread 0)
-    const int l2mode = persist_handshake(ex, gid, ubw, (H >> 4) / UW, tid, err);     // 1: this group shares one XCD's L2 (publish with plain stores)
-    if (tid == 0) pub_step = 0;
-    if (tid < 2) poll_fail[tid] = 0;                   // first read after the first barrier
-    const bool stamp = ex.prof != nullptr && blockIdx.x == 0 && tid == ex.prof_tid;
-    long long psum[6] = {0, 0, 0, 0, 0, 0}, last = stamp ? clock64() : 0;
+    M3T_PERSIST_POLL_STATE(ubw, (H >> 4) / UW);
+    M3T_STAMP_STATE();
 
     const bool MARK_ASC = !d.reverse;
     M3T_MARK_STATE();
-    // x-projection of the step in (xr, xz, xn).  The next step's is requested right after this step's gather has
-    // completed (nothing else outstanding then) and has the rest of the step to arrive: loaded after the publish it sat
-    // in front of the next gather's vmcnt(0) (vector-memory operations retire in order).  Inline asm, unconditional
-    // (lanes past the batch and the step past the end re-read a valid address), defined by the next gather's vmcnt(0)
-    // and laundered there -- as in the backward kernel below, compiler-visible loads made hipcc wait for them mid-step.
-    float xrA, xzA, xnA, xrB, xzB, xnB;               // two register sets: even / odd steps (the loop body is included twice)
+    float xrA, xzA, xnA, xrB, xzB, xnB;                // the x-projection's two register sets (M3T_FWD_LOAD_X)
     // memory-side identity of this thread (CO; else = its cell) and the LDS slots of the hand-over, padded one per 16
     const int hrow = CO ? (ti >> 4) : prow, hun = CO ? (ti & 15) : pu;
     const int hb = r0 + hrow, hj = j0 + hun;
@@ -543,57 +325,21 @@ __global__ __launch_bounds__(NT) void gru_persist_fwd6_kernel(FwdGroup g, FragPt
     f32x4* const so = sx + 2 * UW * SLOTS;                                                // [parity][UW][SLOTS] (r, z, n, W_hn h + b_hn)
     float* const sh = reinterpret_cast<float*>(so + 2 * UW * SLOTS);                      // [parity][UW][SLOTS] h_t
     const float* xq = d.xproj + (size_t)(hb < B ? hb : B - 1) * T * d.ldx + d.xoff + hj;
-    auto store_results = [&](int step_of, const f32x4& g4, float hv) {
+    auto store_results = [&](int step_of, const f32x4& g4, float hv) {      // (CO: the memory-order thread, one step late)
         const int t_ = d.reverse ? T - 1 - step_of : step_of;
-        d.out[((size_t)hb * T + t_) * d.ldo + d.ooff + hj] = hv;
-        if (d.gates) *reinterpret_cast<f32x4*>(d.gates + ((size_t)hb * T + t_) * 4 * H + 4 * (size_t)hj) = g4;
-        if (d.h_n && step_of == T - 1) d.h_n[(size_t)hb * H + hj] = hv;
+        M3T_FWD_STORE_RESULTS(hb, hj, t_, step_of == T - 1, f32x4, g4, hv);
     };
-#define M3T_FWD_LOAD_X(step_, XR, XZ, XN)                                                                             \
-    do {                                                                                                               \
-        const int ls_ = (step_) < T ? (step_) : T - 1;                                                                 \
-        const float* xa_ = xq + (size_t)(d.reverse ? T - 1 - ls_ : ls_) * d.ldx;                                       \
-        asm volatile("global_load_dword %0, %3, off\n\t"                                                               \
-                     "global_load_dword %1, %4, off\n\t"                                                               \
-                     "global_load_dword %2, %5, off"                                                                   \
-                     : "=&v"(XR), "=&v"(XZ), "=&v"(XN) : "v"(xa_), "v"(xa_ + H), "v"(xa_ + 2 * H) : "memory");         \
-    } while (0)
-    M3T_FWD_LOAD_X(0, xrA, xzA, xnA);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(xrA), "+v"(xzA), "+v"(xnA) :: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0): see gru_persist_fwd_kernel
+    M3T_FWD_LOAD_X_FIRST();
 
-    for (int step2 = 0; step2 < T; step2 += 2) {
-#define STEPV step2
-#define PARV 0
-#define CUR(x) x##A
-#define NXT(x) x##B
-#include "gru_persist_fwd6_step.inc"
-#undef STEPV
-#undef PARV
-#undef CUR
-#undef NXT
-        if (step2 + 1 >= T) break;
-#define STEPV (step2 + 1)
-#define PARV 1
-#define CUR(x) x##B
-#define NXT(x) x##A
-#include "gru_persist_fwd6_step.inc"
-#undef STEPV
-#undef PARV
-#undef CUR
-#undef NXT
-    }
-#undef M3T_FWD_LOAD_X
+#define M3T_STEP_FILE "gru_persist_fwd6_step.inc"
+#include "gru_persist_ab.inc"
 #undef M3T_RED
-    // the last step's request for "the next step's inputs" is still in flight and invisible to hipcc (inline asm): a wave must
-    // not end with a load outstanding into registers that the next wave on this SIMD is about to own
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    scan_drain();
     if (CO) {                                          // the last step's results are still in LDS
         __syncthreads();
         if (hok) store_results(T - 1, so[((T - 1) & 1) * UW * SLOTS + slot_h], sh[((T - 1) & 1) * UW * SLOTS + slot_h]);
     }
-    if (stamp)
-        for (int i = 0; i < 6; ++i) ex.prof[i] = (unsigned long long)psum[i];
+    M3T_STAMP_DUMP();
 }
 
 // ------------------------------------------------------------------------------------------------ backward, bf16 mode
@@ -627,10 +373,7 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd16_kernel(BwdGroup g, FragP
     constexpr int ROWS = 16, RT = 1, KS = NC / 2;
     constexpr int H = 128 * NC, H3 = 3 * H, nchh = H >> 4;
     __shared__ float red[2][NW][ROWS][UB + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int gid, ub;
-    if (!persist_map((int)blockIdx.x, G, ex.slot_map, gid, ub)) return;      // a block of an XCD slot that hosts no group of this launch
-    const int s = gid / nrb, rb = gid % nrb;
+    M3T_PERSIST_WHO(ub);
     const m3t_gru_bwd_desc d = g.d[s];
     const int j0 = ub * UB, r0 = rb * ROWS;
 
@@ -657,86 +400,15 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd16_kernel(BwdGroup g, FragP
     const size_t slot = ex.slot[s];
     const size_t grp = (size_t)rb * nchh * TILE;
     const size_t pub = grp + (size_t)ub * TILE + tid;
-    bool dead = false;
-    int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
-    __shared__ unsigned poll_fail[2];                  // by step parity
-    __shared__ int pub_step;                           // steps this workgroup has published (thread 0)
-    const int l2mode = persist_handshake(ex, gid, ub, H >> 4, tid, err);     // 1: this group shares one XCD's L2 (publish with plain stores)
-    if (tid == 0) pub_step = 0;
-    if (tid < 2) poll_fail[tid] = 0;                   // first read after the first barrier
-    const bool stamp = ex.prof != nullptr && blockIdx.x == 0 && tid == ex.prof_tid;
-    long long psum[6] = {0, 0, 0, 0, 0, 0}, last = stamp ? clock64() : 0;
+    M3T_PERSIST_POLL_STATE(ub, H >> 4);
+    M3T_STAMP_STATE();
+    M3T_BWD_ENVELOPE(pb, pj);
 
-    // HBM traffic of a step and the chain.  Vector-memory operations retire in order, so everything a wave has issued
-    // before its gather loads sits in front of the gather's vmcnt(0): with the step's six result stores and the next
-    // step's three activation loads issued after the publish (the natural place), every step waited ~0.7 us for each
-    // group (tools/scan_bench.py ablation), and hipcc added a vmcnt(0) + register copies at the bottom of the step on
-    // top (2.4 of 5 us, in-kernel stamps).  Now: the results of step t are kept in registers and stored, and the
-    // activations of step t+1 are requested, right AFTER the gather of step t has completed -- they have the whole
-    // step (MFMAs, barrier, cell math, publish, the peers' latency) to retire before the next gather waits, and between
-    // the publish and the next gather a wave has nothing outstanding but the publish itself.  Two register sets (A for
-    // even steps, B for odd ones; the loop body is included twice) hold the activations; the loads are inline asm,
-    // UNCONDITIONAL (every thread, every step; lanes past the batch and the step past the end re-read a valid address):
-    // compiler-visible or conditional definitions make hipcc wait for them or merge them with copies that read
-    // registers still in flight.  A set is defined by the vmcnt(0) of the gather that precedes its use and laundered there.
-    float doutA, hprevA, doutB, hprevB;
-    f32x4 g4A, g4B;                                    // (r, z, n, W_hn h + b_hn) of this (row, unit, t)
-    const int pbc = pb < B ? pb : B - 1;
-    const float* pd0 = d.dout + (size_t)pbc * T * d.ldo + d.ooff + pj;
-    const float* pg0 = d.gates + (size_t)pbc * T * 4 * H + 4 * (size_t)pj;
-    const float* ph0 = d.out + (size_t)pbc * T * d.ldo + d.ooff + pj;
-#define M3T_BWD_LOAD_STEP(step_, DOUT, G4, HPREV)                                                                     \
-    do {                                                                                                               \
-        const int ls_ = (step_) < T ? (step_) : T - 1;                                                                 \
-        const int lt_ = d.reverse ? ls_ : T - 1 - ls_;                                                                 \
-        const int ltp_ = ls_ < T - 1 ? (d.reverse ? lt_ + 1 : lt_ - 1) : lt_;                                          \
-        asm volatile("global_load_dword %0, %3, off\n\t"                                                               \
-                     "global_load_dwordx4 %1, %4, off\n\t"                                                             \
-                     "global_load_dword %2, %5, off"                                                                   \
-                     : "=&v"(DOUT), "=&v"(G4), "=&v"(HPREV)                                                            \
-                     : "v"(pd0 + (size_t)lt_ * d.ldo), "v"(pg0 + (size_t)lt_ * 4 * H), "v"(ph0 + (size_t)ltp_ * d.ldo)  \
-                     : "memory");                                                                                      \
-    } while (0)
-    M3T_BWD_LOAD_STEP(0, doutA, g4A, hprevA);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(doutA), "+v"(g4A), "+v"(hprevA) :: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0), visible to hipcc: no wait for the weight fragments inside the loop
-    float st_dr = 0.f, st_dz = 0.f, st_dn = 0.f, st_dnr = 0.f;     // results of the previous step, stored after this step's gather
-    auto store_results = [&](int step_of) {
-        const int t = d.reverse ? step_of : T - 1 - step_of;
-        float* gx = d.dgx + ((size_t)pb * T + t) * d.ldg + d.goff;
-        gx[pj] = st_dr; gx[H + pj] = st_dz; gx[2 * H + pj] = st_dn;
-        float* gh = d.dgh + ((size_t)pb * T + t) * H3;
-        gh[pj] = st_dr; gh[H + pj] = st_dz; gh[2 * H + pj] = st_dnr;
-    };
-
-    for (int step2 = 0; step2 < T; step2 += 2) {
-#define STEPV step2
-#define CUR(x) x##A
-#define NXT(x) x##B
-#include "gru_persist_bwd16_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-        if (step2 + 1 >= T) break;
-#define STEPV (step2 + 1)
-#define CUR(x) x##B
-#define NXT(x) x##A
-#include "gru_persist_bwd16_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-    }
-#undef M3T_BWD_LOAD_STEP
-    // the last step's request for "the next step's inputs" is still in flight and invisible to hipcc (inline asm): a wave must
-    // not end with a load outstanding into registers that the next wave on this SIMD is about to own
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (pok) d.dh[(size_t)pb * H + pj] = dh_carry;
-    if (pok && d.db_part) {
-        float* q = d.db_part + (size_t)pb * 4 * H + pj;
-        q[0] = sb_r; q[H] = sb_z; q[2 * H] = sb_n; q[3 * H] = sb_nr;
-    }
-    if (stamp)
-        for (int i = 0; i < 6; ++i) ex.prof[i] = (unsigned long long)psum[i];
+#define M3T_STEP_FILE "gru_persist_bwd16_step.inc"
+#include "gru_persist_ab.inc"
+    scan_drain();
+    M3T_BWD_STORE_CARRY();
+    M3T_STAMP_DUMP();
 }
 
 
@@ -747,10 +419,7 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd_kernel(BwdGroup g, FragPtr
     constexpr int ROWS = 16 * RT;
     constexpr int H = 128 * NC, H3 = 3 * H, nchh = H >> 4, nch = H3 >> 4;
     __shared__ float red[2][NW][ROWS][UB + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int gid, ub;
-    if (!persist_map((int)blockIdx.x, G, ex.slot_map, gid, ub)) return;      // a block of an XCD slot that hosts no group of this launch
-    const int s = gid / nrb, rb = gid % nrb;
+    M3T_PERSIST_WHO(ub);
     const m3t_gru_bwd_desc d = g.d[s];
     const int j0 = ub * UB, r0 = rb * ROWS;
 
@@ -776,86 +445,15 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd_kernel(BwdGroup g, FragPtr
     const size_t slot = ex.slot[s];
     const size_t grp = (size_t)rb * nchh * TILE;
     const size_t pub = grp + (size_t)ub * TILE + tid;
-    bool dead = false;
-    int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
-    __shared__ unsigned poll_fail[2];                  // by step parity
-    __shared__ int pub_step;                           // steps this workgroup has published (thread 0)
-    const int l2mode = persist_handshake(ex, gid, ub, H >> 4, tid, err);     // 1: this group shares one XCD's L2 (publish with plain stores)
-    if (tid == 0) pub_step = 0;
-    if (tid < 2) poll_fail[tid] = 0;                   // first read after the first barrier
-    const bool stamp = ex.prof != nullptr && blockIdx.x == 0 && tid == ex.prof_tid;
-    long long psum[6] = {0, 0, 0, 0, 0, 0}, last = stamp ? clock64() : 0;
+    M3T_PERSIST_POLL_STATE(ub, H >> 4);
+    M3T_STAMP_STATE();
+    M3T_BWD_ENVELOPE(pb, pj);
 
-    // HBM traffic of a step and the chain.  Vector-memory operations retire in order, so everything a wave has issued
-    // before its gather loads sits in front of the gather's vmcnt(0): with the step's six result stores and the next
-    // step's three activation loads issued after the publish (the natural place), every step waited ~0.7 us for each
-    // group (tools/scan_bench.py ablation), and hipcc added a vmcnt(0) + register copies at the bottom of the step on
-    // top (2.4 of 5 us, in-kernel stamps).  Now: the results of step t are kept in registers and stored, and the
-    // activations of step t+1 are requested, right AFTER the gather of step t has completed -- they have the whole
-    // step (MFMAs, barrier, cell math, publish, the peers' latency) to retire before the next gather waits, and between
-    // the publish and the next gather a wave has nothing outstanding but the publish itself.  Two register sets (A for
-    // even steps, B for odd ones; the loop body is included twice) hold the activations; the loads are inline asm,
-    // UNCONDITIONAL (every thread, every step; lanes past the batch and the step past the end re-read a valid address):
-    // compiler-visible or conditional definitions make hipcc wait for them or merge them with copies that read
-    // registers still in flight.  A set is defined by the vmcnt(0) of the gather that precedes its use and laundered there.
-    float doutA, hprevA, doutB, hprevB;
-    f32x4 g4A, g4B;                                    // (r, z, n, W_hn h + b_hn) of this (row, unit, t)
-    const int pbc = pb < B ? pb : B - 1;
-    const float* pd0 = d.dout + (size_t)pbc * T * d.ldo + d.ooff + pj;
-    const float* pg0 = d.gates + (size_t)pbc * T * 4 * H + 4 * (size_t)pj;
-    const float* ph0 = d.out + (size_t)pbc * T * d.ldo + d.ooff + pj;
-#define M3T_BWD_LOAD_STEP(step_, DOUT, G4, HPREV)                                                                     \
-    do {                                                                                                               \
-        const int ls_ = (step_) < T ? (step_) : T - 1;                                                                 \
-        const int lt_ = d.reverse ? ls_ : T - 1 - ls_;                                                                 \
-        const int ltp_ = ls_ < T - 1 ? (d.reverse ? lt_ + 1 : lt_ - 1) : lt_;                                          \
-        asm volatile("global_load_dword %0, %3, off\n\t"                                                               \
-                     "global_load_dwordx4 %1, %4, off\n\t"                                                             \
-                     "global_load_dword %2, %5, off"                                                                   \
-                     : "=&v"(DOUT), "=&v"(G4), "=&v"(HPREV)                                                            \
-                     : "v"(pd0 + (size_t)lt_ * d.ldo), "v"(pg0 + (size_t)lt_ * 4 * H), "v"(ph0 + (size_t)ltp_ * d.ldo)  \
-                     : "memory");                                                                                      \
-    } while (0)
-    M3T_BWD_LOAD_STEP(0, doutA, g4A, hprevA);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(doutA), "+v"(g4A), "+v"(hprevA) :: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0), visible to hipcc: no wait for the weight fragments inside the loop
-    float st_dr = 0.f, st_dz = 0.f, st_dn = 0.f, st_dnr = 0.f;     // results of the previous step, stored after this step's gather
-    auto store_results = [&](int step_of) {
-        const int t = d.reverse ? step_of : T - 1 - step_of;
-        float* gx = d.dgx + ((size_t)pb * T + t) * d.ldg + d.goff;
-        gx[pj] = st_dr; gx[H + pj] = st_dz; gx[2 * H + pj] = st_dn;
-        float* gh = d.dgh + ((size_t)pb * T + t) * H3;
-        gh[pj] = st_dr; gh[H + pj] = st_dz; gh[2 * H + pj] = st_dnr;
-    };
-
-    for (int step2 = 0; step2 < T; step2 += 2) {
-#define STEPV step2
-#define CUR(x) x##A
-#define NXT(x) x##B
-#include "gru_persist_bwd_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-        if (step2 + 1 >= T) break;
-#define STEPV (step2 + 1)
-#define CUR(x) x##B
-#define NXT(x) x##A
-#include "gru_persist_bwd_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-    }
-#undef M3T_BWD_LOAD_STEP
-    // the last step's request for "the next step's inputs" is still in flight and invisible to hipcc (inline asm): a wave must
-    // not end with a load outstanding into registers that the next wave on this SIMD is about to own
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (pok) d.dh[(size_t)pb * H + pj] = dh_carry;
-    if (pok && d.db_part) {
-        float* q = d.db_part + (size_t)pb * 4 * H + pj;
-        q[0] = sb_r; q[H] = sb_z; q[2 * H] = sb_n; q[3 * H] = sb_nr;
-    }
-    if (stamp)
-        for (int i = 0; i < 6; ++i) ex.prof[i] = (unsigned long long)psum[i];
+#define M3T_STEP_FILE "gru_persist_bwd_step.inc"
+#include "gru_persist_ab.inc"
+    scan_drain();
+    M3T_BWD_STORE_CARRY();
+    M3T_STAMP_DUMP();
 }
 
 // ------------------------------------------------------------------------------------------------ backward, bf16x6
@@ -919,10 +517,7 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd6_kernel(BwdGroup g, FragPt
     constexpr int RT = 1, ROWS = 16, KS = NC / 2;
     constexpr int H = 128 * NC, H3 = 3 * H, nchh = H >> 4;
     __shared__ float red[2][NW][ROWS][UB + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int gid, ub;
-    if (!persist_map((int)blockIdx.x, G, ex.slot_map, gid, ub)) return;      // a block of an XCD slot that hosts no group of this launch
-    const int s = gid / nrb, rb = gid % nrb;
+    M3T_PERSIST_WHO(ub);
     const m3t_gru_bwd_desc d = g.d[s];
     const int j0 = ub * UB, r0 = rb * ROWS;
 
@@ -948,90 +543,19 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd6_kernel(BwdGroup g, FragPt
     const size_t slot = ex.slot[s];
     const size_t grp = (size_t)rb * nchh * TILE;
     const size_t pub = grp + (size_t)ub * TILE + tid;
-    bool dead = false;
-    int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
-    __shared__ unsigned poll_fail[2];                  // by step parity
-    __shared__ int pub_step;                           // steps this workgroup has published (thread 0)
-    const int l2mode = persist_handshake(ex, gid, ub, H >> 4, tid, err);     // 1: this group shares one XCD's L2 (publish with plain stores)
-    if (tid == 0) pub_step = 0;
-    if (tid < 2) poll_fail[tid] = 0;                   // first read after the first barrier
-    const bool stamp = ex.prof != nullptr && blockIdx.x == 0 && tid == ex.prof_tid;
-    long long psum[6] = {0, 0, 0, 0, 0, 0}, last = stamp ? clock64() : 0;
+    M3T_PERSIST_POLL_STATE(ub, H >> 4);
+    M3T_STAMP_STATE();
+    M3T_BWD_ENVELOPE(pb, pj);
 
-    // HBM traffic of a step and the chain.  Vector-memory operations retire in order, so everything a wave has issued
-    // before its gather loads sits in front of the gather's vmcnt(0): with the step's six result stores and the next
-    // step's three activation loads issued after the publish (the natural place), every step waited ~0.7 us for each
-    // group (tools/scan_bench.py ablation), and hipcc added a vmcnt(0) + register copies at the bottom of the step on
-    // top (2.4 of 5 us, in-kernel stamps).  Now: the results of step t are kept in registers and stored, and the
-    // activations of step t+1 are requested, right AFTER the gather of step t has completed -- they have the whole
-    // step (MFMAs, barrier, cell math, publish, the peers' latency) to retire before the next gather waits, and between
-    // the publish and the next gather a wave has nothing outstanding but the publish itself.  Two register sets (A for
-    // even steps, B for odd ones; the loop body is included twice) hold the activations; the loads are inline asm,
-    // UNCONDITIONAL (every thread, every step; lanes past the batch and the step past the end re-read a valid address):
-    // compiler-visible or conditional definitions make hipcc wait for them or merge them with copies that read
-    // registers still in flight.  A set is defined by the vmcnt(0) of the gather that precedes its use and laundered there.
-    float doutA, hprevA, doutB, hprevB;
-    f32x4 g4A, g4B;                                    // (r, z, n, W_hn h + b_hn) of this (row, unit, t)
-    const int pbc = pb < B ? pb : B - 1;
-    const float* pd0 = d.dout + (size_t)pbc * T * d.ldo + d.ooff + pj;
-    const float* pg0 = d.gates + (size_t)pbc * T * 4 * H + 4 * (size_t)pj;
-    const float* ph0 = d.out + (size_t)pbc * T * d.ldo + d.ooff + pj;
-#define M3T_BWD_LOAD_STEP(step_, DOUT, G4, HPREV)                                                                     \
-    do {                                                                                                               \
-        const int ls_ = (step_) < T ? (step_) : T - 1;                                                                 \
-        const int lt_ = d.reverse ? ls_ : T - 1 - ls_;                                                                 \
-        const int ltp_ = ls_ < T - 1 ? (d.reverse ? lt_ + 1 : lt_ - 1) : lt_;                                          \
-        asm volatile("global_load_dword %0, %3, off\n\t"                                                               \
-                     "global_load_dwordx4 %1, %4, off\n\t"                                                             \
-                     "global_load_dword %2, %5, off"                                                                   \
-                     : "=&v"(DOUT), "=&v"(G4), "=&v"(HPREV)                                                            \
-                     : "v"(pd0 + (size_t)lt_ * d.ldo), "v"(pg0 + (size_t)lt_ * 4 * H), "v"(ph0 + (size_t)ltp_ * d.ldo)  \
-                     : "memory");                                                                                      \
-    } while (0)
-    M3T_BWD_LOAD_STEP(0, doutA, g4A, hprevA);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(doutA), "+v"(g4A), "+v"(hprevA) :: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0), visible to hipcc: no wait for the weight fragments inside the loop
-    float st_dr = 0.f, st_dz = 0.f, st_dn = 0.f, st_dnr = 0.f;     // results of the previous step, stored after this step's gather
-    auto store_results = [&](int step_of) {
-        const int t = d.reverse ? step_of : T - 1 - step_of;
-        float* gx = d.dgx + ((size_t)pb * T + t) * d.ldg + d.goff;
-        gx[pj] = st_dr; gx[H + pj] = st_dz; gx[2 * H + pj] = st_dn;
-        float* gh = d.dgh + ((size_t)pb * T + t) * H3;
-        gh[pj] = st_dr; gh[H + pj] = st_dz; gh[2 * H + pj] = st_dnr;
-    };
-
-    for (int step2 = 0; step2 < T; step2 += 2) {
-#define STEPV step2
-#define CUR(x) x##A
-#define NXT(x) x##B
-#include "gru_persist_bwd6_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-        if (step2 + 1 >= T) break;
-#define STEPV (step2 + 1)
-#define CUR(x) x##B
-#define NXT(x) x##A
-#include "gru_persist_bwd6_step.inc"
-#undef STEPV
-#undef CUR
-#undef NXT
-    }
-#undef M3T_BWD_LOAD_STEP
-    // the last step's request for "the next step's inputs" is still in flight and invisible to hipcc (inline asm): a wave must
-    // not end with a load outstanding into registers that the next wave on this SIMD is about to own
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (pok) d.dh[(size_t)pb * H + pj] = dh_carry;
-    if (pok && d.db_part) {
-        float* q = d.db_part + (size_t)pb * 4 * H + pj;
-        q[0] = sb_r; q[H] = sb_z; q[2 * H] = sb_n; q[3 * H] = sb_nr;
-    }
+#define M3T_STEP_FILE "gru_persist_bwd6_step.inc"
+#include "gru_persist_ab.inc"
+    scan_drain();
+    M3T_BWD_STORE_CARRY();
     if (d.amax && pw) {                                // (waves 0..3: uniform per wave)
         const float m = wave_max(pok ? amx : 0.f);
         if (lane == 0) atomicMax(d.amax, (unsigned long long)__float_as_uint(m));
     }
-    if (stamp)
-        for (int i = 0; i < 6; ++i) ex.prof[i] = (unsigned long long)psum[i];
+    M3T_STAMP_DUMP();
 }
 
 // ---- producer-side operand split (gru_persist_bwd3q_kernel below; its narrow predecessor gru_persist_bwd3p_kernel of round 3 was removed in round 5:
@@ -1142,10 +666,7 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
     static_assert(RB == 16 || (RB == 8 && !PROF), "row blocks: 16 clips, or 8 (the gather deals the units over lane bit 3 for 8 rows)");
     constexpr int H = 128 * NC, H3 = 3 * H, nchh = H >> 4;
     __shared__ float red[2][NW][2][ROWS][UB + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int gid, ubw;
-    if (!persist_map((int)blockIdx.x, G, ex.slot_map, gid, ubw)) return;      // a block of an XCD slot that hosts no group of this launch
-    const int s = gid / nrb, rb = gid % nrb;
+    M3T_PERSIST_WHO(ubw);
     const m3t_gru_bwd_desc d = g.d[s];
     const int tu = tid >> 8;                           // the unit tile this thread does cell math for
     const int ub = ubw * 2 + tu;
@@ -1189,7 +710,7 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
     // (RB = 8: row lane & 7, and lane bit 3 picks the odd unit e, 32 granules on)
     const size_t lane_src = RB < ROWS ? (size_t)(2 * wave + (lane >> 5)) * TILE + ((lane >> 4) & 1) * 16 + (lane & 7) + 32 * ((lane >> 3) & 1)
                                       : (size_t)(2 * wave + (lane >> 5)) * TILE + ((lane >> 4) & 1) * 16 + (lane & 15);
-    bool dead = false;
+    bool dead = false;                                 // M3T_PERSIST_POLL_STATE without pub_step: every wave of this kernel does cell math
     int poll_delay = ex.poll_fixed >= 0 ? ex.poll_fixed : POLL_DELAY_INIT;
     __shared__ unsigned poll_fail[2];                  // by step parity
     const int l2mode = persist_handshake(ex, gid, ubw, (H >> 4) / 2, tid, err);     // 1: this group shares one XCD's L2 (publish with plain stores)
@@ -1206,8 +727,6 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
 
     // activations: loaded one step ahead by inline asm in MEMORY order (thread ti: row ti >> 4, unit ti & 15 of its tile), handed to the
     // cell threads through LDS; results the other way, stored one step late
-    float doutA, hprevA, doutB, hprevB;
-    f32x4 g4A, g4B;                                    // (r, z, n, W_hn h + b_hn) of this (row, unit, t)
     const int hrow = ti >> 4, hun = ti & 15;
     const int hb = r0 + hrow, hj = j0 + hun;
     const bool hok = hrow < RB && hb < B;
@@ -1218,70 +737,18 @@ __global__ __launch_bounds__(NT) void gru_persist_bwd3q_kernel(BwdGroup g, FragP
     f32x4* const sin4 = reinterpret_cast<f32x4*>(stage_raw);                  // [parity][2][SLOTS] gate records
     f32x4* const sout = sin4 + 2 * 2 * SLOTS;                                 // [parity][2][SLOTS] (dr~, dz~, dn~, dn~ r)
     float2* const sin2 = reinterpret_cast<float2*>(sout + 2 * 2 * SLOTS);     // [parity][2][SLOTS] (dout, h_prev)
-    const int pbc = hb < B ? hb : B - 1;
-    const float* pd0 = d.dout + (size_t)pbc * T * d.ldo + d.ooff + hj;
-    const float* pg0 = d.gates + (size_t)pbc * T * 4 * H + 4 * (size_t)hj;
-    const float* ph0 = d.out + (size_t)pbc * T * d.ldo + d.ooff + hj;
-#define M3T_BWD_LOAD_STEP(step_, DOUT, G4, HPREV)                                                                     \
-    do {                                                                                                               \
-        const int ls_ = (step_) < T ? (step_) : T - 1;                                                                 \
-        const int lt_ = d.reverse ? ls_ : T - 1 - ls_;                                                                 \
-        const int ltp_ = ls_ < T - 1 ? (d.reverse ? lt_ + 1 : lt_ - 1) : lt_;                                          \
-        asm volatile("global_load_dword %0, %3, off\n\t"                                                               \
-                     "global_load_dwordx4 %1, %4, off\n\t"                                                             \
-                     "global_load_dword %2, %5, off"                                                                   \
-                     : "=&v"(DOUT), "=&v"(G4), "=&v"(HPREV)                                                            \
-                     : "v"(pd0 + (size_t)lt_ * d.ldo), "v"(pg0 + (size_t)lt_ * 4 * H), "v"(ph0 + (size_t)ltp_ * d.ldo)  \
-                     : "memory");                                                                                      \
-    } while (0)
-    M3T_BWD_LOAD_STEP(0, doutA, g4A, hprevA);
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(doutA), "+v"(g4A), "+v"(hprevA) :: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0), visible to hipcc: no wait for the weight fragments inside the loop
-    float st_dr = 0.f, st_dz = 0.f, st_dn = 0.f, st_dnr = 0.f;     // results of the cell this thread stores for
-    auto store_results = [&](int step_of) {
-        const int t = d.reverse ? step_of : T - 1 - step_of;
-        float* gx = d.dgx + ((size_t)hb * T + t) * d.ldg + d.goff;
-        gx[hj] = st_dr; gx[H + hj] = st_dz; gx[2 * H + hj] = st_dn;
-        float* gh = d.dgh + ((size_t)hb * T + t) * H3;
-        gh[hj] = st_dr; gh[H + hj] = st_dz; gh[2 * H + hj] = st_dnr;
-    };
+    M3T_BWD_ENVELOPE(hb, hj);                         // st_*: the results of the cell this thread stores for
 
-    for (int step2 = 0; step2 < T; step2 += 2) {
-#define STEPV step2
-#define PARV 0
-#define CUR(x) x##A
-#define NXT(x) x##B
-#include "gru_persist_bwd3q_step.inc"
-#undef STEPV
-#undef PARV
-#undef CUR
-#undef NXT
-        if (step2 + 1 >= T) break;
-#define STEPV (step2 + 1)
-#define PARV 1
-#define CUR(x) x##B
-#define NXT(x) x##A
-#include "gru_persist_bwd3q_step.inc"
-#undef STEPV
-#undef PARV
-#undef CUR
-#undef NXT
-    }
-#undef M3T_BWD_LOAD_STEP
-    // the last step's request for "the next step's inputs" is still in flight and invisible to hipcc (inline asm): a wave must
-    // not end with a load outstanding into registers that the next wave on this SIMD is about to own
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#define M3T_STEP_FILE "gru_persist_bwd3q_step.inc"
+#include "gru_persist_ab.inc"
+    scan_drain();
     __syncthreads();                                   // the last step's results are still in LDS
     if (hok) {
         const f32x4 r4 = sout[((T - 1) & 1) * 2 * SLOTS + slot_h];
         st_dr = r4[0]; st_dz = r4[1]; st_dn = r4[2]; st_dnr = r4[3];
         store_results(T - 1);
     }
-    if (pok) d.dh[(size_t)pb * H + pj] = dh_carry;
-    if (pok && d.db_part) {
-        float* q = d.db_part + (size_t)pb * 4 * H + pj;
-        q[0] = sb_r; q[H] = sb_z; q[2 * H] = sb_n; q[3 * H] = sb_nr;
-    }
+    M3T_BWD_STORE_CARRY();
     if (d.amax) {
         const float m = wave_max(pok ? amx : 0.f);
         if (lane == 0) {
@@ -1419,6 +886,27 @@ static size_t exclusive_lds(K kernel, int grid, size_t need = 0) {
         return 0;
     }
     return dyn;
+}
+
+// The scan kernel of a level, behind whatever the level prepared (fragments, exchange): the stream first waits for the caller's event
+// (m3t_gru_scan_after: the preparation kernels and memsets in front are not held back), the caller's event pair (m3t_gru_scan_events) is
+// recorded right around the kernel, and the launch owns its CUs (exclusive_lds).  need: the dynamic LDS the kernel itself uses.
+template <typename K, typename Grp>
+static int launch_scan(K kernel, const Shape& sh, size_t need, const Grp& g, const FragPtrs& fp, const ExPtrs& ex, int B, int T, hipStream_t s) {
+    { const int e = persist_take_after(s); if (e) return e; }
+    persist_record_start(s);
+    const size_t dyn = exclusive_lds(kernel, sh.active, need);
+    if (dyn < need) return M3T_EINVAL;
+    hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(NT), dyn, s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
+    persist_record_end(s);
+    M3T_LAUNCH_CHECK();
+    return 0;
+}
+
+// grid of a grid-stride fragment prep kernel: one thread per weight of W_hh [3H][H], at most 1024 blocks
+static int prep_blocks(int H) {
+    const int blk = (3 * H * H + 255) / 256;
+    return blk > 1024 ? 1024 : blk;
 }
 
 // ---- exchange arena: tags that are unique per launch instead of a memset per launch ---------------------------------------
@@ -1871,7 +1359,6 @@ static int persist_fwd_launch_impl(const FwdGroup& g, const FragPtrs& fp, int B,
     }
     { const int e = prepare_exchange(g, fp, sh, x6 ? 1 : 0, 8, x6 ? 65535ull : 0xffffffffull, T, ex, s); if (e) return e; }
     ++g_launches;
-    if (!x6) { const int e = persist_take_after(s); if (e) return e; }
     if (x6) {
         // fp32 mode with M3T_GEMM_F16X3: the product from two fp16 terms (three MFMAs per k-step and gate) instead of three bf16 terms (six)
         const bool f16 = !g.bf16 && (flags & M3T_GEMM_F16X3) && m3t_f16x3_enabled();
@@ -1891,41 +1378,22 @@ static int persist_fwd_launch_impl(const FwdGroup& g, const FragPtrs& fp, int B,
         }
         for (int i = 0; i < g.n && !f16; ++i) {
             const int H = g.d[i].H;
-            int blk = (3 * H * H + 255) / 256;
-            if (blk > 1024) blk = 1024;
-            wfrag6_prep_kernel<<<blk, 256, 0, s>>>(g.d[i].w_hh, reinterpret_cast<unsigned short*>(fp.wfrag[i]), H, g.bf16);
+            wfrag6_prep_kernel<<<prep_blocks(H), 256, 0, s>>>(g.d[i].w_hh, reinterpret_cast<unsigned short*>(fp.wfrag[i]), H, g.bf16);
         }
         M3T_LAUNCH_CHECK();
-        { const int e = persist_take_after(s); if (e) return e; }
-        persist_record_start(s);
-        if (f16) {
-            if (uw == 2) {
-                const size_t need = (size_t)2 * NW * 2 * 3 * 16 * (UB + 1) * sizeof(float)           // the kernel's partial sums (RED_FLOATS)
-                                    + (size_t)2 * 2 * 272 * 36;                                      // + the staging slots (sx, so, sh)
-                const FwdKernel kk = sh.rb == 8 ? (sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 2, 8> : gru_persist_fwd6_kernel<4, true, 2, 8>)
-                                                : (sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 2> : gru_persist_fwd6_kernel<4, true, 2>);
-                const size_t dyn = exclusive_lds(kk, sh.active, need);
-                if (dyn < need) return M3T_EINVAL;
-                hipLaunchKernelGGL(kk, dim3(sh.grid), dim3(NT), dyn, s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-            }
-            else if (sh.rb == 8) {
-                const FwdKernel kk = sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 1, 8> : gru_persist_fwd6_kernel<4, true, 1, 8>;
-                hipLaunchKernelGGL(kk, dim3(sh.grid), dim3(NT), exclusive_lds(kk, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-            }
-            else if (sh.nc == 2) hipLaunchKernelGGL((gru_persist_fwd6_kernel<2, true>), dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_fwd6_kernel<2, true>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-            else hipLaunchKernelGGL((gru_persist_fwd6_kernel<4, true>), dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_fwd6_kernel<4, true>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
+        if (f16 && uw == 2) {
+            const size_t need = (size_t)2 * NW * 2 * 3 * 16 * (UB + 1) * sizeof(float)           // the kernel's partial sums (RED_FLOATS)
+                                + (size_t)2 * 2 * 272 * 36;                                      // + the staging slots (sx, so, sh)
+            return launch_scan(sh.rb == 8 ? (sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 2, 8> : gru_persist_fwd6_kernel<4, true, 2, 8>)
+                                          : (sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 2> : gru_persist_fwd6_kernel<4, true, 2>),
+                               sh, need, g, fp, ex, B, T, s);
         }
-        else if (sh.nc == 2) hipLaunchKernelGGL(gru_persist_fwd6_kernel<2>, dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_fwd6_kernel<2>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-        else hipLaunchKernelGGL(gru_persist_fwd6_kernel<4>, dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_fwd6_kernel<4>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-        persist_record_end(s);
-        M3T_LAUNCH_CHECK();
-        return 0;
+        if (f16 && sh.rb == 8)
+            return launch_scan(sh.nc == 2 ? gru_persist_fwd6_kernel<2, true, 1, 8> : gru_persist_fwd6_kernel<4, true, 1, 8>, sh, 0, g, fp, ex, B, T, s);
+        if (f16) return launch_scan(sh.nc == 2 ? gru_persist_fwd6_kernel<2, true> : gru_persist_fwd6_kernel<4, true>, sh, 0, g, fp, ex, B, T, s);
+        return launch_scan(sh.nc == 2 ? gru_persist_fwd6_kernel<2> : gru_persist_fwd6_kernel<4>, sh, 0, g, fp, ex, B, T, s);
     }
-    persist_record_start(s);
-    hipLaunchKernelGGL(pick_fwd(sh), dim3(sh.grid), dim3(NT), exclusive_lds(pick_fwd(sh), sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-    persist_record_end(s);
-    M3T_LAUNCH_CHECK();
-    return 0;
+    return launch_scan(pick_fwd(sh), sh, 0, g, fp, ex, B, T, s);
 }
 
 // M3T_SCAN_BWD3P=0: the six-product backward scan (consumer-side split) for the H = 512 / 256 levels also in the fp16x3 mode, instead of the
@@ -1978,80 +1446,46 @@ static int persist_bwd_launch_impl(const BwdGroup& g, const FragPtrs& fp, int B,
     }
     { const int e = prepare_exchange(g, fp, sh, b16 ? 2 : 3, b16 ? 8 : 16, b16 ? 65535ull : (p3 ? 0xffffffull : 0xffffffffull), T, ex, s, p3 ? 1 : 0); if (e) return e; }
     ++g_launches;
-    if (p3) {
-        PrepBwd3pArgs pa;
+    if (p3) {                                                                // (p3 implies uw == 2) the wide form: 32-deep MFMAs over producer pairs, memory-order hand-over
         const int H = g.d[0].H;                                               // (level_shape: one H per level)
-        for (int i = 0; i < M3T_MAX_SCANS; ++i) {
-            const int j = i < g.n ? i : 0;
-            pa.w[i] = g.d[j].w_hh_t; pa.wf[i] = reinterpret_cast<unsigned short*>(fp.wfrag[j]); pa.inv[i] = fp.wfrag[j] + (size_t)4 * H * H;
-        }
-        if (uw == 2) {                                                       // the wide form: 32-deep MFMAs over producer pairs, memory-order hand-over
-            bool ready = true;                                               // round 5: fragments prepared ahead of time (m3t_gru_bwd_prepare)
-            for (int i = 0; i < g.n; ++i) ready = ready && g.d[i].wfrag != nullptr && ((uintptr_t)g.d[i].wfrag % 16) == 0;
-            FragPtrs fq = fp;
-            if (ready) {
-                for (int i = 0; i < g.n; ++i) fq.wfrag[i] = const_cast<float*>(g.d[i].wfrag);
-            } else {
-                wfrag_bwd3q_prep_kernel<<<dim3(H / 16, PREP3H_SPLIT, g.n), 256, 0, s>>>(pa, H, (flags & M3T_SCAN_WHH) ? 1 : 0);
-                M3T_LAUNCH_CHECK();
+        bool ready = true;                                                   // round 5: fragments prepared ahead of time (m3t_gru_bwd_prepare)
+        for (int i = 0; i < g.n; ++i) ready = ready && g.d[i].wfrag != nullptr && ((uintptr_t)g.d[i].wfrag % 16) == 0;
+        FragPtrs fq = fp;
+        if (ready) {
+            for (int i = 0; i < g.n; ++i) fq.wfrag[i] = const_cast<float*>(g.d[i].wfrag);
+        } else {
+            PrepBwd3pArgs pa;
+            for (int i = 0; i < M3T_MAX_SCANS; ++i) {
+                const int j = i < g.n ? i : 0;
+                pa.w[i] = g.d[j].w_hh_t; pa.wf[i] = reinterpret_cast<unsigned short*>(fp.wfrag[j]); pa.inv[i] = fp.wfrag[j] + (size_t)4 * H * H;
             }
-            { const int e = persist_take_after(s); if (e) return e; }
-            persist_record_start(s);
-            const BwdKernel kq = sh.rb == 8 ? (sh.nc == 2 ? gru_persist_bwd3q_kernel<2, false, 8> : gru_persist_bwd3q_kernel<4, false, 8>)
-                                 : sh.nc == 2 ? gru_persist_bwd3q_kernel<2> : (ex.prof ? gru_persist_bwd3q_kernel<4, true> : gru_persist_bwd3q_kernel<4>);
-            const size_t need = (size_t)2 * 2 * 272 * 40;                    // the staging slots (sin4, sout, sin2)
-            const size_t dyn = exclusive_lds(kq, sh.active, need);
-            if (dyn < need) return M3T_EINVAL;
-            hipLaunchKernelGGL(kq, dim3(sh.grid), dim3(NT), dyn, s, g, fq, ex, B, T, sh.G, sh.nrb, g_err_dev);
-            persist_record_end(s);
+            wfrag_bwd3q_prep_kernel<<<dim3(H / 16, PREP3H_SPLIT, g.n), 256, 0, s>>>(pa, H, (flags & M3T_SCAN_WHH) ? 1 : 0);
             M3T_LAUNCH_CHECK();
-            return 0;
         }
-        return M3T_EINVAL;      // (unreachable: p3 implies the wide form since round 5)
+        const BwdKernel kq = sh.rb == 8 ? (sh.nc == 2 ? gru_persist_bwd3q_kernel<2, false, 8> : gru_persist_bwd3q_kernel<4, false, 8>)
+                             : sh.nc == 2 ? gru_persist_bwd3q_kernel<2> : (ex.prof ? gru_persist_bwd3q_kernel<4, true> : gru_persist_bwd3q_kernel<4>);
+        return launch_scan(kq, sh, (size_t)2 * 2 * 272 * 40, g, fq, ex, B, T, s);      // need: the staging slots (sin4, sout, sin2)
     }
     if (b16) {
         for (int i = 0; i < g.n; ++i) {                                      // W_hh^T -> bf16 B-operand fragments
             const int H = g.d[i].H;
-            int blk = (3 * H * H + 255) / 256;
-            if (blk > 1024) blk = 1024;
-            wfrag_bwd16_prep_kernel<<<blk, 256, 0, s>>>(g.d[i].w_hh_t, reinterpret_cast<unsigned short*>(fp.wfrag[i]), H, (flags & M3T_SCAN_WHH) ? 1 : 0);
+            wfrag_bwd16_prep_kernel<<<prep_blocks(H), 256, 0, s>>>(g.d[i].w_hh_t, reinterpret_cast<unsigned short*>(fp.wfrag[i]), H, (flags & M3T_SCAN_WHH) ? 1 : 0);
         }
         M3T_LAUNCH_CHECK();
-        { const int e = persist_take_after(s); if (e) return e; }
-        persist_record_start(s);
-        if (sh.nc == 2) hipLaunchKernelGGL(gru_persist_bwd16_kernel<2>, dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_bwd16_kernel<2>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-        else hipLaunchKernelGGL(gru_persist_bwd16_kernel<4>, dim3(sh.grid), dim3(NT), exclusive_lds(gru_persist_bwd16_kernel<4>, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-        persist_record_end(s);
-        M3T_LAUNCH_CHECK();
-        return 0;
+        return launch_scan(sh.nc == 2 ? gru_persist_bwd16_kernel<2> : gru_persist_bwd16_kernel<4>, sh, 0, g, fp, ex, B, T, s);
     }
     if (persist_bwd_uses_x6(g, B, T, flags)) {
-        {                                                                     // W_hh -> bf16x3 B-operand fragments, every scan of the level
-            PrepBwd6Args pa;
-            const int H = g.d[0].H;                                           // (level_shape: one H per level)
-            for (int i = 0; i < M3T_MAX_SCANS; ++i) {
-                const int j = i < g.n ? i : 0;
-                pa.w[i] = g.d[j].w_hh_t; pa.wf[i] = reinterpret_cast<unsigned short*>(fp.wfrag[j]);
-            }
-            int blk = (3 * H * H + 255) / 256;
-            if (blk > 1024) blk = 1024;
-            wfrag_bwd6_prep_kernel<<<dim3(blk, g.n), 256, 0, s>>>(pa, H, (flags & M3T_SCAN_WHH) ? 1 : 0);
+        PrepBwd6Args pa;                                                      // W_hh -> bf16x3 B-operand fragments, every scan of the level
+        const int H = g.d[0].H;                                               // (level_shape: one H per level)
+        for (int i = 0; i < M3T_MAX_SCANS; ++i) {
+            const int j = i < g.n ? i : 0;
+            pa.w[i] = g.d[j].w_hh_t; pa.wf[i] = reinterpret_cast<unsigned short*>(fp.wfrag[j]);
         }
+        wfrag_bwd6_prep_kernel<<<dim3(prep_blocks(H), g.n), 256, 0, s>>>(pa, H, (flags & M3T_SCAN_WHH) ? 1 : 0);
         M3T_LAUNCH_CHECK();
-        { const int e = persist_take_after(s); if (e) return e; }
-        persist_record_start(s);
-        const BwdKernel kk = sh.nc == 2 ? gru_persist_bwd6_kernel<2> : gru_persist_bwd6_kernel<4>;
-        hipLaunchKernelGGL(kk, dim3(sh.grid), dim3(NT), exclusive_lds(kk, sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-        persist_record_end(s);
-        M3T_LAUNCH_CHECK();
-        return 0;
+        return launch_scan(sh.nc == 2 ? gru_persist_bwd6_kernel<2> : gru_persist_bwd6_kernel<4>, sh, 0, g, fp, ex, B, T, s);
     }
-    { const int e = persist_take_after(s); if (e) return e; }
-    persist_record_start(s);
-    hipLaunchKernelGGL(pick_bwd(sh), dim3(sh.grid), dim3(NT), exclusive_lds(pick_bwd(sh), sh.active), s, g, fp, ex, B, T, sh.G, sh.nrb, g_err_dev);
-    persist_record_end(s);
-    M3T_LAUNCH_CHECK();
-    return 0;
+    return launch_scan(pick_bwd(sh), sh, 0, g, fp, ex, B, T, s);
 }
 
 static thread_local hipEvent_t g_ev_start = nullptr, g_ev_end = nullptr;

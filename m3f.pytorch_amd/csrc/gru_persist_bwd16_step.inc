@@ -9,11 +9,7 @@
         const unsigned long long* src = gran + (size_t)((step - 1) & 1) * slot + grp + lane_off;
         pu32x4 v[KS][4];                               // [k-step][unit pair jp] = {lo(j0), hi(j0), lo(j1), hi(j1)}
         int spins = 0;
-        if (!pw && (ex.poll_align & 1)) {              // waves without cell math arrive a cell phase early: count the delay from
-            int w = 0;                                 // the workgroup's own publish (thread 0's mark in LDS) for them too
-            while (__hip_atomic_load(&pub_step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < step && ++w < ex.spin_limit) __builtin_amdgcn_s_sleep(1);
-        }
-        for (int z = 0; z < poll_delay; ++z) __builtin_amdgcn_s_sleep(1);      // see poll_delay in the kernel
+        M3T_GATHER_DELAY(step);
         for (;;) {
 #pragma unroll
             for (int k = 0; k < KS; ++k) {
@@ -34,11 +30,9 @@
                     asm volatile("" : "+v"(v[k][jp]));
                     ok = ok && ((v[k][jp].y >> 16) == tag) && ((v[k][jp].w >> 16) == tag);
                 }
-            if (__all(ok) || dead) break;
-            if (++spins > ex.spin_limit) { dead = true; if (lane == 0) raise_spin(err, step); break; }
-            __builtin_amdgcn_s_sleep(1);
+            M3T_GATHER_RETRY(ok, step);
         }
-        if (spins > 0 && lane == 0) atomicOr(&poll_fail[step & 1], 1u);
+        gather_note_fail(spins, lane, &poll_fail[step & 1]);
         // this step's activations (requested one step ago) are complete since the vmcnt(0) above
         asm volatile("" : "+v"(CUR(dout)), "+v"(CUR(g4)), "+v"(CUR(hprev)));
         M3T_STAMP(1);
@@ -59,19 +53,13 @@
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[step & 1][wave][(lane >> 4) * 4 + r][lane & 15] = acc[r];
     }
-    // nothing is outstanding here on either path (the gather ended with this very wait; step 0 had the prologue's): stated
-    // again so that EVERY path to the cell phase passes a vmcnt(0) behind the previous step's requests (tools/check_inflight.py)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    cell_phase_wait();
     // every step, unconditionally (a conditional definition gets merged by copies that read registers in flight): with
     // nothing else outstanding, request the next step's activations -- a whole step to arrive
     M3T_BWD_LOAD_STEP(step + 1, NXT(dout), NXT(g4), NXT(hprev));
     M3T_STAMP(2);
     __syncthreads();
-    if (ex.poll_fixed < 0) {                       // adaptive poll delay, one value per workgroup: see poll_delay in the kernel
-        const bool wg_failed = poll_fail[step & 1] != 0;
-        if (tid == 0) poll_fail[(step + 1) & 1] = 0;        // next written after the next gather; last read before this barrier
-        poll_delay = wg_failed ? min(poll_delay + 2, POLL_DELAY_MAX) : ((step & 7) == 0 && poll_delay > 0 ? poll_delay - 1 : poll_delay);
-    }
+    M3T_POLL_ADAPT(step & 1, (step + 1) & 1, step);
     M3T_STAMP(3);
     if (pw) {
         float mm = 0.f;
@@ -81,15 +69,13 @@
         }
         const float gr = CUR(g4).x, gz = CUR(g4).y, gn = CUR(g4).z, ghn = CUR(g4).w;
         const GateBwd c = gru_cell_bwd(CUR(dout), dh_carry, z_next, mm, has_next, gr, gz, gn, ghn, step < T - 1 ? CUR(hprev) : 0.f);
-        if (step + 1 < T && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)                            // 8-byte granule {bf16 dr, bf16 dz, bf16 dn*r, tag16}: the values ARE bf16 in this mode
+        if (M3T_SCAN_PUBLISHES(step, true)) {             // 8-byte granule {bf16 dr, bf16 dz, bf16 dn*r, tag16}: the values ARE bf16 in this mode
             const unsigned lo = (__float_as_uint(pok ? rbf(c.dr) : 0.f) >> 16) | (__float_as_uint(pok ? rbf(c.dz) : 0.f) & 0xffff0000u);
             const unsigned hi = (__float_as_uint(pok ? rbf(c.dnr) : 0.f) >> 16) | (((ex.tag_base + (unsigned)step + 1u) & 0xffffu) << 16);
             const unsigned long long gq = ((unsigned long long)hi << 32) | lo;
-            unsigned long long* q = gran + (size_t)(step & 1) * slot + pub;
-            if (l2mode) asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(q), "v"(gq) : "memory");          // the group shares one XCD: the line stays in its L2
-            else asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(q), "v"(gq) : "memory");
+            M3T_PUBLISH8(gran + (size_t)(step & 1) * slot + pub, gq);
         }
-        if (tid == 0) __hip_atomic_store(&pub_step, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // the other waves' poll delay counts from here
+        M3T_MARK_PUBLISHED(step);
         M3T_STAMP(4);
         dh_carry = c.dht; z_next = gz;
         sb_r += c.dr; sb_z += c.dz; sb_n += c.dn; sb_nr += c.dnr;

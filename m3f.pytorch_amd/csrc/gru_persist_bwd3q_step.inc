@@ -12,7 +12,7 @@
         const u32x4* src = gran + (size_t)(1 - PARV) * slot + grp + lane_src;
         u32x4 v[NP][8];                                // [pair of this wave's K-slice][unit e of this lane's 8]: {hi|lo dr, hi|lo dz, hi|lo dnr, tag24|exp}
         int spins = 0;
-        for (int z = 0; z < poll_delay; ++z) __builtin_amdgcn_s_sleep(1);      // see poll_delay in gru_persist.hip
+        M3T_POLL_SLEEP();                              // (M3T_GATHER_DELAY without the wait for pub_step: no wave of this kernel arrives early)
         for (;;) {
 #pragma unroll
             for (int m = 0; m < NP; ++m) {
@@ -47,11 +47,9 @@
                     asm volatile("" : "+v"(v[m][e]));              // defined only after the wait above
                     ok = ok && ((v[m][e].w & 0xffffffu) == tag);
                 }
-            if (__all(ok) || dead) break;
-            if (++spins > ex.spin_limit) { dead = true; if (lane == 0) raise_spin(err, step); break; }
-            __builtin_amdgcn_s_sleep(1);
+            M3T_GATHER_RETRY(ok, step);
         }
-        if (spins > 0 && lane == 0) atomicOr(&poll_fail[PARV], 1u);       // any wave's failed first attempt counts for the workgroup
+        gather_note_fail(spins, lane, &poll_fail[PARV]);
         M3T_QSTAMP(1);
         // per pair m: this lane holds the granules of its 8 consecutive k (units 8 (q&1) + e of tile q>>1): dword g of a granule =
         // (hi | lo << 16) of gate g -- four v_perm pack the eight hi (lo) terms into the A operand of a 32-deep fp16 MFMA; three MFMAs per
@@ -99,9 +97,7 @@
 #pragma unroll
             for (int r = 0; r < 4; ++r) red[PARV][wave][u][(lane >> 4) * 4 + r][lane & 15] = acc[u][r] * winv[u];
     }
-    // nothing is outstanding here on either path (the gather ended with this very wait; step 0 had the prologue's): stated
-    // again so that EVERY path to the cell phase passes a vmcnt(0) behind the previous step's requests (tools/check_inflight.py)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    cell_phase_wait();
     // this step's activations (requested one step ago), loaded in memory order: to the cell threads through LDS.  ONE place, behind the
     // unconditional wait: defined on two paths (inside and outside the gather branch) hipcc merged them with copies that read the
     // registers while the loads were still in flight (tools/check_inflight.py caught it)
@@ -114,11 +110,7 @@
     M3T_QSTAMP(2);
     __syncthreads();
     M3T_MARK_AFTER_BARRIER(step);
-    if (ex.poll_fixed < 0) {                       // adaptive poll delay, one value per workgroup: see poll_delay in gru_persist.hip
-        const bool wg_failed = poll_fail[PARV] != 0;
-        if (tid == 0) poll_fail[(1 - PARV)] = 0;        // next written after the next gather; last read before this barrier
-        poll_delay = wg_failed ? min(poll_delay + 2, POLL_DELAY_MAX) : ((step & 7) == 0 && poll_delay > 0 ? poll_delay - 1 : poll_delay);
-    }
+    M3T_POLL_ADAPT(PARV, 1 - PARV, step);
     M3T_QSTAMP(3);
     {
         float mm = 0.f;
@@ -155,13 +147,11 @@
         }
         float psc, pisc;
         m3t_f16_scale(mxb, psc, pisc);
-        if (step + 1 < T && (RB == ROWS || plive) && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)
+        if (M3T_SCAN_PUBLISHES(step, RB == ROWS || plive)) {      // (rows past an 8-clip block publish nothing)
             u32x4 gq;
             gq.x = bwd3p_split(p0 * psc); gq.y = bwd3p_split(p1 * psc); gq.z = bwd3p_split(p2 * psc);
             gq.w = ((ex.tag_base + (unsigned)step + 1u) & 0xffffffu) | ((__float_as_uint(psc) >> 23) << 24);
-            u32x4* q = gran + (size_t)PARV * slot + pub;
-            if (l2mode) asm volatile("global_store_dwordx4 %0, %1, off" :: "v"(q), "v"(gq) : "memory");          // the group shares one XCD: the line stays in its L2
-            else asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(q), "v"(gq) : "memory");
+            M3T_PUBLISH16(gran + (size_t)PARV * slot + pub, gq);
         }
         M3T_QSTAMP(4);
         dh_carry = c.dht; z_next = gz;

@@ -10,11 +10,7 @@
         const u32x4* src = gran + (size_t)((step - 1) & 1) * slot + grp + (size_t)wave * TILE + lane;
         u32x4 v[NC][RT][4];
         int spins = 0;
-        if (!pw && (ex.poll_align & 1)) {              // waves without cell math arrive a cell phase early: count the delay from
-            int w = 0;                                 // the workgroup's own publish (thread 0's mark in LDS) for them too
-            while (__hip_atomic_load(&pub_step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < step && ++w < ex.spin_limit) __builtin_amdgcn_s_sleep(1);
-        }
-        for (int z = 0; z < poll_delay; ++z) __builtin_amdgcn_s_sleep(1);      // see poll_delay in the kernel
+        M3T_GATHER_DELAY(step);
         for (;;) {
 #pragma unroll
             for (int m = 0; m < NC; ++m)
@@ -39,11 +35,9 @@
                         asm volatile("" : "+v"(v[m][rt][e]));          // defined only after the wait above
                         ok = ok && (v[m][rt][e].w == tag);
                     }
-            if (__all(ok) || dead) break;
-            if (++spins > ex.spin_limit) { dead = true; if (lane == 0) raise_spin(err, step); break; }
-            __builtin_amdgcn_s_sleep(1);
+            M3T_GATHER_RETRY(ok, step);
         }
-        if (spins > 0 && lane == 0) atomicOr(&poll_fail[step & 1], 1u);       // any wave's failed first attempt counts for the workgroup
+        gather_note_fail(spins, lane, &poll_fail[step & 1]);
         // this step's activations (requested one step ago) are complete since the vmcnt(0) above
         asm volatile("" : "+v"(CUR(dout)), "+v"(CUR(g4)), "+v"(CUR(hprev)));
         M3T_STAMP(1);
@@ -76,19 +70,13 @@
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[step & 1][wave][(lane >> 4) * 4 + r][lane & 15] = acc[r];
     }
-    // nothing is outstanding here on either path (the gather ended with this very wait; step 0 had the prologue's): stated
-    // again so that EVERY path to the cell phase passes a vmcnt(0) behind the previous step's requests (tools/check_inflight.py)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    cell_phase_wait();
     // every step, unconditionally (a conditional definition gets merged by copies that read registers in flight): with
     // nothing else outstanding, request the next step's activations -- a whole step to arrive
     M3T_BWD_LOAD_STEP(step + 1, NXT(dout), NXT(g4), NXT(hprev));
     M3T_STAMP(2);
     __syncthreads();
-    if (ex.poll_fixed < 0) {                       // adaptive poll delay, one value per workgroup: see poll_delay in the kernel
-        const bool wg_failed = poll_fail[step & 1] != 0;
-        if (tid == 0) poll_fail[(step + 1) & 1] = 0;        // next written after the next gather; last read before this barrier
-        poll_delay = wg_failed ? min(poll_delay + 2, POLL_DELAY_MAX) : ((step & 7) == 0 && poll_delay > 0 ? poll_delay - 1 : poll_delay);
-    }
+    M3T_POLL_ADAPT(step & 1, (step + 1) & 1, step);
     M3T_STAMP(3);
     if (pw) {
         float mm = 0.f;
@@ -98,16 +86,14 @@
         }
         const float gr = CUR(g4).x, gz = CUR(g4).y, gn = CUR(g4).z, ghn = CUR(g4).w;
         const GateBwd c = gru_cell_bwd(CUR(dout), dh_carry, z_next, mm, has_next, gr, gz, gn, ghn, step < T - 1 ? CUR(hprev) : 0.f);
-        if (step + 1 < T && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)
+        if (M3T_SCAN_PUBLISHES(step, true)) {             // 16-byte granule {dr, dz, dn*r, tag32}
             u32x4 gq;
             const bool bf = g.bf16 != 0;
             gq.x = __float_as_uint(pok ? (bf ? rbf(c.dr) : c.dr) : 0.f); gq.y = __float_as_uint(pok ? (bf ? rbf(c.dz) : c.dz) : 0.f);
             gq.z = __float_as_uint(pok ? (bf ? rbf(c.dnr) : c.dnr) : 0.f); gq.w = ex.tag_base + (unsigned)step + 1u;
-            u32x4* q = gran + (size_t)(step & 1) * slot + pub;
-            if (l2mode) asm volatile("global_store_dwordx4 %0, %1, off" :: "v"(q), "v"(gq) : "memory");          // the group shares one XCD: the line stays in its L2
-            else asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(q), "v"(gq) : "memory");
+            M3T_PUBLISH16(gran + (size_t)(step & 1) * slot + pub, gq);
         }
-        if (tid == 0) __hip_atomic_store(&pub_step, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // the other waves' poll delay counts from here
+        M3T_MARK_PUBLISHED(step);
         M3T_STAMP(4);
         dh_carry = c.dht; z_next = gz;
         sb_r += c.dr; sb_z += c.dz; sb_n += c.dn; sb_nr += c.dnr;

@@ -10,11 +10,7 @@
             const unsigned long long* src = gran + (size_t)(1 - PARV) * slot + grp + lane_off;
             pu32x4 v[KS][4];                               // [k-step][unit pair jp] = {lo(j0), hi(j0), lo(j1), hi(j1)}
             int spins = 0;
-            if (!pw && (ex.poll_align & 1)) {              // waves without cell math arrive a cell phase early: count the delay from
-                int w = 0;                                 // the workgroup's own publish (thread 0's mark in LDS) for them too
-                while (__hip_atomic_load(&pub_step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < step && ++w < ex.spin_limit) __builtin_amdgcn_s_sleep(1);
-            }
-            for (int z = 0; z < poll_delay; ++z) __builtin_amdgcn_s_sleep(1);      // see poll_delay in the kernel
+            M3T_GATHER_DELAY(step);
             for (;;) {
                 // ONE 16-byte load takes two adjacent granules: the exchange is priced per load instruction, not per byte
                 // (tools/persist_probe.hip: 8 dwordx4 instead of 16 dwordx2 loads = 1.63 vs 2.03 us per step)
@@ -44,11 +40,9 @@
                         asm volatile("" : "+v"(v[k][jp]));
                         ok = ok && ((v[k][jp].y >> 16) == tag) && ((v[k][jp].w >> 16) == tag);
                     }
-                if (__all(ok) || dead) break;
-                if (++spins > ex.spin_limit) { dead = true; if (lane == 0) raise_spin(err, step); break; }
-                __builtin_amdgcn_s_sleep(1);
+                M3T_GATHER_RETRY(ok, step);
             }
-            if (spins > 0 && lane == 0) atomicOr(&poll_fail[PARV], 1u);       // any wave's failed first attempt counts for the workgroup
+            gather_note_fail(spins, lane, &poll_fail[PARV]);
             M3T_STAMP(1);
             if (F16) {
                 // fp16x3: granule = {fp16 hi, fp16 lo, 0, tag}; products lo hi, hi lo, hi hi.  The A operands of all k-steps first (the gather
@@ -131,9 +125,7 @@
                         for (int r = 0; r < 4; ++r) M3T_RED(PARV, wave, u, ct, (lane >> 4) * 4 + r, lane & 15) = acc[u][ct][r];
             }
         }
-        // nothing is outstanding here on either path (the gather ended with this very wait; step 0 had the prologue's): stated
-        // again so that EVERY path to the cell phase passes a vmcnt(0) behind the previous step's requests (tools/check_inflight.py)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        cell_phase_wait();
         // every step, unconditionally (a conditional definition gets merged by copies that read registers in flight):
         // this step's x-projection (requested one step ago) is complete since the gather's vmcnt(0) (step 0: the
         // prologue's); with nothing else outstanding, request the next step's into the other register set
@@ -143,11 +135,7 @@
         M3T_STAMP(2);
         __syncthreads();
         M3T_MARK_AFTER_BARRIER(step);
-        if (ex.poll_fixed < 0) {                       // adaptive poll delay, one value per workgroup: see poll_delay in the kernel
-            const bool wg_failed = poll_fail[PARV] != 0;
-            if (tid == 0) poll_fail[(1 - PARV)] = 0;        // next written after the next gather; last read before this barrier
-            poll_delay = wg_failed ? min(poll_delay + 2, POLL_DELAY_MAX) : ((step & 7) == 0 && poll_delay > 0 ? poll_delay - 1 : poll_delay);
-        }
+        M3T_POLL_ADAPT(PARV, 1 - PARV, step);
         M3T_STAMP(3);
         if (pw) {
             float hr = br, hz = bz, hn = bn;
@@ -173,7 +161,7 @@
             float c_xr = CUR(xr), c_xz = CUR(xz), c_xn = CUR(xn);
             if (CO) { const f32x4 x4 = sx[PARV * UW * SLOTS + slot_c]; c_xr = x4[0]; c_xz = x4[1]; c_xn = x4[2]; }
             const GateFwd c = gru_cell_fwd(c_xr, c_xz, c_xn, hr, hz, hn, hprev);
-            if (step + 1 < T && (RB == ROWS || plive) && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)
+            if (M3T_SCAN_PUBLISHES(step, RB == ROWS || plive)) {      // (rows past an 8-clip block publish nothing)
                 const float hv = pok ? (g.bf16 ? rbf(c.h) : c.h) : 0.f;
                 unsigned long long gq;
                 if (F16) {                                 // two fp16 terms of 2^14 h (|h| <= 1)
@@ -193,13 +181,9 @@
                          ((unsigned long long)__builtin_bit_cast(unsigned short, h3) << 32) |
                          ((unsigned long long)((ex.tag_base + (unsigned)step + 1u) & 0xffffu) << 48);
                 }
-                {
-                    unsigned long long* q_ = gran + (size_t)PARV * slot + pub;
-                    if (l2mode) asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(q_), "v"(gq) : "memory");      // the group shares one XCD: the line stays in its L2
-                    else asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(q_), "v"(gq) : "memory");
-                }
+                M3T_PUBLISH8(gran + (size_t)PARV * slot + pub, gq);
             }
-            if (tid == 0) __hip_atomic_store(&pub_step, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // the other waves' poll delay counts from here
+            M3T_MARK_PUBLISHED(step);
             M3T_STAMP(4);
             hprev = c.h;
             if (CO) {
@@ -208,12 +192,7 @@
                 sh[PARV * UW * SLOTS + slot_c] = c.h;
                 if (step > 0 && hok) store_results(step - 1, so[(1 - PARV) * UW * SLOTS + slot_h], sh[(1 - PARV) * UW * SLOTS + slot_h]);
             } else if (pok) {
-                d.out[((size_t)pb * T + t) * d.ldo + d.ooff + pj] = c.h;
-                if (d.gates) {
-                    float* gp = d.gates + ((size_t)pb * T + t) * 4 * H;
-                    *reinterpret_cast<float4*>(gp + 4 * (size_t)pj) = make_float4(c.r, c.z, c.n, hn);
-                }
-                if (d.h_n && step == T - 1) d.h_n[(size_t)pb * H + pj] = c.h;
+                M3T_FWD_STORE_RESULTS(pb, pj, t, step == T - 1, float4, make_float4(c.r, c.z, c.n, hn), c.h);
             }
         }
         M3T_STAMP(5);

@@ -9,11 +9,7 @@
             const unsigned long long* src = gran + (size_t)((step - 1) & 1) * slot + grp + (size_t)wave * TILE + lane;
             unsigned long long v[NC][RT][4];
             int spins = 0;
-            if (!pw && (ex.poll_align & 1)) {              // waves without cell math arrive a cell phase early: count the delay from
-                int w = 0;                                 // the workgroup's own publish (thread 0's mark in LDS) for them too
-                while (__hip_atomic_load(&pub_step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < step && ++w < ex.spin_limit) __builtin_amdgcn_s_sleep(1);
-            }
-            for (int z = 0; z < poll_delay; ++z) __builtin_amdgcn_s_sleep(1);      // see poll_delay in the kernel
+            M3T_GATHER_DELAY(step);
             for (;;) {
 #pragma unroll
                 for (int m = 0; m < NC; ++m)
@@ -38,11 +34,9 @@
                             asm volatile("" : "+v"(v[m][rt][e]));          // defined only after the wait above
                             ok = ok && ((unsigned)(v[m][rt][e] >> 32) == tag);
                         }
-                if (__all(ok) || dead) break;
-                if (++spins > ex.spin_limit) { dead = true; if (lane == 0) raise_spin(err, step); break; }
-                __builtin_amdgcn_s_sleep(1);
+                M3T_GATHER_RETRY(ok, step);
             }
-            if (spins > 0 && lane == 0) atomicOr(&poll_fail[step & 1], 1u);       // any wave's failed first attempt counts for the workgroup
+            gather_note_fail(spins, lane, &poll_fail[step & 1]);
             M3T_STAMP(1);
             f32x4 acc[RT][3];
 #pragma unroll
@@ -67,9 +61,7 @@
 #pragma unroll
                     for (int r = 0; r < 4; ++r) red[step & (NB - 1)][wave][ct][rt * 16 + (lane >> 4) * 4 + r][lane & 15] = acc[rt][ct][r];
         }
-        // nothing is outstanding here on either path (the gather ended with this very wait; step 0 had the prologue's): stated
-        // again so that EVERY path to the cell phase passes a vmcnt(0) behind the previous step's requests (tools/check_inflight.py)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        cell_phase_wait();
         // every step, unconditionally (a conditional definition gets merged by copies that read registers in flight):
         // this step's x-projection (requested one step ago) is complete since the gather's vmcnt(0) (step 0: the
         // prologue's); with nothing else outstanding, request the next step's into the other register set
@@ -77,11 +69,7 @@
         M3T_FWD_LOAD_X(step + 1, NXT(xr), NXT(xz), NXT(xn));
         M3T_STAMP(2);
         __syncthreads();
-        if (ex.poll_fixed < 0) {                       // adaptive poll delay, one value per workgroup: see poll_delay in the kernel
-            const bool wg_failed = poll_fail[step & 1] != 0;
-            if (tid == 0) poll_fail[(step + 1) & 1] = 0;        // next written after the next gather; last read before this barrier
-            poll_delay = wg_failed ? min(poll_delay + 2, POLL_DELAY_MAX) : ((step & 7) == 0 && poll_delay > 0 ? poll_delay - 1 : poll_delay);
-        }
+        M3T_POLL_ADAPT(step & 1, (step + 1) & 1, step);
         M3T_STAMP(3);
         if (pw) {
             float hr = br, hz = bz, hn = bn;
@@ -94,25 +82,14 @@
                 }
             }
             const GateFwd c = gru_cell_fwd(CUR(xr), CUR(xz), CUR(xn), hr, hz, hn, hprev);
-            if (step + 1 < T && !(step == ex.fault_step && blockIdx.x == 0)) {   // (fault injection: workgroup 0 stays silent)                        // publish: the only store on the chain
+            if (M3T_SCAN_PUBLISHES(step, true)) {          // 8-byte granule {h, tag32}
                 const unsigned long long gq = ((unsigned long long)(ex.tag_base + (unsigned)step + 1u) << 32) | __float_as_uint(pok ? (g.bf16 ? rbf(c.h) : c.h) : 0.f);
-                {
-                    unsigned long long* q_ = gran + (size_t)(step & 1) * slot + pub;
-                    if (l2mode) asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(q_), "v"(gq) : "memory");      // the group shares one XCD: the line stays in its L2
-                    else asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(q_), "v"(gq) : "memory");
-                }
+                M3T_PUBLISH8(gran + (size_t)(step & 1) * slot + pub, gq);
             }
-            if (tid == 0) __hip_atomic_store(&pub_step, step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // the other waves' poll delay counts from here
+            M3T_MARK_PUBLISHED(step);
             M3T_STAMP(4);
             hprev = c.h;
-            if (pok) {                                 // off the chain: results to HBM, next step's inputs from HBM
-                d.out[((size_t)pb * T + t) * d.ldo + d.ooff + pj] = c.h;
-                if (d.gates) {
-                    float* gp = d.gates + ((size_t)pb * T + t) * 4 * H;
-                    *reinterpret_cast<float4*>(gp + 4 * (size_t)pj) = make_float4(c.r, c.z, c.n, hn);
-                }
-                if (d.h_n && step == T - 1) d.h_n[(size_t)pb * H + pj] = c.h;
-            }
+            if (pok) M3T_FWD_STORE_RESULTS(pb, pj, t, step == T - 1, float4, make_float4(c.r, c.z, c.n, hn), c.h);
         }
         if (NB == 1) __syncthreads();
         M3T_STAMP(5);
