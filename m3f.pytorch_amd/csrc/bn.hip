@@ -5,6 +5,8 @@
 // forward reads x twice (statistics, apply) and writes y once; the backward reads dy, x, y
 // twice and writes dx once.  Column statistics go through fp64 per-chunk partials reduced in
 // a fixed order (deterministic, no atomics).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -157,8 +159,8 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------------------------- channel PLANES
 // BatchNorm3d (+ReLU) of the 3-D conv stems (reference models/backbone.py:73-103,179-191: Conv3d -> BatchNorm3d -> ReLU), x [N][C][S]
 // with S = T H W contiguous (or [N][C][H W]: BatchNorm2d): a channel is N planes of S floats.  A workgroup takes one chunk (<= 8192 floats) of one plane: float4
-// sweeps, the plane's scalars (mean, invstd, gamma, beta) loaded once.  Forward: statistics sweep (per-chunk fp64 partials, reduced per
-// channel in a fixed order) | apply + ReLU; backward: sums sweep (d beta, d gamma with the ReLU mask from y) | dx.  MIOpen ran the
+// sweeps, the plane's scalars (mean, invstd, gamma, beta) loaded once.  Forward: statistics sweep (fp64 from the first add, per-chunk fp64
+// partials reduced per channel in a fixed order) | apply + ReLU; backward: sums sweep (d beta, d gamma with the ReLU mask from y) | dx.  MIOpen ran the
 // normalisation and torch the ReLU as separate passes: one read + one write of the activation less in each direction.
 constexpr int PL_CHUNK = 8192;
 
@@ -172,23 +174,25 @@ __device__ __forceinline__ void pl_block_sum2(double& a, double& b) {
     b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
 }
 
-// partial[(plane * nch + chunk) * 2 + {0, 1}]: sum x, sum x^2
+// partial[(plane * nch + chunk) * 2 + {0, 1}]: sum x, sum x^2 -- fp64 from the first add, the square included (as bn_stats_partial_kernel and
+// GroupNorm): the variance is sum x^2 / count - mean^2, and fp32 sums of x^2 lose its digits to the mean (x = 1000 + N(0, 1): invstd off by a
+// percent).  The sweep is HBM-bound, the fp64 adds ride along.
 template <bool VEC>
 __global__ __launch_bounds__(256) void bnp_stats_partial_kernel(const float* __restrict__ x, int S, int nch, double* __restrict__ partial) {
     const size_t plane = blockIdx.x;
     const int s0 = blockIdx.y * PL_CHUNK, s1 = min(S, s0 + PL_CHUNK);
     const float* p = x + plane * (size_t)S;
-    float s = 0.f, ss = 0.f;
+    double a = 0.0, b = 0.0;
     if (VEC) {
         for (int i = s0 + 4 * threadIdx.x; i < s1; i += 1024) {
             const float4 v = *reinterpret_cast<const float4*>(p + i);
-            s += (v.x + v.y) + (v.z + v.w);
-            ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+            const double vx = (double)v.x, vy = (double)v.y, vz = (double)v.z, vw = (double)v.w;
+            a += (vx + vy) + (vz + vw);
+            b += (vx * vx + vy * vy) + (vz * vz + vw * vw);
         }
     } else {
-        for (int i = s0 + threadIdx.x; i < s1; i += 256) { const float v = p[i]; s += v; ss += v * v; }
+        for (int i = s0 + threadIdx.x; i < s1; i += 256) { const double v = (double)p[i]; a += v; b += v * v; }
     }
-    double a = (double)s, b = (double)ss;
     pl_block_sum2(a, b);
     if (threadIdx.x == 0) {
         partial[(plane * nch + blockIdx.y) * 2 + 0] = a;
@@ -341,17 +345,20 @@ static SmallMap small_map(int S, bool vec) {
     const size_t base = plane * (size_t)S;                                                                      \
     constexpr int E = VEC ? 4 : 1;
 
-__device__ __forceinline__ void seg_sum2(float& a, float& b, int lpp) {
+template <typename T>
+__device__ __forceinline__ void seg_sum2(T& a, T& b, int lpp) {
     for (int o = 1; o < lpp; o <<= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
 }
 
-// MODE 0: sum x, sum x^2;  MODE 1: sum g, sum g xhat (g = dy masked by y > 0 when relu).  partial[plane * 2 + {0, 1}]
+// MODE 0: sum x, sum x^2 (fp64 from the first add, lanes folded in fp64: see bnp_stats_partial_kernel);  MODE 1: sum g, sum g xhat (g = dy
+// masked by y > 0 when relu; fp32 per plane -- xhat is centred, nothing large cancels).  partial[plane * 2 + {0, 1}]
 template <bool VEC, int MODE>
 __global__ __launch_bounds__(256) void bnp_small_reduce_kernel(const float* __restrict__ a, const float* __restrict__ x, const float* __restrict__ y,
                                                                const float* __restrict__ mean, const float* __restrict__ invstd, size_t P, int C, int S,
                                                                int lpp, int lg, int relu, double* __restrict__ partial) {
     M3T_SMALL_PROLOGUE
-    float s = 0.f, t = 0.f;
+    using acc_t = typename std::conditional<MODE == 0, double, float>::type;
+    acc_t s = 0, t = 0;
     if (live) {
         float mu = 0.f, is = 1.f;
         if (MODE == 1) { const int c = (int)(plane % (size_t)C); mu = mean[c]; is = invstd[c]; }
@@ -371,7 +378,7 @@ __global__ __launch_bounds__(256) void bnp_small_reduce_kernel(const float* __re
             }
 #pragma unroll
             for (int e = 0; e < E; ++e) {
-                if (MODE == 0) { s += v[e]; t += v[e] * v[e]; }
+                if (MODE == 0) { const acc_t w = (acc_t)v[e]; s += w; t += w * w; }
                 else {
                     float g = v[e];
                     if (relu && !(yv[e] > 0.f)) g = 0.f;

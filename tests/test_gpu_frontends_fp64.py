@@ -190,7 +190,11 @@ SE_DIM = 8          # the SENet / AU feature widths VA_3DVGGM_Split.features con
 # 1e-9 changes every tensor by ~1e-8 -- smooth error is not amplified).  Flips are dense in the train-mode DenseNet (1 of 16 videos of
 # densenet_ap is free of them: its accumulation test is skipped).  A rounding change in a kernel can move a flip onto these videos: the message
 # then names a tensor upstream of a ReLU / pooling, with an error of 1e-3 or more while every other tensor stays near 1e-6.
-VIDEOS = {"vggm_bn": (2, 3), "vggm_gn": (0, 1), "split3": (1, 2), "resnet_v1_cbam": (1, 2), "resnet_v2": (0, 1), "resnet_v2_cbam": (7, 4),
+# (This happened to resnet_v2's video 0 when the plane BatchNorm kernels took their statistic sums in fp64: in float64 its closest
+# pre-activation, at resnet.layer2.0.bn1, lies 7 fp32 roundings from zero, and the last bits of that layer's invstd now decide it the other way
+# -- dbeta of layer2.0.bn1 and everything upstream moved by 2e-2 ... 5e-2, y and the running statistics stayed at 2e-6 / 2e-7.  Of the videos
+# 0 ... 4, 6, 8, 9 measured with those kernels, 1, 3 and 6 are free of flips; the bars are unchanged.)
+VIDEOS = {"vggm_bn": (2, 3), "vggm_gn": (0, 1), "split3": (1, 2), "resnet_v1_cbam": (1, 2), "resnet_v2": (1, 3), "resnet_v2_cbam": (7, 4),
           "densenet_ap": (13,), "densenet_fc": (9, 11)}
 
 # Bars: max |err| / max |ref| per case, mode and tensor kind -- y output, dx video gradient, w weight gradients, bn normalisation affine

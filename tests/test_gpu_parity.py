@@ -1478,7 +1478,8 @@ def test_conv_walk_entry_points_planes_output_and_refusals():
 def test_batchnorm3d_relu_on_channel_planes(N, C_, T, H, W, training):
     """models.backbone.BatchNorm3dReLU (nn.BatchNorm3d + nn.ReLU of the 3-D stems, reference models/backbone.py:73-103,179-191) on
     csrc/bn.hip's channel-plane kernels: planes of 315 floats (scalar sweeps), of 576 (float4), eval mode, one value per plane --
-    output, running statistics, input and parameter gradients against float64 torch on the CPU"""
+    output, running statistics, input and parameter gradients against float64 torch on the CPU
+    (the kernels' fp32-rounding bar, every dispatch branch and large-mean inputs: tests/test_gpu_bn_fp64.py)"""
     from models.backbone import BatchNorm3dReLU
     rs = np.random.RandomState(N + C_ + H)
     m = BatchNorm3dReLU(C_).to(DEV)
@@ -1511,7 +1512,8 @@ def test_batchnorm3d_relu_on_channel_planes(N, C_, T, H, W, training):
 def test_plane_batchnorm2d_on_the_resnet_maps(N, C_, H, W, training, relu):
     """models.resnet.PlaneBatchNorm2d (nn.BatchNorm2d [+ ReLU] of the per-frame ResNet, reference models/resnet.py:18-60) on csrc/bn.hip's
     small-plane kernels: 784 / 196 floats per plane (float4 units, 64 lanes per plane), 49 (scalar units), 16 (four lanes per plane, 16
-    planes per wave), ragged plane counts, eval mode -- against float64 torch on the CPU"""
+    planes per wave), ragged plane counts, eval mode -- against float64 torch on the CPU
+    (the kernels' fp32-rounding bar, every dispatch branch and large-mean inputs: tests/test_gpu_bn_fp64.py)"""
     from models.resnet import PlaneBatchNorm2d
     rs = np.random.RandomState(N + C_ + H)
     m = PlaneBatchNorm2d(C_, fuse_relu=relu).to(DEV)
