@@ -978,6 +978,35 @@ int m3t_stack_context_batch(const float* mels, long long total_rows, int n_mels,
 int m3t_label_rows(const uint8_t* table, long long n_files, int n_classes, const long long* items, int N, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Wave conversion (csrc/resample.hip; m3t.audio.decode_waves): what `librosa.load(path, sr=16000)` does to a file before the reference
+ * sees a sample (models/audioset_dataset.py:61, process/extract_melspec.py:13) -- decode to float32, down-mix to mono, resample to 16 kHz
+ * with resampy's 'kaiser_best' filter, pad to ceil(frames * 16000 / rate) -- for a ragged batch of clips of ONE source rate in one launch.
+ * The rule is DESIGN.md 4c: the project's own restatement of libsndfile, librosa 0.7 and resampy 0.2.2, not a run of them.
+ * bytes: the clips' raw interleaved 'data' bodies in one device buffer of n_bytes (4-byte aligned).
+ * clips: device long long [N][8] = byte offset, frames, channels (1..8), kind (0 u8, 1 i16, 2 i24, 3 i32, 4 f32), output offset, n_res,
+ *        n_out, tile prefix.  A clip's offset is a multiple of its sample size (1 for i24); its outputs are out[output offset .. + n_out);
+ *        n_res = int(frames * ratio), n_out = int(ceil(frames * ratio)) in float64, ratio = 16000.0 / rate; it owns the workgroups
+ *        tile prefix .. + ceil(n_out / 256) of the n_tiles of the launch (the prefix is non-decreasing: the kernel searches it).
+ * Sample to float: (u8 - 128) / 128, i16 / 32768, i24 / 8388608, i32 / 2147483648 rounded once, float32 as stored; mono = the channels
+ * summed in order in fp32, divided by their count (one channel: the sample itself).
+ * rate == 16000: out[t] = mono[t]; table and starts are not read.
+ * Otherwise, with scale = min(1, ratio), step = int(scale * 512), r_0 = 0.0, r_{t+1} = r_t + rate / 16000.0 in float64:
+ *     n = int(r_t), frac = scale (r_t - n)
+ *     out[t] =   sum_{i < min(n + 1, (32769 - o) / step)}          w(o + i step) mono[n - i],      o, eta from frac 512
+ *              + sum_{k < min(frames - n - 1, (32769 - o') / step)} w(o' + k step) mono[n + k + 1],  o', eta' from (scale - frac) 512
+ *     w(j) = table[j][0] + eta table[j][1]                                  for t < n_res;   out[t] = 0.0f for n_res <= t < n_out
+ * accumulated in ONE fp32 value in that order, in resampy's arithmetic: acc = float(double(acc) + w(j) * double(mono[.])), w(j) and the
+ * product in fp64, every operation rounded on its own.  table: device double [32769][2] = (win, delta) of the half filter (already
+ * multiplied by ratio when ratio < 1), 16-byte aligned.  starts: device double [n_starts], starts[s] = r_{64 s} as the sequential additions give it
+ * (the host accumulates them once per rate; the lanes carry on with the same additions); n_starts >= 4 ceil(n_out / 256) of the longest
+ * clip.  No atomics, nothing read back, reruns bit-identical.  A row that does not fit the buffers (or channels / kind out of range, a
+ * misaligned offset, too few starts) is caught on the device: nothing of that clip is read or written; the host refuses it first
+ * (m3t.audio.plan_convert).  M3T_EINVAL: null or misaligned pointers, non-positive sizes, a rate whose tile span does not fit 64 KB of LDS
+ * (above about 600 kHz); N == 0 or n_tiles == 0 returns 0. */
+int m3t_wave_convert(const uint8_t* bytes, long long n_bytes, const long long* clips, int N, long long n_tiles, int rate,
+                     const double* table, const double* starts, long long n_starts, float* out, long long n_out_total, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Video ingest: what the reference's two loaders do to pixels between the decoder and the first convolution (models/dataset.py:16-31,46-80
  * and :312, models/vox2_dataset.py:14-50, models/cv_augment.py:6-37) and the normalisation of models/model.py:106, in one pass over the
  * uint8 frames as decoded, frames [N][Ts][Hs][Ws][3] (channel order as stored).  For clip n, output frame t, pixel (y, x), channel c:

@@ -26,17 +26,27 @@ temporal crop with np.pad 'wrap', the spectrogram above, the context stack) in t
   load_audio_batch(mels, starts, ...)    the AffWild2 loader's collate step (`models/dataset.py:83-95, :276-306`): N pre-extracted tracks
                                          -> [N, window, 200] in one launch, edge padding and the "fps < 15 -> zeros" rule included
 
-Wav reading is m3t/wav.py (16-bit mono PCM, on the host) and the resident store of a split's clips m3t/audioset.py.  Out of scope:
-resampling and the other sample formats `librosa.load` takes.
+The wave conversion (csrc/resample.hip) is what `librosa.load(path, sr=16000)` does in front of both: any WAV rate, 1..8 channels,
+PCM 8/16/24/32 or float32 -> 16 kHz mono float32, from the raw bytes, one launch per source rate for a ragged batch:
+
+  decode_waves(files or (bytes, WaveInfo) pairs)   -> (flat float32 device buffer, offsets, lengths)
+  load_wave(path)                                  = librosa.load(path, sr=16000)[0] (process/extract_melspec.py:13)
+  converted_length(frames, rate)                   a clip's length after conversion, from its header alone (what an epoch plan needs)
+  plan_convert(...)                                host validation + the per-clip table, before anything touches a device
+
+Wav reading is m3t/wav.py (on the host: headers and raw bytes), the resident store of a split's clips m3t/audioset.py, the AffWild2 mel
+tracks m3t/melspec.py.
 """
 import ctypes as C
 import math
+import os
 import random
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import wav as _wav
 from .ops import lib, _stream, _p, sgemm, workspace, M3THipError
 
 SR, N_FFT, WIN, N_MELS = 16000, 512, 400, 40
@@ -324,3 +334,181 @@ def load_audio_batch(mels, starts, track_lens, window, valid=None):
     _lib.check(lib().m3t_stack_context_batch(_p(flat), int(rows.sum()), n_mels, tab.data_ptr(), N, window, 3, 5, _p(out), _stream()),
                "m3t_stack_context_batch")
     return out
+
+
+# ---- wave conversion: a WAV of any rate, channel count and depth -> 16 kHz mono float32 (csrc/resample.hip) --------------
+NUM_ZEROS, PRECISION, ROLLOFF, KAISER_BETA = 64, 9, 0.9475937167399596, 14.769656459379492       # resampy's 'kaiser_best'
+TILE, SEG = 256, 64                     # outputs of a workgroup; outputs per host-accumulated register start (csrc/resample.hip)
+MAX_RATE = 384000                       # the tile's span of source frames must fit 64 KB of LDS
+STAGE_BYTES = 64 << 20
+_ALIGN = 16
+_RES_TABLE, _RES_STARTS = {}, {}
+
+
+def converted_length(frames, rate):
+    """len(librosa.load(path, sr=16000)[0]) for a file of `frames` frames at `rate` Hz: int(ceil(frames * (16000.0 / rate))) in float64 AS
+    WRITTEN (librosa.resample's n_samples: the rule is the float64 expression, not integer arithmetic).  Host only."""
+    return int(np.ceil(int(frames) * (float(SR) / int(rate))))
+
+
+def resampled_length(frames, rate):
+    """the outputs the filter computes, resampy's int(frames * ratio); the rest up to converted_length is fix_length's 0.0"""
+    return int(int(frames) * (float(SR) / int(rate)))
+
+
+def resample_filter(rate):
+    """-> float64 [32769, 2] = (win, delta) of DESIGN.md 4c for a source of `rate` Hz: the right half of
+    kaiser(2n + 1, beta) * rolloff * sinc(rolloff * j / 512), n = 64 * 512, times ratio when ratio < 1; delta = diff(win) and a last 0."""
+    n = NUM_ZEROS << PRECISION
+    win = np.kaiser(2 * n + 1, KAISER_BETA)[n:] * (ROLLOFF * np.sinc(ROLLOFF * np.linspace(0, NUM_ZEROS, num=n + 1, endpoint=True)))
+    ratio = float(SR) / int(rate)
+    if ratio < 1:
+        win = win * ratio
+    delta = np.zeros_like(win)
+    delta[:-1] = np.diff(win)
+    return np.ascontiguousarray(np.stack([win, delta], 1), np.float64)
+
+
+def register_starts(rate, n_out):
+    """float64 [4 ceil(n_out / 256)]: the time register r_t at t = 0, 64, 128, ..., where r_0 = 0.0 and r_{t+1} = r_t + rate / 16000.0 by
+    sequential float64 additions (np.add.accumulate; resampy's `time_register += time_increment`).  Depends on the rate only."""
+    count = (TILE // SEG) * -(-int(n_out) // TILE)
+    steps = np.full(count * SEG, int(rate) / float(SR))
+    steps[0] = 0.0
+    return np.ascontiguousarray(np.add.accumulate(steps)[::SEG])
+
+
+def plan_convert(infos, byte_offsets, n_bytes, out_offsets=None, names=None):
+    """Host validation of a convert call, before anything touches a device.  infos: one m3t.wav.WaveInfo per clip; byte_offsets: where each
+    clip's 'data' body starts in the byte buffer of `n_bytes`; out_offsets: where its outputs start (default: packed in order).
+    -> (out_offsets int64 [F], lengths int64 [F], total outputs, {rate: (clip indices, table int64 [N, 8], tiles)}), the table of
+    include/m3t_hip.h (m3t_wave_convert).  ValueError, with the clip named, for an empty clip, a kind / channel count / rate outside
+    what the kernel takes, a body that leaves the buffer or starts off its sample's alignment."""
+    F = len(infos)
+    if F == 0:
+        raise ValueError("decode_waves: no clips")
+    names = ["clip %d" % i for i in range(F)] if names is None else names
+    offs = np.asarray(byte_offsets, np.int64).reshape(-1)
+    if offs.shape != (F,):
+        raise ValueError("decode_waves: %d byte offsets for %d clips" % (offs.shape[0], F))
+    lengths = np.zeros(F, np.int64)
+    for i, w in enumerate(infos):
+        if not (0 <= int(w.kind) < len(_wav.KIND_BYTES) and 1 <= int(w.channels) <= _wav.MAX_CHANNELS):
+            raise ValueError("%s: kind %r with %r channels is not a sample format the convert kernel takes" % (names[i], w.kind, w.channels))
+        if not 1 <= int(w.rate) <= MAX_RATE:
+            raise ValueError("%s: sampled at %d Hz; 1 .. %d Hz is taken" % (names[i], w.rate, MAX_RATE))
+        if int(w.frames) <= 0:
+            raise ValueError("%s: an empty clip (no whole frame in its 'data' chunk)" % (names[i],))
+        sample = _wav.KIND_BYTES[w.kind]
+        if offs[i] < 0 or offs[i] % (1 if w.kind == _wav.KIND_I24 else sample) or int(w.frames) * sample * int(w.channels) > n_bytes - offs[i]:
+            raise ValueError("%s: bytes %d .. %d lie outside the buffer's %d (or off the sample's alignment)"
+                             % (names[i], offs[i], offs[i] + int(w.frames) * sample * int(w.channels), n_bytes))
+        lengths[i] = converted_length(w.frames, w.rate)
+    if out_offsets is None:
+        out_offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+    out_offsets = np.asarray(out_offsets, np.int64)
+    groups = {}
+    for rate in sorted({int(w.rate) for w in infos}):
+        idx = np.array([i for i, w in enumerate(infos) if int(w.rate) == rate], np.int64)
+        table = np.zeros((idx.shape[0], 8), np.int64)
+        for r, i in enumerate(idx):
+            w = infos[i]
+            table[r, :7] = (offs[i], w.frames, w.channels, w.kind, out_offsets[i], resampled_length(w.frames, rate), lengths[i])
+        tiles = -(-table[:, 6] // TILE)
+        table[1:, 7] = np.cumsum(tiles[:-1])
+        groups[rate] = (idx, table, int(tiles.sum()))
+    return out_offsets, lengths, int(lengths.sum()), groups
+
+
+def _filter_on(dev, rate):
+    key = (dev.type, dev.index, rate if rate > SR else 0)            # (upsampling does not scale the table: one for every such rate)
+    t = _RES_TABLE.get(key)
+    if t is None:
+        t = _RES_TABLE[key] = torch.from_numpy(resample_filter(rate)).to(dev)
+    return t
+
+
+def _starts_on(dev, rate, n_out):
+    key = (dev.type, dev.index, rate)
+    need = (TILE // SEG) * -(-int(n_out) // TILE)
+    t = _RES_STARTS.get(key)
+    if t is None or t.numel() < need:
+        t = _RES_STARTS[key] = torch.from_numpy(register_starts(rate, n_out)).to(dev)
+    return t
+
+
+def convert_planned(raw, groups, out):
+    """the launches of a planned convert: raw, the uint8 device buffer of the clips' bodies; groups, plan_convert's; out, the flat float32
+    device buffer the tables' output offsets point into.  One table upload, one launch per distinct rate; nothing is read back."""
+    dev = raw.device
+    tab = torch.from_numpy(np.concatenate([t.reshape(-1) for _, t, _ in groups.values()])).to(dev, non_blocking=True)
+    row = 0
+    for rate, (idx, table, tiles) in groups.items():
+        N = int(table.shape[0])
+        filt = starts = None
+        if rate != SR:
+            filt, starts = _filter_on(dev, rate), _starts_on(dev, rate, int(table[:, 6].max()))
+        _lib.check(lib().m3t_wave_convert(raw.data_ptr(), raw.numel(), tab.data_ptr() + 64 * row, N, tiles, rate,
+                                          None if filt is None else filt.data_ptr(),
+                                          None if starts is None else starts.data_ptr(), 0 if starts is None else starts.numel(),
+                                          _p(out), out.numel(), _stream()), "m3t_wave_convert")
+        row += N
+
+
+def decode_waves(items, device=None, chunk_bytes=STAGE_BYTES):
+    """items: .wav paths, or (bytes, WaveInfo) pairs as m3t.wav.read_wave gives them (a uint8 array or a bytes object: the 'data' body).
+    -> (flat float32 device buffer, offsets int64 [F], lengths int64 [F] on the host): clip i, as `librosa.load(path, sr=16000)[0]` of the
+    reference's era gives it, is buffer[offsets[i] : offsets[i] + lengths[i]].
+    The headers are read first (the buffer's size is known before a sample is); then the bodies go up in chunks of at most `chunk_bytes`
+    through ONE pinned stage (a longer clip goes on its own), each chunk converted with one launch per distinct rate in it -- a call whose
+    bodies fit one chunk is one upload and one launch per rate.  The host never holds more than a chunk; nothing is read back."""
+    if not torch.cuda.is_available():
+        raise M3THipError("m3t.audio needs the GPU: the M3T path has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    items = list(items)
+    names = [str(it) if isinstance(it, (str, bytes, os.PathLike)) else "clip %d" % i for i, it in enumerate(items)]
+    infos = [_wav.probe_wave(it) if isinstance(it, (str, bytes, os.PathLike)) else it[1] for it in items]
+    sizes = np.array([int(w.frames) * w.frame_bytes for w in infos], np.int64)
+    padded = (sizes + _ALIGN - 1) // _ALIGN * _ALIGN
+    out_offsets, lengths, total, _ = plan_convert(infos, np.zeros(len(items), np.int64), int(sizes.max(initial=0)), names=names)
+    out = torch.empty(total, dtype=torch.float32, device=dev)
+    cap = max(int(chunk_bytes), _ALIGN)
+    stage, copied = None, None
+    lo = 0
+    with torch.cuda.device(dev):
+        while lo < len(items):
+            hi, fill = lo + 1, int(padded[lo])
+            while hi < len(items) and fill + padded[hi] <= cap:
+                fill += int(padded[hi])
+                hi += 1
+            if stage is None or stage.numel() < fill:
+                stage = torch.empty(max(fill, min(cap, int(padded.sum()))), dtype=torch.uint8, pin_memory=True)
+            elif copied is not None:
+                copied.synchronize()                                  # the stage is free again once the previous chunk's copy has ended
+            host, offs, pos = stage.numpy(), [], 0
+            for i in range(lo, hi):
+                it = items[i]
+                if isinstance(it, (str, bytes, os.PathLike)):
+                    body, info = _wav.read_wave(it)
+                    if info != infos[i]:
+                        raise ValueError("%s: its header read %r when the call was planned and reads %r now" % (names[i], tuple(infos[i]), tuple(info)))
+                else:
+                    body = np.frombuffer(it[0], np.uint8) if isinstance(it[0], (bytes, bytearray, memoryview)) else np.asarray(it[0], np.uint8).reshape(-1)
+                    if body.shape[0] < sizes[i]:
+                        raise ValueError("%s: %d bytes given, its WaveInfo asks for %d" % (names[i], body.shape[0], sizes[i]))
+                host[pos:pos + sizes[i]] = body[:sizes[i]]
+                offs.append(pos)
+                pos += int(padded[i])
+            raw = torch.empty(fill, dtype=torch.uint8, device=dev)
+            raw.copy_(stage[:fill], non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record()
+            _, _, _, groups = plan_convert(infos[lo:hi], offs, fill, out_offsets[lo:hi], names[lo:hi])
+            convert_planned(raw, groups, out)
+            lo = hi
+    return out, out_offsets, lengths
+
+
+def load_wave(path):
+    """`librosa.load(path, sr=16000)[0]` (process/extract_melspec.py:13) -> float32 device tensor [converted_length]"""
+    return decode_waves([path])[0]

@@ -3,7 +3,9 @@ reference's workflow).  The reference's loader (`models/audioset_dataset.py`, `A
 and per item decodes a whole 10 s clip with librosa, crops it, and computes the log-Mel rows on the host.  Here:
 
   scan_audioset   the reference's `__init__` (`audioset_dataset.py:99-121`), rule for rule -> Scan (files, uint8 label matrix).  Host only.
-  WaveStore       every clip of a split read once (m3t/wav.py) into ONE flat int16 device buffer, the label matrix beside it as uint8
+  WaveStore       every clip of a split read once (m3t/wav.py) into ONE flat int16 device buffer, the label matrix beside it as uint8;
+                  with convert=True clips of any rate, channel count and sample kind, converted on the device (m3t.audio.decode_waves) into
+                  ONE flat float32 buffer of 16 kHz mono
   AudioSetFeed    plan_epoch(epoch) -> [BatchPlan], host only; iterating it yields {'audio': float32 [N, window, 200], 'label': float32
                   [N, 527]} on the current stream -- what the reference's loader yields, so AudioSet.training_step / validation_step take it
                   unchanged; set_epoch / state_dict / load_state_dict
@@ -22,8 +24,8 @@ no sample crosses the bus after the store is built, and nothing is read back.
 Everything down to "which clips, which draws" runs without a GPU and without initialising one (the clips' lengths come from the files'
 headers); the store is built when the first batch is asked for (or by build_store()).
 
-Out of scope: resampling and other sample formats (a clip that is not 16 kHz, 16-bit, mono is refused with its name), stereo down-mix, a
-disk cache or a host arena for the store (balanced train is about 7 GB of int16: it fits), prefetch threads, `spec_augment` (defined by the
+Without `convert` a clip that is not 16 kHz, 16-bit, mono is refused with its name, as before.  Out of scope: a
+disk cache or a host arena for the store (balanced train is about 7 GB of int16, 14 GB of float32: it fits), prefetch threads, `spec_augment` (defined by the
 reference, never called by it), the VoxCeleb2 loader, multi-GPU measurements (the sharding rule is tested on the host).
 """
 import os
@@ -49,19 +51,25 @@ CHUNK_BYTES = 64 << 20
 class Scan:
     """What scan_audioset found.  files: the clips' paths in the reference's order; labels: uint8 [F, 527], 1 where the reference's float
     vector is 1.0; split, path.  lengths() reads the files' headers (once) -> int64 [F] samples; a rate other than 16 kHz or an empty clip is
-    refused there, with the file named."""
-    __slots__ = ("files", "labels", "split", "path", "_lengths")
+    refused there, with the file named.  A scan made with convert=True takes every file m3t.wav.probe_wave takes, and a clip's length is
+    m3t.audio.converted_length of its header -- what the reference's `len(y)` after `librosa.load(path, sr=16000)` would be."""
+    __slots__ = ("files", "labels", "split", "path", "convert", "_lengths")
 
     def __len__(self):
         return len(self.files)
 
     def lengths(self):
         if self._lengths is None:
-            self._lengths = np.array([_clip_samples(f) for f in self.files], np.int64)
+            self._lengths = np.array([_clip_samples(f, self.convert) for f in self.files], np.int64)
         return self._lengths
 
 
-def _clip_samples(path):
+def _clip_samples(path, convert=False):
+    if convert:
+        info = _wav.probe_wave(path)
+        if info.frames <= 0:
+            raise ValueError("%s: an empty clip (no whole frame in its 'data' chunk)" % (path,))
+        return _audio.converted_length(info.frames, info.rate)
     n, rate = _wav.probe_pcm16(path)
     _check_clip(path, n, rate)
     return n
@@ -82,7 +90,7 @@ def _lines(path, what):
         raise ValueError("scan_audioset: no %s: %s (%s)" % (what, path, e.strerror or e)) from None
 
 
-def scan_audioset(path, split):
+def scan_audioset(path, split, convert=False):
     """The reference's `AudioSetDataset.__init__` (`audioset_dataset.py:99-121`), rule for rule -> Scan.  Host only.
       * `path`/class_labels_indices.csv without its first line: the mid of class i is `l.split(',')[1]` of line i (display names may hold
         commas and quotes: they come third);
@@ -120,7 +128,7 @@ def scan_audioset(path, split):
         files.append(wav_path)
         rows.append(row)
     s = Scan()
-    s.files, s.split, s.path, s._lengths = files, split, path, None
+    s.files, s.split, s.path, s.convert, s._lengths = files, split, path, bool(convert), None
     s.labels = np.stack(rows) if rows else np.zeros((0, N_CLASSES), np.uint8)
     return s
 
@@ -146,9 +154,12 @@ class WaveStore:
     refused with the file named); labels: uint8 [F, n_classes] or None.  The samples go to ONE flat int16 device buffer `wave`, staged
     through a host buffer of at most `chunk_bytes` (a longer clip goes on its own): the host never holds the corpus.  offsets, lengths:
     int64 [F] on the host, clip i = wave[offsets[i] : offsets[i] + lengths[i]]; label_table: the uint8 matrix on the device.
-    lengths (optional): what the files' headers said; the store refuses a file that now reads differently."""
+    lengths (optional): what the files' headers said; the store refuses a file that now reads differently.
+    convert=True: every file m3t.wav.read_wave takes, of any rate; the raw bytes go up through a pinned stage of at most `chunk_bytes` and
+    m3t.audio.decode_waves turns them into 16 kHz mono on the device, so `wave` is ONE flat float32 buffer (the ingest reads either dtype in
+    place) and a clip's length is m3t.audio.converted_length of its header.  A 16 kHz, 16-bit, mono clip holds int16 / 32768 exactly."""
 
-    def __init__(self, files, labels=None, lengths=None, chunk_bytes=CHUNK_BYTES, device=None):
+    def __init__(self, files, labels=None, lengths=None, chunk_bytes=CHUNK_BYTES, device=None, convert=False):
         files = list(files)
         if not files:
             raise ValueError("WaveStore: no files")
@@ -160,6 +171,16 @@ class WaveStore:
             raise M3THipError("m3t.audioset.WaveStore needs the GPU: the M3T path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.files = files
+        self.convert = bool(convert)
+        self.label_table = None if labels is None else torch.from_numpy(labels).to(self.device)
+        self.n_classes = 0 if labels is None else int(labels.shape[1])
+        if self.convert:
+            self.wave, self.offsets, self.lengths = _audio.decode_waves(files, self.device, chunk_bytes)
+            if lengths is not None and not np.array_equal(np.asarray(lengths, np.int64), self.lengths):
+                i = int(np.flatnonzero(np.asarray(lengths, np.int64) != self.lengths)[0])
+                raise ValueError("%s: %d samples after conversion, %d expected from its header when the epoch was planned"
+                                 % (files[i], self.lengths[i], np.asarray(lengths)[i]))
+            return
         if lengths is None:
             lengths = [_clip_samples(f) for f in files]
         self.lengths = np.asarray(lengths, np.int64).copy()
@@ -192,15 +213,13 @@ class WaveStore:
                 fill += y.shape[0]
         flush()
         assert base == total
-        self.label_table = None if labels is None else torch.from_numpy(labels).to(self.device)
-        self.n_classes = 0 if labels is None else int(labels.shape[1])
 
     def __len__(self):
         return len(self.files)
 
     @property
     def nbytes(self):
-        return int(self.wave.numel()) * 2 + (0 if self.label_table is None else int(self.label_table.numel()))
+        return int(self.wave.numel()) * self.wave.element_size() + (0 if self.label_table is None else int(self.label_table.numel()))
 
     def plan(self, items, draws, window):
         return plan_batch(self.wave, self.offsets, self.lengths, items, draws, window)
@@ -263,15 +282,19 @@ class AudioSetFeed:
     window, batch_size, split: the reference's (`audioset_dataset.py:99`, `audioset_model.py:129-145`); split must be the scan's.  rank /
     world: world > 1 shards the indices with torch's DistributedSampler in both splits (the reference's default one: shuffled, seed 0,
     set_epoch(epoch)).  sampler: overrides the index order -- any iterable of indices, or a callable that makes one from the data set.
-    pad_mode: the STFT's padding, m3t.audio's ('constant' is librosa >= 0.10's).
+    pad_mode: the STFT's padding, m3t.audio's ('constant' is librosa >= 0.10's).  convert: the scan's (scan_audioset(..., convert=True));
+    given here it must agree with it, since the planned lengths are the scan's.
 
     Construction reads the clips' headers (Scan.lengths) and touches no device.  plan_epoch(epoch) is host only.  Iterating builds the
     WaveStore on the current device at the first batch and yields, per BatchPlan, WaveStore.batch(items, draws): validated for the whole
     batch before its first launch, queued on the current stream, nothing read back."""
 
-    def __init__(self, scan, window, batch_size, split, rank=0, world=1, sampler=None, pad_mode="constant"):
+    def __init__(self, scan, window, batch_size, split, rank=0, world=1, sampler=None, pad_mode="constant", convert=None):
         if scan.split != split:
             raise ValueError("AudioSetFeed: split is %r, the folder was scanned for %r" % (split, scan.split))
+        self.convert = bool(getattr(scan, "convert", False)) if convert is None else bool(convert)
+        if self.convert != bool(getattr(scan, "convert", False)):
+            raise ValueError("AudioSetFeed: convert=%r, the folder was scanned with convert=%r" % (self.convert, bool(getattr(scan, "convert", False))))
         self.scan, self.window, self.batch_size, self.split = scan, int(window), int(batch_size), split
         self.rank, self.world, self.pad_mode = int(rank), int(world), pad_mode
         if self.batch_size <= 0 or self.window <= 0:
@@ -333,7 +356,7 @@ class AudioSetFeed:
     def build_store(self):
         """the WaveStore of the scan on the current device (once)"""
         if self.store is None:
-            self.store = WaveStore(self.files, self.scan.labels, self.lengths)
+            self.store = WaveStore(self.files, self.scan.labels, self.lengths, convert=self.convert)
         return self
 
     def batch(self, plan):
@@ -348,5 +371,7 @@ class AudioSetFeed:
 
 
 def feed_from_hparams(hparams, split, rank=0, world=1):
-    """the feed of one split with the reference's arguments (`audioset_model.py:129-145`): dataset_path, window, batch_size"""
-    return AudioSetFeed(scan_audioset(hparams.dataset_path, split), hparams.window, hparams.batch_size, split, rank, world)
+    """the feed of one split with the reference's arguments (`audioset_model.py:129-145`): dataset_path, window, batch_size; convert_audio
+    (pretrain_audioset.py --convert_audio), when the namespace has it, is the scan's `convert`"""
+    scan = scan_audioset(hparams.dataset_path, split, convert=bool(getattr(hparams, "convert_audio", False)))
+    return AudioSetFeed(scan, hparams.window, hparams.batch_size, split, rank, world)

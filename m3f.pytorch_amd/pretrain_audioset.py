@@ -11,6 +11,8 @@ m3t/trainer.py and the epoch feed of m3t/audioset.py.
     val feed goes through Trainer.validate, and end_epoch keeps `<checkpoint_path>/best.ckpt` by the best val_loss;
   * `--dataset_path` holds class_labels_indices.csv, balanced_train_segments.csv, eval_segments.csv and the two folders of 16 kHz, 16-bit,
     mono .wav clips of the same names; both splits are uploaded to the device once, before the first step;
+  * `--convert_audio` takes the folder as the reference's loader does: clips of any rate, channel count and sample kind (m3t/wav.py's wider
+    reader), down-mixed and resampled to 16 kHz on the device when the store is built (m3t.audio.decode_waves); without it such a clip is refused;
   * `--gpus` / `--nodes` are accepted and ignored: start one process per GPU with torchrun and pass `--distributed`; the world is torchrun's;
   * `--workers` is accepted and ignored: there is no host-side decoding left to spread;
   * `--test_lr` (the LR range finder) is out of scope and raises.
@@ -18,7 +20,7 @@ m3t/trainer.py and the epoch feed of m3t/audioset.py.
 import os
 import random
 import sys
-from argparse import ArgumentParser
+from argparse import SUPPRESS, ArgumentParser
 
 import numpy as np
 import torch
@@ -35,6 +37,7 @@ def make_parser():
     parser.add_argument('--nodes', type=int, default=1)
     parser.add_argument('--seed', type=int, default=12345)
     parser.add_argument('--checkpoint', type=str, default='')
+    parser.add_argument('--convert_audio', action='store_true', default=SUPPRESS)    # (absent unless given: the reference has no such flag)
     return AudioSet.add_model_specific_args(parser)
 
 
