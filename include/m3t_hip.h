@@ -1308,6 +1308,41 @@ int m3t_cls_loss(const float* logits, int B, int C, int kind, const void* target
 int m3t_tpool_cls_loss(const float* z, int B, int T, int C, int mode, int kind, const void* target, float* pooled, int* arg,
                        float* out_scalars, float* correct, float* dz, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Multi-label evaluation epoch on the device (csrc/cls_eval.hip, m3t/cls_evaluate.py): mean average precision, mean ROC-AUC and d' of
+ * the AudioSet stage.  The reference has no counterpart (its validation_end reports val_loss and a top-1 val_acc, audioset_model.py:
+ * 89-104); the three launches replace a read-back of the [M, C] scores followed by scikit-learn's average_precision_score and
+ * roc_auc_score per class on the host.  Resident state, owned by the caller and zero-filled before the first append: col_scores
+ * [C][M] fp32 and col_labels [C][M] uint8 (CLASS-major: a class's column is contiguous), seen [M] uint8, counters [2] uint32.
+ * 1 <= M <= M3T_CLS_EVAL_MAX_ROWS, C >= 1, no alignment or divisibility requirement; anything else returns M3T_EINVAL.  No float
+ * atomics and every float64 sum in a fixed order: the same bits run to run.
+ *
+ * m3t_cls_eval_append, one launch per batch: scores [B,C] (the pooled per-clip logits of m3t_tpool_cls_loss) and labels [B,C] fp32
+ * go to row rows[b] of every class column, transposed through an LDS tile (labels as uint8: 1 where the label is 1.0); seen[rows[b]] = 1;
+ * counters[0] += the scores that are NaN or +-inf, counters[1] += the labels that are neither 0.0 nor 1.0.  rows: int32 [B], each in
+ * [0, M) (validated by the caller; a row outside is not written).  Writing a row twice with equal values is legal. */
+#define M3T_CLS_EVAL_LDS_ROWS 16384     /* the longest column the rank kernel sorts wholly in LDS (128 KiB of items + 16 KiB of scans) */
+#define M3T_CLS_EVAL_MAX_ROWS 262144    /* capacity: the longest column at all */
+int m3t_cls_eval_append(const float* scores, const float* labels, const int* rows, int B, int C, long long M, float* col_scores,
+                        unsigned char* col_labels, unsigned char* seen, unsigned int* counters, void* stream);
+/* m3t_cls_eval_rank, one launch for all classes (one workgroup per class): the column is ordered descending by its float32 VALUES
+ * (-0.0 ties with +0.0, denormals are kept apart) and scores that compare equal form one threshold group.  With TP, FP the counts after
+ * a group and dTP, dFP its own, P and N the column's positives and negatives:
+ *   AP  = (1 / P) sum_groups dTP TP / (TP + FP)            float64, one correctly rounded division per group, fixed order
+ *   AUC = sum_groups dFP (2 TP_before + dTP) / (2 P N)     the numerator a 64-bit integer (exact), one float64 division
+ * -- scikit-learn's average_precision_score and roc_auc_score with their handling of ties.  per_class [C][4] float64 = AP, AUC, P, N;
+ * AP is NaN without a positive, AUC without a positive or without a negative.  lds_rows: the longest column sorted wholly in LDS, rounded
+ * down to a power of two (0 or above M3T_CLS_EVAL_LDS_ROWS: M3T_CLS_EVAL_LDS_ROWS); a column whose power-of-two padding is longer is
+ * sorted in LDS-sized chunks with the wide strides in ws, m3t_cls_eval_rank_ws_bytes(C, M, lds_rows) bytes (0: not needed), 8-B aligned. */
+size_t m3t_cls_eval_rank_ws_bytes(int C, long long M, int lds_rows);
+int m3t_cls_eval_rank(const float* col_scores, const unsigned char* col_labels, int C, long long M, int lds_rows, void* ws,
+                      size_t ws_bytes, double* per_class, void* stream);
+/* m3t_cls_eval_reduce, one workgroup: out8 float64 = mAP, mAUC (means over the scored classes in class order; NaN when no class is
+ * scored or a counter is above zero), classes scored for AP, for AUC, rows of `seen` still 0, counters[0], counters[1], 0.  out8 and
+ * per_class, kept in one buffer, are the epoch's one read-back. */
+int m3t_cls_eval_reduce(const double* per_class, int C, const unsigned char* seen, long long M, const unsigned int* counters,
+                        double* out8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ M3T_SCAN_FAULT = 16
 M3T_SCAN_WIDE = 32        # room for a second persistent scan beside this one (include/m3t_hip.h)
 M3T_SCAN_SPREAD = 64      # nothing runs beside this launch: 8-clip row blocks on the idle CUs (include/m3t_hip.h)
 M3T_MAX_SCANS = 8
+M3T_CLS_EVAL_LDS_ROWS = 16384      # the longest column m3t_cls_eval_rank sorts wholly in LDS (include/m3t_hip.h)
+M3T_CLS_EVAL_MAX_ROWS = 262144     # its capacity
 M3T_JPEG_TRUNC, M3T_JPEG_CODE, M3T_JPEG_RST, M3T_JPEG_EXTRA = 1, 2, 4, 8      # status bits of m3t_jpeg_decode (include/m3t_hip.h)
 
 _f = C.c_void_p      # device pointer
@@ -221,10 +223,15 @@ SIGNATURES = {
     "m3t_cls_loss_ws_bytes": [_i],
     "m3t_cls_loss": [_f, _i, _i, _i, _f, _f, _f, _f, _f, _z, _s],
     "m3t_tpool_cls_loss": [_f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _z, _s],
+    "m3t_cls_eval_append": [_f, _f, _f, _i, _i, C.c_longlong, _f, _f, _f, _f, _s],
+    "m3t_cls_eval_rank_ws_bytes": [_i, C.c_longlong, _i],
+    "m3t_cls_eval_rank": [_f, _f, _i, C.c_longlong, _i, _f, _z, _f, _s],
+    "m3t_cls_eval_reduce": [_f, _i, _f, C.c_longlong, _f, _f, _s],
 }
 
 RESTYPES = {"m3t_gru_bwd_prepare_floats": C.c_size_t, "m3t_bn_rows_ws_bytes": C.c_size_t, "m3t_bn_planes_ws_bytes": C.c_size_t, "m3t_va_loss_ws_bytes": C.c_size_t, "m3t_bn_cl_ws_bytes": C.c_size_t, "m3t_gn_cl_ws_bytes": C.c_size_t, "m3t_relu_cl_ws_bytes": C.c_size_t, "m3t_cbam_fused_ws_bytes": C.c_size_t,
-            "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t, "m3t_cls_loss_ws_bytes": C.c_size_t, "m3t_jpeg_workspace_bytes": C.c_size_t}
+            "m3t_dense_stats_ws_bytes": C.c_size_t, "m3t_dense_wgrad_ws_bytes": C.c_size_t, "m3t_cls_loss_ws_bytes": C.c_size_t, "m3t_jpeg_workspace_bytes": C.c_size_t,
+            "m3t_cls_eval_rank_ws_bytes": C.c_size_t}
 
 _lib = None
 

@@ -13,6 +13,7 @@ training_step, backward, RCCL all-reduce + clip, fused optimizer step -- plus:
   * validation after every epoch through the module's own validation_step / validation_end (window stitching,
     SURVEY 8(f) f-1) and a best-`val_loss` checkpoint (Lightning's default ModelCheckpoint monitors val_loss, mode min);
     `evaluate()` is the same epoch without a read-back per batch (m3t/evaluate.py), beside `validate()`, which `fit()` calls;
+    `evaluate_cls()` is the multi-label counterpart for the AudioSet stage (m3t/cls_evaluate.py: mAP, mean AUC, d');
   * `{'state_dict': ...}` checkpoints the reference's eval.py loads strictly (eval.py:14-15), with optimizer and
     scheduler state for resume.
 
@@ -152,6 +153,41 @@ class Trainer:
             bar["val_acc_expr"] = m["val_acc_expr"]
         return {"val_loss": m["val_loss"], "progress_bar": bar, "log": dict(m)}
 
+    def evaluate_cls(self, feed, lds_rows=None):
+        """validate() of a multi-label module (AudioSet) with the ranking metrics every published AudioSet figure is given in, scored on
+        the device (m3t/cls_evaluate.py): one append launch per batch, no read-back per batch, one at the end.  `feed`: an epoch feed
+        with plans() / batch(plan) / files (m3t/audioset.py), which says which items a batch holds; the module needs eval_scores(batch).
+        Returns validation_end's dict, val_loss and val_acc with validate()'s bits as Python floats, with val_map / val_auc / val_dprime
+        (and the counts) added to `log` and the three to `progress_bar`; the result stays as self.last_eval (report(), save()).  With
+        world > 1 every rank's scores, labels and items are gathered (one all_gather each) and absorbed, so every rank ranks the whole
+        split and reports the same ranking figures; val_loss / val_acc stay the rank's own shard's, as in validate()."""
+        from .cls_evaluate import ClsEvaluator
+        self.model.eval()
+        ev = None
+        for plan in feed.plans():
+            b = feed.batch(plan)
+            pooled, loss, correct = self.model.eval_scores(b)
+            if ev is None:
+                ev = ClsEvaluator(len(feed.files), pooled.size(1), lds_rows=lds_rows)
+            ev.add(pooled, b["label"], plan.items, loss, correct)
+        self.ddp.agree_on_scan_error()               # as in validate(): nothing else would report a dead scan
+        if ev is None:
+            raise ValueError("evaluate_cls: the feed gave no batch")
+        if self.ddp.world > 1:
+            mine = ev.shard()
+            shards = []
+            for t in mine:                           # DistributedSampler pads: every rank holds the same number of rows
+                parts = [torch.empty_like(t) for _ in range(self.ddp.world)]
+                dist.all_gather(parts, t, group=self.ddp.pg)
+                shards.append(parts)
+            for r in range(self.ddp.world):
+                if r != self.rank:
+                    ev.absorb(shards[0][r], shards[1][r], shards[2][r])
+        res = self.last_eval = ev.finish()
+        m = res.metrics
+        bar = {k: m[k] for k in ("val_loss", "val_acc", "val_map", "val_auc", "val_dprime")}
+        return {"val_loss": m["val_loss"], "progress_bar": bar, "log": dict(m)}
+
     # ------------------------------------------------------------------ rank plumbing
     @property
     def rank(self):
@@ -192,8 +228,9 @@ class Trainer:
                 self.save_checkpoint(os.path.join(self.checkpoint_path, "best.ckpt"))
         return improved
 
-    def fit(self, batches, max_steps=None, log_every=0, val_batches=None, max_epochs=1):
-        """`batches`: an iterable of batch dicts = one epoch (re-iterated per epoch when max_epochs > 1)."""
+    def fit(self, batches, max_steps=None, log_every=0, val_batches=None, max_epochs=1, val_fn=None):
+        """`batches`: an iterable of batch dicts = one epoch (re-iterated per epoch when max_epochs > 1).  val_fn: what scores
+        `val_batches` after an epoch instead of validate(), e.g. evaluate_cls; its dict's val_loss drives end_epoch as before."""
         history = []
         done = 0
         for _ in range(max_epochs):
@@ -212,7 +249,7 @@ class Trainer:
                     history.append(float(out["loss"].detach()))
             val_loss = None
             if val_batches is not None:
-                val_loss = float(self.validate(val_batches)["val_loss"])
+                val_loss = float((val_fn or self.validate)(val_batches)["val_loss"])
             self.end_epoch(val_loss)
             if max_steps is not None and done >= max_steps:
                 break

@@ -66,6 +66,14 @@ class AudioSet(_Base):
             loss, _, correct = ops.pooled_cls_loss(self.audio(x), batch['label'], 'max', 'bce')
         return {'val_loss': loss, 'correct': correct}
 
+    def eval_scores(self, batch):
+        """validation_step's own call with the pooled per-clip logits kept: (pooled [N, 527], val_loss, correct [N]), the input of the
+        device-side evaluation epoch (m3t/cls_evaluate.py, Trainer.evaluate_cls)"""
+        with torch.no_grad():
+            x = self._features(batch['audio'], batch.get('audio_aug'), batch.get('audio_len'))
+            loss, _, correct, pooled, _ = ops.pooled_cls_loss(self.audio(x), batch['label'], 'max', 'bce', return_pooled=True)
+        return pooled, loss, correct
+
     def validation_end(self, outputs):
         return _classification_epoch_end(outputs)
 

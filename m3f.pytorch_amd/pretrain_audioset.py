@@ -13,6 +13,8 @@ m3t/trainer.py and the epoch feed of m3t/audioset.py.
     mono .wav clips of the same names; both splits are uploaded to the device once, before the first step;
   * `--convert_audio` takes the folder as the reference's loader does: clips of any rate, channel count and sample kind (m3t/wav.py's wider
     reader), down-mixed and resampled to 16 kHz on the device when the store is built (m3t.audio.decode_waves); without it such a clip is refused;
+  * `--eval_on_device` sends the epoch's validation through Trainer.evaluate_cls (m3t/cls_evaluate.py): the epoch line also gives mean average
+    precision, mean ROC-AUC and d' over the classes, scored on the device; `best.ckpt` is still chosen by val_loss.  Without it nothing changes;
   * `--gpus` / `--nodes` are accepted and ignored: start one process per GPU with torchrun and pass `--distributed`; the world is torchrun's;
   * `--workers` is accepted and ignored: there is no host-side decoding left to spread;
   * `--test_lr` (the LR range finder) is out of scope and raises.
@@ -38,6 +40,7 @@ def make_parser():
     parser.add_argument('--seed', type=int, default=12345)
     parser.add_argument('--checkpoint', type=str, default='')
     parser.add_argument('--convert_audio', action='store_true', default=SUPPRESS)    # (absent unless given: the reference has no such flag)
+    parser.add_argument('--eval_on_device', action='store_true', default=SUPPRESS)   # (absent unless given, as --convert_audio)
     return AudioSet.add_model_specific_args(parser)
 
 
@@ -67,10 +70,16 @@ def main(hparams):
         train_feed.set_epoch(epoch)
         val_feed.set_epoch(epoch)
         best = trainer.best_val_loss
-        trainer.fit(train_feed, val_batches=val_feed, max_epochs=1)     # (validate and end_epoch are fit's own)
+        on_device = bool(getattr(hparams, 'eval_on_device', False))
+        trainer.fit(train_feed, val_batches=val_feed, max_epochs=1,     # (validate and end_epoch are fit's own)
+                    val_fn=trainer.evaluate_cls if on_device else None)
         if trainer.rank == 0:
-            print('epoch %d: lr %.3g, best val_loss %.6f%s' % (epoch, trainer.lr, trainer.best_val_loss,
-                                                               ' (improved)' if trainer.best_val_loss < best else ''), flush=True)
+            ranking = ''
+            if on_device:
+                m = trainer.last_eval.metrics
+                ranking = ", mAP %.4f, AUC %.4f, d' %.3f" % (m['val_map'], m['val_auc'], m['val_dprime'])
+            print('epoch %d: lr %.3g, best val_loss %.6f%s%s' % (epoch, trainer.lr, trainer.best_val_loss,
+                                                                 ' (improved)' if trainer.best_val_loss < best else '', ranking), flush=True)
 
 
 if __name__ == '__main__':
