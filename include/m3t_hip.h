@@ -957,6 +957,23 @@ int m3t_audio_power_mel(const float* spec, long long R, int bins, int n_mels, co
  * Of `clips` only nf and row_off are read.  T width n_mels < 2^31, amin > 0. */
 int m3t_audio_db_stack(const float* mel, long long R, const long long* clips, int N, int T, int n_mels, int step, int width,
                        float amin, float top_db, float* out, void* stream);
+/* m3t_audio_db_stack with the training-time augmentation of the AudioSet feed, in the same single launch: the reference's spec_augment
+ * (models/audioset_dataset.py:17-55), run as if its load_audio called it on the dB spectrogram [1, n_mels, nf] between power_to_db (:76)
+ * and the stacking (:77-85), and a mix across the batch (mixup; beyond the reference) applied after the masks.
+ * aug: device int [N][20] = n_freq, n_time, partner, 0, (f0, f) x 4, (t0, t) x 4.  mixw: device float [N][2] = lam32, om32.
+ * Per clip n, with db and nf as in m3t_audio_db_stack (the clip's own maximum and floor):
+ *     x[n][t][k n_mels + c] = 0.0f  if t step + k >= nf, or f0 <= c < f0 + f for one of its n_freq frequency masks, or
+ *                                   t0 <= t step + k < t0 + t for one of its n_time time masks       (an assignment: a NaN or inf cell
+ *                                   becomes 0.0f; csrc/audio_aug_core.h is this rule, shared with csrc/audio_aug_host_check.cpp)
+ *                           = db[t step + k][c]  otherwise
+ *     partner == -1:  out[n] = x[n], no multiply
+ *     partner >= 0 :  out[n] = __fadd_rn(__fmul_rn(lam32, x[n]), __fmul_rn(om32, x[partner]))   (x[partner]: that clip's own nf, floor, masks)
+ * One workgroup per OUTPUT clip: it reduces its own maximum and, when mixing, the partner's; no atomics, a rerun gives the same bits.
+ * Counts are clamped into [0, 4]; a mask is only compared with a position, never used as an address; a partner outside [-1, N) gives a
+ * zero clip.  The host (m3t.audio.plan_aug) refuses all of these before the launch.  M3T_EINVAL as m3t_audio_db_stack, and for a null or
+ * misaligned aug / mixw. */
+int m3t_audio_db_stack_aug(const float* mel, long long R, const long long* clips, int N, const int* aug, const float* mixw, int T,
+                           int n_mels, int step, int width, float amin, float top_db, float* out, void* stream);
 /* The AffWild2 route (dataset.py:83-95, :276-278, :302-306) for N pre-extracted tracks in one launch.  mels: flat [total_rows][n_mels];
  * tracks: device long long [N][4] = row_off, n_rows, start, track_len.  out [N][window][width n_mels]:
  *     i' = min(i, track_len - 1)                                      (rows track_len .. window-1 repeat the last: np.pad 'edge', :303-304)
@@ -976,6 +993,14 @@ int m3t_stack_context_batch(const float* mels, long long total_rows, int n_mels,
  * refuses such an item before the launch (m3t.audioset).  M3T_EINVAL: null pointers, items not 8-byte or out not 4-byte aligned, n_files or
  * n_classes <= 0, N < 0; N == 0 returns 0. */
 int m3t_label_rows(const uint8_t* table, long long n_files, int n_classes, const long long* items, int N, float* out, void* stream);
+/* m3t_label_rows for a batch mixed by m3t_audio_db_stack_aug (the mix that follows the reference's spec_augment,
+ * models/audioset_dataset.py:17-55; aug and mixw are that launch's tables, of which only the partner and the two weights are read):
+ *     partner == -1:  out[n][c] = (float) table[items[n]][c]
+ *     partner >= 0 :  out[n][c] = __fadd_rn(__fmul_rn(lam32, (float) table[items[n]][c]), __fmul_rn(om32, (float) table[items[partner]][c]))
+ * An item outside [0, n_files) (the row's own or its partner's) or a partner outside [-1, N) leaves the row untouched and reads nothing.
+ * M3T_EINVAL as m3t_label_rows, and for a null or misaligned aug / mixw. */
+int m3t_label_rows_mix(const uint8_t* table, long long n_files, int n_classes, const long long* items, int N, const int* aug,
+                       const float* mixw, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Wave conversion (csrc/resample.hip; m3t.audio.decode_waves): what `librosa.load(path, sr=16000)` does to a file before the reference

@@ -6,10 +6,13 @@
 //     (m3t_sgemm)              [R, n_fft] x [n_fft, 2 bins]: ONE DFT product for the batch
 //     m3t_audio_power_mel      re^2 + im^2 and the (sparse) mel filterbank -> [R, n_mels]
 //     m3t_audio_db_stack       per-clip power_to_db (the clip's own maximum over ALL its rows) + context stack -> [N, T, width n_mels]
+//     m3t_audio_db_stack_aug   the same launch with the reference's spec_augment masks (audioset_dataset.py:17-55; the cell rule is
+//                              audio_aug_core.h) and a mix with a partner clip of the batch, opt-in: training-time augmentation
 //     m3t_stack_context_batch  pre-extracted mel tracks -> [N, window, width n_mels] (edge padding, zero clips)
 // HBM- and latency-bound glue: no atomics, every reduction in a fixed order, no synchronisation inside a call.  Device-side tables are
 // checked against the buffers' sizes in the kernels: a bad entry writes zeros (or nothing), it never leaves an allocation.
 #include "common.h"
+#include "audio_aug_core.h"
 
 namespace {
 
@@ -131,6 +134,74 @@ __global__ __launch_bounds__(256) void db_stack_kernel(const float* __restrict__
     }
 }
 
+// db_stack_kernel's per-clip half for the augmented route: the clip's rows and the floor of its own power_to_db
+struct AugClip {
+    const float* m;
+    long long nf;
+    float floor_db;
+};
+
+// the clip `n` of the table: its rows (a bad entry: a zero clip) and, by the fixed-order workgroup maximum of db_stack_kernel, its floor
+__device__ __forceinline__ AugClip aug_clip(const float* __restrict__ mel, long long R, const long long* __restrict__ clips, long long n,
+                                            int n_mels, float amin, float top_db, float ref, float* red) {
+    const long long* c = clips + 8 * n;
+    long long nf = c[C_NF], ro = c[C_ROW];
+    if (nf <= 0 || ro < 0 || ro > R - nf) { nf = 0; ro = 0; }
+    const float* m = mel + ro * n_mels;
+    const long long cells = nf * n_mels;
+    float mx = -3.0e38f;
+    for (long long i = threadIdx.x; i < cells; i += 256) mx = fmaxf(mx, 10.0f * log10f(fmaxf(amin, m[i])));
+    mx = wave_max(mx);
+    __syncthreads();                                         // (red is free: the previous clip's maximum has been read)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    return {m, nf, (mx - ref) - top_db};
+}
+
+// the value cell i of the stacked rows takes from one clip: db_stack_kernel's, or exactly 0.0 where audio_aug_core.h says so
+__device__ __forceinline__ float aug_value(const AugClip& c, const int* p, int n_mels, int step, int width, float amin, float top_db,
+                                           float ref, int i) {
+    const long long src = aug_cell(p, c.nf, n_mels, step, width, i);
+    if (src < 0) return 0.f;
+    float v = 10.0f * log10f(fmaxf(amin, c.m[src])) - ref;
+    if (top_db >= 0.f) v = fmaxf(v, c.floor_db);
+    return v;
+}
+
+// db_stack_kernel with the reference's spec_augment (audioset_dataset.py:17-55) and a mix across the batch.  One workgroup per OUTPUT
+// clip n: x[n] = its own masked dB rows (its own nf, floor and masks); with a partner p >= 0 also x[p] (the partner's nf, floor and
+// masks), and out[n] = lam32 x[n] + om32 x[p] in two rounded products and one rounded sum.  Without a partner x[n] is written as it is.
+__global__ __launch_bounds__(256) void db_stack_aug_kernel(const float* __restrict__ mel, long long R, const long long* __restrict__ clips,
+                                                           int N, const int* __restrict__ aug, const float* __restrict__ mixw, int T,
+                                                           int n_mels, int step, int width, float amin, float top_db,
+                                                           float* __restrict__ out) {
+    __shared__ float red[4];
+    const long long n = blockIdx.x;
+    const int* pa = aug + AUG_INTS * n;
+    const int partner = pa[AUG_PARTNER];
+    const int W = width * n_mels;
+    float* o = out + n * T * W;
+    if (partner < -1 || partner >= N) {                      // (a bad table: a zero clip; uniform per workgroup)
+        for (int i = threadIdx.x; i < T * W; i += 256) o[i] = 0.f;
+        return;
+    }
+    const float ref = 10.0f * log10f(fmaxf(amin, 1.0f));
+    const AugClip a = aug_clip(mel, R, clips, n, n_mels, amin, top_db, ref, red);
+    if (partner < 0) {
+        for (int i = threadIdx.x; i < T * W; i += 256) o[i] = aug_value(a, pa, n_mels, step, width, amin, top_db, ref, i);
+        return;
+    }
+    const AugClip b = aug_clip(mel, R, clips, partner, n_mels, amin, top_db, ref, red);
+    const int* pb = aug + AUG_INTS * (long long)partner;
+    const float lam = mixw[2 * n], om = mixw[2 * n + 1];
+    for (int i = threadIdx.x; i < T * W; i += 256) {
+        const float xa = aug_value(a, pa, n_mels, step, width, amin, top_db, ref, i);
+        const float xb = aug_value(b, pb, n_mels, step, width, amin, top_db, ref, i);
+        o[i] = __fadd_rn(__fmul_rn(lam, xa), __fmul_rn(om, xb));
+    }
+}
+
 // models/dataset.py:83-95 and :276-306 for N tracks: out[n][i] = the row m3t_stack_context gives for frame min(i, track_len - 1)
 // (np.pad 'edge' of a short window), zeros for track_len == 0 (an invalid clip: fps < 15)
 __global__ __launch_bounds__(256) void stack_batch_kernel(const float* __restrict__ mels, long long total_rows, int n_mels,
@@ -204,6 +275,21 @@ extern "C" int m3t_audio_db_stack(const float* mel, long long R, const long long
         return M3T_EINVAL;
     if (((uintptr_t)mel % 4) != 0 || ((uintptr_t)clips % 8) != 0 || ((uintptr_t)out % 4) != 0) return M3T_EINVAL;
     db_stack_kernel<<<(unsigned)N, 256, 0, (hipStream_t)stream>>>(mel, R, clips, T, n_mels, step, width, amin, top_db, out);
+    M3T_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int m3t_audio_db_stack_aug(const float* mel, long long R, const long long* clips, int N, const int* aug, const float* mixw, int T,
+                                      int n_mels, int step, int width, float amin, float top_db, float* out, void* stream) {
+    if (N < 0 || T < 0) return M3T_EINVAL;
+    if (N == 0 || T == 0) return 0;
+    if (!mel || !clips || !aug || !mixw || !out || R <= 0 || n_mels <= 0 || step <= 0 || width <= 0 || amin <= 0.f ||
+        (long long)T * width * n_mels > 0x7fffffffll)
+        return M3T_EINVAL;
+    if (((uintptr_t)mel % 4) != 0 || ((uintptr_t)clips % 8) != 0 || ((uintptr_t)aug % 4) != 0 || ((uintptr_t)mixw % 4) != 0 ||
+        ((uintptr_t)out % 4) != 0)
+        return M3T_EINVAL;
+    db_stack_aug_kernel<<<(unsigned)N, 256, 0, (hipStream_t)stream>>>(mel, R, clips, N, aug, mixw, T, n_mels, step, width, amin, top_db, out);
     M3T_LAUNCH_CHECK();
     return 0;
 }

@@ -180,8 +180,10 @@ SIGNATURES = {
     "m3t_audio_frame_batch": [_f, _i, C.c_longlong, _f, _i, C.c_longlong, _i, _i, _f, _f, _s],
     "m3t_audio_power_mel": [_f, C.c_longlong, _i, _i, _f, _f, _i, _f, _s],
     "m3t_audio_db_stack": [_f, C.c_longlong, _f, _i, _i, _i, _i, _i, C.c_float, C.c_float, _f, _s],
+    "m3t_audio_db_stack_aug": [_f, C.c_longlong, _f, _i, _f, _f, _i, _i, _i, _i, C.c_float, C.c_float, _f, _s],
     "m3t_stack_context_batch": [_f, C.c_longlong, _i, _f, _i, _i, _i, _i, _f, _s],
     "m3t_label_rows": [_f, C.c_longlong, _i, _f, _i, _f, _s],
+    "m3t_label_rows_mix": [_f, C.c_longlong, _i, _f, _i, _f, _f, _f, _s],
     "m3t_wave_convert": [_f, C.c_longlong, _f, _i, C.c_longlong, _i, _f, _f, C.c_longlong, _f, C.c_longlong, _s],
     "m3t_video_ingest": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],
     "m3t_video_ingest_half": [_f, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _i, _i, _f, _s],

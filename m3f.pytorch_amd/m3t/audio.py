@@ -23,6 +23,9 @@ temporal crop with np.pad 'wrap', the spectrogram above, the context stack) in t
   draw_audioset(tot, length, training)   one clip's draws, consuming `random` in the reference's order
   plan_waves(...)                        host validation + the per-clip table, before anything touches a device
   ingest(waves, aug, length)             m3t_audio_frame_batch -> m3t_sgemm (ONE DFT product) -> m3t_audio_power_mel -> m3t_audio_db_stack
+  draw_spec_augment(tau, F, T, ..)       the mask draws of the reference's spec_augment (`audioset_dataset.py:17-55`), in its order
+  plan_aug(aug, table, mix)              host validation + the two tables of the augmented last kernel (m3t_audio_db_stack_aug): masks from
+                                         the draws, mix = (partner, lam); None when neither is present, and the call is what it was
   load_audio_batch(mels, starts, ...)    the AffWild2 loader's collate step (`models/dataset.py:83-95, :276-306`): N pre-extracted tracks
                                          -> [N, window, 200] in one launch, edge padding and the "fps < 15 -> zeros" rule included
 
@@ -148,17 +151,111 @@ FPS_VALUES = [15.0, 17.0, 19.0, 22.0, 23.976, 24.0, 25.0, 29.97, 30.0]      # au
 _MEL_SPARSE = {}
 
 
-def draw_audioset(tot_samples, length, training):
+MAX_MASKS = 4                           # masks of each kind a clip may carry (csrc/audio_aug_core.h)
+_AUG_INTS = 20                          # n_freq, n_time, partner, 0, (f0, f) x 4, (t0, t) x 4
+
+
+def draw_spec_augment(tau, F=20, T=20, n_freq=1, n_time=1, name="clip"):
+    """The draws of the reference's spec_augment (models/audioset_dataset.py:17-55) for a spectrogram [1, 40, tau], consuming np.random and
+    `random` in its order: per frequency mask f = int(np.random.uniform(0.0, F)) then f0 = random.randint(0, 40 - f); then per time mask
+    t = int(np.random.uniform(0.0, T)) then t0 = random.randint(0, tau - t).  -> {"fmask": [(f0, f), ..], "tmask": [(t0, t), ..]}: bands
+    f0 .. f0 + f - 1 and frames t0 .. t0 + t - 1 become 0.0.  A draw the reference's randint would refuse (f > 40, t > tau) is a
+    ValueError that names the clip; so are more than MAX_MASKS masks of a kind.  Host only."""
+    tau, n_freq, n_time = int(tau), int(n_freq), int(n_time)
+    if not (0 <= n_freq <= MAX_MASKS and 0 <= n_time <= MAX_MASKS):
+        raise ValueError("spec_augment: %s: %d frequency and %d time masks asked for; 0 .. %d of each are taken" % (name, n_freq, n_time, MAX_MASKS))
+    fmask, tmask = [], []
+    for _ in range(n_freq):
+        f = int(np.random.uniform(low=0.0, high=F))
+        if f > N_MELS:
+            raise ValueError("spec_augment: %s: a frequency mask of %d bands does not fit the %d there are" % (name, f, N_MELS))
+        fmask.append((random.randint(0, N_MELS - f), f))
+    for _ in range(n_time):
+        t = int(np.random.uniform(low=0.0, high=T))
+        if t > tau:
+            raise ValueError("spec_augment: %s: a time mask of %d frames does not fit the %d there are" % (name, t, tau))
+        tmask.append((random.randint(0, tau - t), t))
+    return {"fmask": fmask, "tmask": tmask}
+
+
+def draw_audioset(tot_samples, length, training, spec_aug=None, name="clip"):
     """One clip's draws of models/audioset_dataset.py:60-69 for a decoded clip of `tot_samples` samples: random.choice(FPS_VALUES) (training
     only; 30.0 otherwise), nsamples = int(length / fps * 16000), then random.randint(0, tot' - nsamples) (training) or the centre, where
-    tot' = nsamples + 5 when the clip is shorter than nsamples (the np.pad(..., 'wrap') of :65-68) and tot_samples otherwise."""
+    tot' = nsamples + 5 when the clip is shorter than nsamples (the np.pad(..., 'wrap') of :65-68) and tot_samples otherwise.
+    spec_aug: None, or draw_spec_augment's keyword arguments (F, T, n_freq, n_time): a TRAINING draw then goes on with that function's
+    draws for tau = 1 + nsamples // hop, after the ones above, and carries its two keys; an evaluation draw never does."""
     fps = random.choice(FPS_VALUES) if training else 30.0
     nsamples = int(length / fps * 16000)
     tot = int(tot_samples)
     if nsamples > tot:
         tot = nsamples + 5
     start = random.randint(0, tot - nsamples) if training else (tot - nsamples) // 2
-    return {"fps": fps, "hop": hop_length(fps), "start": start, "nsamples": nsamples}
+    d = {"fps": fps, "hop": hop_length(fps), "start": start, "nsamples": nsamples}
+    if training and spec_aug is not None:
+        d.update(draw_spec_augment(1 + nsamples // d["hop"], name=name, **spec_aug))
+    return d
+
+
+def plan_aug(aug, table, mix=None):
+    """Host validation of the augmentation of an ingest call, before anything touches a device.  aug: the clips' draws (those that carry
+    draw_spec_augment's "fmask" / "tmask" are masked); table: plan_waves' for the same clips; mix: None or (partner int [N], lam float [N]).
+    -> None when no draw carries a mask and mix is None: the call takes the un-augmented route.  Otherwise (ints int32 [N, 20], weights
+    float32 [N, 2]) of include/m3t_hip.h (m3t_audio_db_stack_aug): counts, partner (-1 without mix), the mask pairs; lam32 =
+    np.float32(lam) and om32 = np.float32(1) - lam32.  ValueError, with the clip named, for more than MAX_MASKS masks of a kind, a mask
+    outside [0, 40] / [0, nf], a partner outside the batch, a lam outside [0, 1]."""
+    N = int(table.shape[0])
+    masked = aug is not None and any(("fmask" in a or "tmask" in a) for a in aug)
+    if not masked and mix is None:
+        return None
+    if aug is None:
+        raise ValueError("ingest: mix goes with training draws; aug=None (the evaluation draws) is never augmented")
+    ints = np.zeros((N, _AUG_INTS), np.int32)
+    ints[:, 2] = -1
+    weights = np.zeros((N, 2), np.float32)
+    weights[:, 0] = 1.0
+    for n, a in enumerate(aug):
+        for kind, (key, col, limit, what) in enumerate((("fmask", 4, N_MELS, "bands"), ("tmask", 12, int(table[n, 5]), "frames"))):
+            pairs = list(a.get(key, ()))
+            if len(pairs) > MAX_MASKS:
+                raise ValueError("ingest: clip %d: %d masks under %r; at most %d are taken" % (n, len(pairs), key, MAX_MASKS))
+            ints[n, kind] = len(pairs)
+            for q, (lo, width) in enumerate(pairs):
+                lo, width = int(lo), int(width)
+                if lo < 0 or width < 0 or lo + width > limit:
+                    raise ValueError("ingest: clip %d: mask %s %d .. %d lies outside the clip's %d" % (n, what, lo, lo + width, limit))
+                ints[n, col + 2 * q], ints[n, col + 2 * q + 1] = lo, width
+    if mix is not None:
+        partner, lam = np.asarray(mix[0]), np.asarray(mix[1], np.float64)
+        if partner.shape != (N,) or lam.shape != (N,) or not np.issubdtype(partner.dtype, np.integer):
+            raise ValueError("ingest: mix needs (partner int [%d], lam float [%d])" % (N, N))
+        for n in np.flatnonzero((partner < 0) | (partner >= N)):
+            raise ValueError("ingest: clip %d: its partner %d is outside the batch of %d" % (n, partner[n], N))
+        for n in np.flatnonzero(~((lam >= 0.0) & (lam <= 1.0))):
+            raise ValueError("ingest: clip %d: lam %r is outside [0, 1]" % (n, float(lam[n])))
+        ints[:, 2] = partner
+        weights[:, 0] = lam.astype(np.float32)
+        weights[:, 1] = np.float32(1) - weights[:, 0]
+    return ints, weights
+
+
+def pack_tables(table, tables, extra=None):
+    """plan_waves' table, plan_aug's two (or None) and an optional int64 tail as ONE int64 array, so that they reach the device in one copy,
+    and the function that cuts the device copy up again: -> (flat int64 array, split(device tensor) -> (tab, (ints, weights) | None, tail))"""
+    N = int(table.shape[0])
+    parts = [table.reshape(-1)]
+    if tables is not None:
+        parts += [np.ascontiguousarray(tables[0]).reshape(-1).view(np.int64), np.ascontiguousarray(tables[1]).reshape(-1).view(np.int64)]
+    if extra is not None:
+        parts.append(np.asarray(extra, np.int64).reshape(-1))
+    a = 8 * N                                    # in int64 words: the clip table, then 20 int32 and 2 float32 per clip, then the tail
+    m = a + (_AUG_INTS // 2) * N
+    b = m + N if tables is not None else a
+
+    def split(dev):
+        aug_tab = None if tables is None else (dev[a:m].view(torch.int32), dev[m:b].view(torch.float32))
+        return dev[:a], aug_tab, dev[b:]
+
+    return np.concatenate(parts), split
 
 
 def plan_waves(waves, aug=None, length=32, lengths=None, offsets=None):
@@ -257,30 +354,46 @@ def _mel_sparse(device):
     return c
 
 
-def ingest(waves, aug=None, length=32, lengths=None, pad_mode="constant", top_db=80.0, offsets=None):
+def ingest(waves, aug=None, length=32, lengths=None, pad_mode="constant", top_db=80.0, offsets=None, mix=None):
     """waves: decoded 16 kHz PCM, int16 or float32: [N, S] (tensor or array; `lengths` int [N] for ragged clips stored in rows of S), a
     list of 1-D arrays, or -- with `offsets` and `lengths`, int [N] -- one flat buffer read in place (plan_waves' store form: nothing is
     copied when it lives on the device).  A host tensor is copied to the device with non_blocking=True -- pin it to overlap the copy.
     aug: one draw per clip (draw_audioset) or None = the evaluation draws (30 fps, centred crop).  -> float32 device tensor
     [N, length, 200]: per clip what load_audio(melspec_db(crop, fps), 0, length) gives (audioset_dataset.py:58-87), the dB floor taken from the clip's own maximum.
-    Everything is validated on the host first (ValueError); the per-clip table reaches the device in one copy; three kernels and one GEMM."""
+    Everything is validated on the host first (ValueError); the per-clip table reaches the device in one copy; three kernels and one GEMM.
+    Training-time augmentation, opt-in (plan_aug): draws that carry draw_spec_augment's "fmask" / "tmask" have those bands and frames of
+    their dB spectrogram set to 0.0 before the stack (the reference's spec_augment, audioset_dataset.py:17-55); mix = (partner, lam) then
+    gives out[n] = lam32[n] x[n] + om32[n] x[partner[n]] over the masked rows x.  Both happen inside the last kernel
+    (m3t_audio_db_stack_aug in place of m3t_audio_db_stack): still three kernels, one GEMM and one table copy.  With neither present
+    the call is what it was."""
     if pad_mode not in ("constant", "reflect"):
         raise ValueError("pad_mode must be 'constant' or 'reflect'")
     wave, table, R = plan_waves(waves, aug, length, lengths, offsets)
+    tables = plan_aug(aug, table, mix)
     if not torch.cuda.is_available():
         raise M3THipError("m3t.audio needs the GPU: the M3T path has no CPU fallback")
     dev = wave.device if wave.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    tab = torch.from_numpy(table.reshape(-1)).to(dev, non_blocking=True)
-    return ingest_planned(wave.to(dev, non_blocking=True), tab, table.shape[0], R, length, pad_mode, top_db)
+    if tables is None:
+        tab = torch.from_numpy(table.reshape(-1)).to(dev, non_blocking=True)
+        return ingest_planned(wave.to(dev, non_blocking=True), tab, table.shape[0], R, length, pad_mode, top_db)
+    flat, split = pack_tables(table, tables)
+    tab, aug_tab, _ = split(torch.from_numpy(flat).to(dev, non_blocking=True))
+    return ingest_planned(wave.to(dev, non_blocking=True), tab, table.shape[0], R, length, pad_mode, top_db, aug_tab)
 
 
-def ingest_planned(wave, tab, N, R, length=32, pad_mode="constant", top_db=80.0):
+def ingest_planned(wave, tab, N, R, length=32, pad_mode="constant", top_db=80.0, aug_tab=None):
     """ingest's launches for a batch that is planned and on the device: wave, the flat sample buffer; tab, plan_waves' table as a device
-    int64 tensor (N * 8 values, 8-byte aligned -- it may be a slice of a larger upload); R, the table's row count."""
+    int64 tensor (N * 8 values, 8-byte aligned -- it may be a slice of a larger upload); R, the table's row count; aug_tab, None or
+    plan_aug's two tables on the device (int32, N * 20 values; float32, N * 2 values; slices of the same upload, pack_tables)."""
     if pad_mode not in ("constant", "reflect"):
         raise ValueError("pad_mode must be 'constant' or 'reflect'")
     if not (wave.is_cuda and tab.is_cuda and tab.dtype == torch.int64 and tab.is_contiguous() and tab.numel() == 8 * N and wave.dim() == 1):
         raise ValueError("ingest_planned: a flat device buffer and a device int64 table of %d x 8 values are needed" % N)
+    if aug_tab is not None:
+        ai, af = aug_tab
+        if not (ai.is_cuda and af.is_cuda and ai.dtype == torch.int32 and af.dtype == torch.float32 and ai.is_contiguous() and af.is_contiguous()
+                and ai.numel() == _AUG_INTS * N and af.numel() == 2 * N):
+            raise ValueError("ingest_planned: the augmentation needs device tables of %d x %d int32 and %d x 2 float32 values" % (N, _AUG_INTS, N))
     dev = wave.device
     N, T, R, bins = int(N), int(length), int(R), 1 + N_FFT // 2
     win, dft, _ = _constants(dev)
@@ -294,7 +407,11 @@ def ingest_planned(wave, tab, N, R, length=32, pad_mode="constant", top_db=80.0)
     mel = torch.empty(R, N_MELS, dtype=torch.float32, device=dev)
     _lib.check(L.m3t_audio_power_mel(_p(spec), R, bins, N_MELS, _p(weights), bands.data_ptr(), nnz, _p(mel), st), "m3t_audio_power_mel")
     out = torch.empty(N, T, 5 * N_MELS, dtype=torch.float32, device=dev)
-    _lib.check(L.m3t_audio_db_stack(_p(mel), R, tab.data_ptr(), N, T, N_MELS, 3, 5, 1e-10, float(top_db), _p(out), st), "m3t_audio_db_stack")
+    if aug_tab is None:
+        _lib.check(L.m3t_audio_db_stack(_p(mel), R, tab.data_ptr(), N, T, N_MELS, 3, 5, 1e-10, float(top_db), _p(out), st), "m3t_audio_db_stack")
+    else:
+        _lib.check(L.m3t_audio_db_stack_aug(_p(mel), R, tab.data_ptr(), N, aug_tab[0].data_ptr(), aug_tab[1].data_ptr(), T, N_MELS, 3, 5, 1e-10,
+                                            float(top_db), _p(out), st), "m3t_audio_db_stack_aug")
     return out
 
 

@@ -24,9 +24,14 @@ no sample crosses the bus after the store is built, and nothing is read back.
 Everything down to "which clips, which draws" runs without a GPU and without initialising one (the clips' lengths come from the files'
 headers); the store is built when the first batch is asked for (or by build_store()).
 
+Training-time augmentation, opt-in and for the train split only: `spec_augment` draws the reference's own frequency and time masks
+(`audioset_dataset.py:17-55`, m3t.audio.draw_spec_augment) per item, after that item's draws above; `mixup_alpha` draws per batch, right
+after its items, `np.random.beta(alpha, alpha, N)` and then `np.random.permutation(N)`.  Both are applied inside the launches a batch
+already has (m3t_audio_db_stack_aug, m3t_label_rows_mix); with both off the plans, the generators and the launches are what they were.
+
 Without `convert` a clip that is not 16 kHz, 16-bit, mono is refused with its name, as before.  Out of scope: a
-disk cache or a host arena for the store (balanced train is about 7 GB of int16, 14 GB of float32: it fits), prefetch threads, `spec_augment` (defined by the
-reference, never called by it), the VoxCeleb2 loader, multi-GPU measurements (the sharding rule is tested on the host).
+disk cache or a host arena for the store (balanced train is about 7 GB of int16, 14 GB of float32: it fits), prefetch threads, time
+warping (the reference removed it), balanced sampling, the VoxCeleb2 loader, multi-GPU measurements (the sharding rule is tested on the host).
 """
 import os
 import random
@@ -137,7 +142,8 @@ def scan_audioset(path, split, convert=False):
 def plan_batch(wave, offsets, lengths, items, draws, window):
     """Host validation of one batch out of a store, before anything touches a device: wave, the store's flat buffer (only its size and dtype
     are looked at); offsets, lengths int64 [F]; items, the clips' indices; draws, one m3t.audio.draw_audioset dict per item or None.
-    -> (items int64 [N], table int64 [N, 8], R) -- m3t.audio.plan_waves' store form.  ValueError for an item outside the store."""
+    -> (items int64 [N], table int64 [N, 8], R) -- m3t.audio.plan_waves' store form.  ValueError for an item outside the store.
+    (The augmentation of a batch is validated beside it: m3t.audio.plan_aug on the same draws and table.)"""
     items = np.asarray(items)
     if items.ndim != 1 or items.size == 0 or not np.issubdtype(items.dtype, np.integer):
         raise ValueError("WaveStore: a batch needs a non-empty 1-D list of clip indices")
@@ -224,56 +230,78 @@ class WaveStore:
     def plan(self, items, draws, window):
         return plan_batch(self.wave, self.offsets, self.lengths, items, draws, window)
 
-    def label_rows(self, items_dev, N):
-        """float32 [N, n_classes]: the rows of the clips `items_dev` (device int64 [N], validated by the caller) -- one launch"""
+    def label_rows(self, items_dev, N, mix=None):
+        """float32 [N, n_classes]: the rows of the clips `items_dev` (device int64 [N], validated by the caller) -- one launch.
+        mix: None, or the batch's two augmentation tables on the device (m3t.audio.plan_aug's, validated by the caller): a row with a
+        partner is lam32 * row + om32 * the partner item's row (m3t_label_rows_mix)."""
         if self.label_table is None:
             raise ValueError("WaveStore: built without labels")
         out = torch.empty(N, self.n_classes, dtype=torch.float32, device=self.device)
-        _lib.check(lib().m3t_label_rows(self.label_table.data_ptr(), len(self.files), self.n_classes, items_dev.data_ptr(), N,
-                                      out.data_ptr(), _stream()), "m3t_label_rows")
+        if mix is None:
+            _lib.check(lib().m3t_label_rows(self.label_table.data_ptr(), len(self.files), self.n_classes, items_dev.data_ptr(), N,
+                                          out.data_ptr(), _stream()), "m3t_label_rows")
+        else:
+            _lib.check(lib().m3t_label_rows_mix(self.label_table.data_ptr(), len(self.files), self.n_classes, items_dev.data_ptr(), N,
+                                              mix[0].data_ptr(), mix[1].data_ptr(), out.data_ptr(), _stream()), "m3t_label_rows_mix")
         return out
 
-    def batch(self, items, draws=None, window=32, pad_mode="constant"):
+    def batch(self, items, draws=None, window=32, pad_mode="constant", mix=None):
         """{'audio': float32 [N, window, 200], 'label': float32 [N, n_classes]} of the clips `items` with `draws` (None: the evaluation
-        draws), queued on the current stream.  Host validation, ONE table upload, the label launch, the ingest's launches."""
+        draws), queued on the current stream.  Host validation, ONE table upload, the label launch, the ingest's launches.
+        Draws that carry masks (m3t.audio.draw_spec_augment) and mix = (partner, lam) augment the batch inside those same launches
+        (m3t.audio.ingest); the labels of a mixed batch are mixed with the same weights.  Without either nothing changes."""
         if pad_mode not in ("constant", "reflect"):
             raise ValueError("pad_mode must be 'constant' or 'reflect'")
         items, table, R = self.plan(items, draws, window)
+        tables = _audio.plan_aug(draws, table, mix)
         N = int(items.shape[0])
-        tab = torch.from_numpy(np.concatenate([table.reshape(-1), items])).to(self.device, non_blocking=True)
-        out = {"audio": _audio.ingest_planned(self.wave, tab[:8 * N], N, R, window, pad_mode)}
+        if tables is None:
+            tab = torch.from_numpy(np.concatenate([table.reshape(-1), items])).to(self.device, non_blocking=True)
+            out = {"audio": _audio.ingest_planned(self.wave, tab[:8 * N], N, R, window, pad_mode)}
+            if self.label_table is not None:
+                out["label"] = self.label_rows(tab[8 * N:], N)
+            return out
+        flat, split = _audio.pack_tables(table, tables, items)
+        tab, aug_tab, items_dev = split(torch.from_numpy(flat).to(self.device, non_blocking=True))
+        out = {"audio": _audio.ingest_planned(self.wave, tab, N, R, window, pad_mode, aug_tab=aug_tab)}
         if self.label_table is not None:
-            out["label"] = self.label_rows(tab[8 * N:], N)
+            out["label"] = self.label_rows(items_dev, N, aug_tab if mix is not None else None)
         return out
 
 
 # ---- the epoch plan -------------------------------------------------------------------------------------------------------------------
 class BatchPlan:
     """One batch of an epoch.  items: the clips' indices into the scan's files, as the sampler gave them; aug: one m3t.audio.draw_audioset
-    dict per item; index: the batch's position in the epoch."""
-    __slots__ = ("items", "aug", "index")
+    dict per item; index: the batch's position in the epoch; mix: None, or the batch's mixup draws (partner [N] ints, lam [N] floats:
+    positions in the batch and the float64 weights as drawn)."""
+    __slots__ = ("items", "aug", "index", "mix")
 
-    def __init__(self, items, aug, index):
-        self.items, self.aug, self.index = items, aug, index
+    def __init__(self, items, aug, index, mix=None):
+        self.items, self.aug, self.index, self.mix = items, aug, index, mix
 
     def __eq__(self, other):
-        return isinstance(other, BatchPlan) and self.items == other.items and self.index == other.index and self.aug == other.aug
+        return (isinstance(other, BatchPlan) and self.items == other.items and self.index == other.index and self.aug == other.aug
+                and self.mix == other.mix)
 
     def __repr__(self):
-        return "BatchPlan(index=%d, items=%r, aug=%r)" % (self.index, self.items, self.aug)
+        return "BatchPlan(index=%d, items=%r, aug=%r%s)" % (self.index, self.items, self.aug, "" if self.mix is None else ", mix=%r" % (self.mix,))
 
 
 class _Draws(Dataset):
-    """the data set the plan's DataLoader reads: item i is (i, draw), drawn when it is read"""
+    """the data set the plan's DataLoader reads: item i is (i, draw), drawn when it is read; spec_aug: m3t.audio.draw_audioset's (the mask
+    draws of a training item, after its own), names: the clips' files, for a refusal"""
 
-    def __init__(self, lengths, window, training):
-        self.lengths, self.window, self.training = lengths, window, training
+    def __init__(self, lengths, window, training, spec_aug=None, names=None):
+        self.lengths, self.window, self.training, self.spec_aug, self.names = lengths, window, training, spec_aug, names
 
     def __len__(self):
         return len(self.lengths)
 
     def __getitem__(self, i):
-        return int(i), _audio.draw_audioset(int(self.lengths[i]), self.window, self.training)
+        if self.spec_aug is None:
+            return int(i), _audio.draw_audioset(int(self.lengths[i]), self.window, self.training)
+        return int(i), _audio.draw_audioset(int(self.lengths[i]), self.window, self.training, self.spec_aug,
+                                            "clip %d" % i if self.names is None else str(self.names[i]))
 
 
 class AudioSetFeed:
@@ -283,13 +311,16 @@ class AudioSetFeed:
     world: world > 1 shards the indices with torch's DistributedSampler in both splits (the reference's default one: shuffled, seed 0,
     set_epoch(epoch)).  sampler: overrides the index order -- any iterable of indices, or a callable that makes one from the data set.
     pad_mode: the STFT's padding, m3t.audio's ('constant' is librosa >= 0.10's).  convert: the scan's (scan_audioset(..., convert=True));
-    given here it must agree with it, since the planned lengths are the scan's.
+    given here it must agree with it, since the planned lengths are the scan's.  spec_augment: None, True (the reference's defaults) or a
+    dict of F, T, n_freq, n_time (defaults 20, 20, 1, 1; at most 4 masks of a kind); mixup_alpha: 0.0 or the Beta distribution's
+    parameter.  Both are ignored for the val split.
 
     Construction reads the clips' headers (Scan.lengths) and touches no device.  plan_epoch(epoch) is host only.  Iterating builds the
     WaveStore on the current device at the first batch and yields, per BatchPlan, WaveStore.batch(items, draws): validated for the whole
     batch before its first launch, queued on the current stream, nothing read back."""
 
-    def __init__(self, scan, window, batch_size, split, rank=0, world=1, sampler=None, pad_mode="constant", convert=None):
+    def __init__(self, scan, window, batch_size, split, rank=0, world=1, sampler=None, pad_mode="constant", convert=None,
+                 spec_augment=None, mixup_alpha=0.0):
         if scan.split != split:
             raise ValueError("AudioSetFeed: split is %r, the folder was scanned for %r" % (split, scan.split))
         self.convert = bool(getattr(scan, "convert", False)) if convert is None else bool(convert)
@@ -308,7 +339,22 @@ class AudioSetFeed:
         self.training = split == "train"
         self.files = list(scan.files)
         self.lengths = scan.lengths()
-        self._draws = _Draws(self.lengths, self.window, self.training)
+        # training-time augmentation: the validation split never draws or applies either
+        self.spec_augment, self.mixup_alpha = None, 0.0
+        if self.training and spec_augment is not None and spec_augment is not False:
+            given = {} if spec_augment is True else dict(spec_augment)
+            if set(given) - {"F", "T", "n_freq", "n_time"}:
+                raise ValueError("AudioSetFeed: spec_augment takes F, T, n_freq, n_time, got %r" % (sorted(given),))
+            sa = {"F": 20, "T": 20, "n_freq": 1, "n_time": 1}
+            sa.update(given)
+            if not (0 <= int(sa["n_freq"]) <= _audio.MAX_MASKS and 0 <= int(sa["n_time"]) <= _audio.MAX_MASKS) or sa["F"] < 0 or sa["T"] < 0:
+                raise ValueError("AudioSetFeed: spec_augment needs F, T >= 0 and 0 .. %d masks of each kind, got %r" % (_audio.MAX_MASKS, sa))
+            self.spec_augment = sa
+        if self.training and mixup_alpha:
+            if not float(mixup_alpha) > 0.0:
+                raise ValueError("AudioSetFeed: mixup_alpha must be positive (0: no mixup), got %r" % (mixup_alpha,))
+            self.mixup_alpha = float(mixup_alpha)
+        self._draws = _Draws(self.lengths, self.window, self.training, self.spec_augment, self.files)
         self._sampler = sampler(self._draws) if callable(sampler) else sampler
         self._dist = None
         if self._sampler is None and self.world > 1:
@@ -334,7 +380,11 @@ class AudioSetFeed:
         elif hasattr(self._sampler, "set_epoch"):
             self._sampler.set_epoch(self.epoch)
         for b, rows in enumerate(self._loader):
-            yield BatchPlan([i for i, _ in rows], [d for _, d in rows], b)
+            mix = None
+            if self.mixup_alpha:                # right after the items' draws: the weights, then the partners
+                lam = np.random.beta(self.mixup_alpha, self.mixup_alpha, size=len(rows))
+                mix = (np.random.permutation(len(rows)).tolist(), lam.tolist())
+            yield BatchPlan([i for i, _ in rows], [d for _, d in rows], b, mix)
 
     def plan_epoch(self, epoch=None):
         """-> [BatchPlan] of one epoch (default: the current one); host only, no device is touched.  Consumes the epoch's random numbers."""
@@ -362,7 +412,7 @@ class AudioSetFeed:
     def batch(self, plan):
         """one BatchPlan -> the batch dict, queued on the current stream"""
         self.build_store()
-        return self.store.batch(plan.items, plan.aug, self.window, self.pad_mode)
+        return self.store.batch(plan.items, plan.aug, self.window, self.pad_mode, mix=plan.mix)
 
     def __iter__(self):
         self.build_store()
@@ -372,6 +422,12 @@ class AudioSetFeed:
 
 def feed_from_hparams(hparams, split, rank=0, world=1):
     """the feed of one split with the reference's arguments (`audioset_model.py:129-145`): dataset_path, window, batch_size; convert_audio
-    (pretrain_audioset.py --convert_audio), when the namespace has it, is the scan's `convert`"""
+    (pretrain_audioset.py --convert_audio), when the namespace has it, is the scan's `convert`; so are the augmentation flags of the driver:
+    spec_augment with freq_mask_para / time_mask_para / freq_mask_num / time_mask_num, and mixup_alpha (the train split only)"""
     scan = scan_audioset(hparams.dataset_path, split, convert=bool(getattr(hparams, "convert_audio", False)))
-    return AudioSetFeed(scan, hparams.window, hparams.batch_size, split, rank, world)
+    spec_aug = None
+    if getattr(hparams, "spec_augment", False):
+        flags = (("F", "freq_mask_para"), ("T", "time_mask_para"), ("n_freq", "freq_mask_num"), ("n_time", "time_mask_num"))
+        spec_aug = {k: getattr(hparams, flag) for k, flag in flags if hasattr(hparams, flag)}
+    alpha = float(getattr(hparams, "mixup_alpha", 0.0) or 0.0)
+    return AudioSetFeed(scan, hparams.window, hparams.batch_size, split, rank, world, spec_augment=spec_aug, mixup_alpha=alpha)

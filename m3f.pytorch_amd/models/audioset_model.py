@@ -35,10 +35,11 @@ class AudioSet(_Base):
         self.audio = GRU(200, hparams.num_hidden, 2, 527, hparams.num_fc_layers, dropout=True)
         self.history = {'lr': [], 'loss': []}
 
-    def _features(self, x, aug=None, lengths=None):
-        """[N, T, 200] rows; a waveform batch (int16, or 2-D float32 [N, S]) goes through m3t.audio.ingest with hparams.window frames"""
+    def _features(self, x, aug=None, lengths=None, mix=None):
+        """[N, T, 200] rows; a waveform batch (int16, or 2-D float32 [N, S]) goes through m3t.audio.ingest with hparams.window frames
+        (masks in the draws and mix = batch['audio_mix'] = (partner, lam) are applied there; the labels of such a batch come mixed)"""
         if x.dtype == torch.int16 or (x.dtype == torch.float32 and x.dim() == 2):
-            return audio.ingest(x, aug, self.hparams.window, lengths)
+            return audio.ingest(x, aug, self.hparams.window, lengths, mix=mix)
         return x
 
     def forward(self, x, aug=None, lengths=None):
@@ -48,7 +49,7 @@ class AudioSet(_Base):
         return ops.cls_loss(y_hat, y, 'bce')[0]
 
     def training_step(self, batch, batch_idx):
-        x, y = self._features(batch['audio'], batch.get('audio_aug'), batch.get('audio_len')), batch['label']
+        x, y = self._features(batch['audio'], batch.get('audio_aug'), batch.get('audio_len'), batch.get('audio_mix')), batch['label']
         loss, stats, _ = ops.pooled_cls_loss(self.audio(x), y, 'max', 'bce')
         # top-1 accuracy: a 0-dim device tensor (the reference: `.item()`, one host sync per step, audioset_model.py:49)
         acc = float(stats[1]) / x.size(0) if _STEP_SYNC else stats[1] / x.size(0)

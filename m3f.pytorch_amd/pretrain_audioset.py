@@ -15,6 +15,10 @@ m3t/trainer.py and the epoch feed of m3t/audioset.py.
     reader), down-mixed and resampled to 16 kHz on the device when the store is built (m3t.audio.decode_waves); without it such a clip is refused;
   * `--eval_on_device` sends the epoch's validation through Trainer.evaluate_cls (m3t/cls_evaluate.py): the epoch line also gives mean average
     precision, mean ROC-AUC and d' over the classes, scored on the device; `best.ckpt` is still chosen by val_loss.  Without it nothing changes;
+  * `--spec_augment` masks every training clip's dB spectrogram with the reference's own `spec_augment` (`audioset_dataset.py:17-55`;
+    `--freq_mask_para` / `--time_mask_para`, default 20, `--freq_mask_num` / `--time_mask_num`, default 1, at most 4), and `--mixup_alpha A`
+    mixes each training batch with a permutation of itself, weights from Beta(A, A), audio and labels alike; both run inside the ingest's
+    own launches and never touch validation;
   * `--gpus` / `--nodes` are accepted and ignored: start one process per GPU with torchrun and pass `--distributed`; the world is torchrun's;
   * `--workers` is accepted and ignored: there is no host-side decoding left to spread;
   * `--test_lr` (the LR range finder) is out of scope and raises.
@@ -41,6 +45,13 @@ def make_parser():
     parser.add_argument('--checkpoint', type=str, default='')
     parser.add_argument('--convert_audio', action='store_true', default=SUPPRESS)    # (absent unless given: the reference has no such flag)
     parser.add_argument('--eval_on_device', action='store_true', default=SUPPRESS)   # (absent unless given, as --convert_audio)
+    # training-time augmentation of the train feed (m3t/audioset.py); every flag absent unless given: no flag, no change
+    parser.add_argument('--spec_augment', action='store_true', default=SUPPRESS)
+    parser.add_argument('--freq_mask_para', type=float, default=SUPPRESS)
+    parser.add_argument('--time_mask_para', type=float, default=SUPPRESS)
+    parser.add_argument('--freq_mask_num', type=int, default=SUPPRESS)
+    parser.add_argument('--time_mask_num', type=int, default=SUPPRESS)
+    parser.add_argument('--mixup_alpha', type=float, default=SUPPRESS)
     return AudioSet.add_model_specific_args(parser)
 
 
